@@ -11,16 +11,22 @@ Reads are resident in HBM before the timed region starts.
 
 Rank 0 prints ONE JSON line.  Multi-GPU: reads shard embarrassingly (every rank maps its own batch of
 the same size against a replicated index; no data-path collective) -> "scaling": "weak".
-The cpu_baseline leg (rank 0, N=1 only) times the single-threaded CPU oracle on a bounded sample of the
-same workload; it is a reported baseline, not the target.
+A plain run sets up, warms up, times the K steps and prints the line; the roofline and per-kernel figures in it
+come from the timed steps' own hipEvents.  --full adds the measurements that take runs of their own: one step
+under the other remain rule, the device copy rate, and the cpu_baseline legs (rank 0, N=1 only), which time the
+single-threaded CPU oracle on a bounded sample of the same workload (a reported baseline, not the target).
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (see write_outputs).
 """
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -28,6 +34,97 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 GFA = os.path.join(ROOT, "tests", "golden", "data", "DRB1-3123.gfa")
+
+# --dump-outputs: what the last timed step handed back (vga_map_result, vga_align_result), bounded to DUMP_BUDGET bytes
+DUMP_BUDGET = 64 * 1000 * 1000
+DUMP_PER_READ_MAX = 1 << 17  # per-read results: every read up to this many, a seeded sample of this many beyond
+DUMP_SAMPLE_READS = 128  # variable-length results (anchors, chains, paths, CIGAR / cs text): a seeded sample of reads
+DUMP_SEED = 20261016
+
+
+def _view(p, n):
+    """numpy view of n elements of a C array (text as uint8); empty for NULL or n == 0"""
+    if not p or not n:
+        return np.zeros(0, dtype=np.uint8)
+    if isinstance(p, ctypes.POINTER(ctypes.c_char)):
+        p = ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8))
+    return np.ctypeslib.as_array(p, shape=(n,))
+
+
+def capture_outputs(q, r):
+    """Copies the results of one step out of the C structs before they are freed: per-read fields of every read (or of a
+    seeded sample, `read_index`) and the variable-length results of a seeded sample of reads (`sample_reads`), in the order
+    of the sample; the per-read counts split the concatenated arrays.  r is None for the map-only workload."""
+    R = int(q.n_reads)
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(R) if R <= DUMP_PER_READ_MAX else np.sort(rng.choice(R, DUMP_PER_READ_MAX, replace=False))
+    sample = np.sort(rng.choice(R, min(R, DUMP_SAMPLE_READS), replace=False))
+    a_off = _view(q.anchor_off, R + 1).astype(np.int64)
+    c_off = _view(q.chain_off, R + 1).astype(np.int64)
+    ca_off = _view(q.chain_anchor_off, int(q.n_chains) + 1).astype(np.int64)
+    out = {"read_index": rows, "n_anchors": np.diff(a_off)[rows], "n_chains": np.diff(c_off)[rows]}
+    if q.curr_max:
+        out["curr_max"] = _view(q.curr_max, R)[rows].copy()
+    if r is not None:
+        p_off = _view(r.path_off, R + 1).astype(np.int64)
+        g_off = _view(r.cigar_off, R + 1).astype(np.int64)
+        s_off = _view(r.cs_off, R + 1).astype(np.int64)
+        out["path_nodes"] = np.diff(p_off)[rows]
+        out["cigar_len"] = np.diff(g_off)[rows] - 1  # (each string is stored with its terminating NUL)
+        out["cs_len"] = np.diff(s_off)[rows] - 1
+        for f in ("aligned", "path_length", "path_start", "path_end", "block_length", "best_score"):
+            out[f] = _view(getattr(r, f), R)[rows].copy()
+    per_read_bytes = sum(8 * v.size for v in out.values())
+
+    def cost(i):  # bytes of read i's variable-length results once written (float64, text as float32)
+        n_ca = ca_off[c_off[i + 1]] - ca_off[c_off[i]]
+        b = 8 * (3 * (a_off[i + 1] - a_off[i]) + 2 * (c_off[i + 1] - c_off[i]) + n_ca)
+        if r is not None:
+            b += 8 * (p_off[i + 1] - p_off[i]) + 4 * (g_off[i + 1] - g_off[i] + s_off[i + 1] - s_off[i])
+        return int(b)
+
+    room = DUMP_BUDGET - per_read_bytes - 64 * 1024  # (.npy headers)
+    keep = []
+    for i in sample:
+        room -= cost(i)
+        if room < 0:
+            break
+        keep.append(int(i))
+    parts = {k: [] for k in ("anchor_query_begin", "anchor_target_begin", "anchor_target_end", "chain_placeholder",
+                             "chain_n_anchors", "chain_anchor_idx")}
+    if r is not None:
+        parts.update({k: [] for k in ("path_handles", "cigar", "cs")})
+    qb, tb, te = _view(q.query_begin, int(q.n_anchors)), _view(q.target_begin, int(q.n_anchors)), _view(q.target_end, int(q.n_anchors))
+    ph = _view(q.chain_placeholder, int(q.n_chains))
+    cai = _view(q.chain_anchor_idx, int(ca_off[-1]) if len(ca_off) else 0)
+    for i in keep:
+        a0, a1, c0, c1 = a_off[i], a_off[i + 1], c_off[i], c_off[i + 1]
+        parts["anchor_query_begin"].append(qb[a0:a1].copy())
+        parts["anchor_target_begin"].append(tb[a0:a1].copy())  # (bit 31: orientation, include/vga_hip.h)
+        parts["anchor_target_end"].append(te[a0:a1].copy())
+        parts["chain_placeholder"].append(ph[c0:c1].copy())
+        parts["chain_n_anchors"].append(np.diff(ca_off[c0:c1 + 1]))
+        parts["chain_anchor_idx"].append(cai[ca_off[c0]:ca_off[c1]].copy())
+        if r is not None:
+            parts["path_handles"].append(_view(r.path_handles, int(p_off[-1]))[p_off[i]:p_off[i + 1]].copy())
+            parts["cigar"].append(_view(r.cigar, int(g_off[-1]))[g_off[i]:g_off[i + 1] - 1].copy())
+            parts["cs"].append(_view(r.cs, int(s_off[-1]))[s_off[i]:s_off[i + 1] - 1].copy())
+    out["sample_reads"] = np.array(keep, dtype=np.int64)
+    for k, v in parts.items():
+        out["sample_" + k] = np.concatenate(v) if v else np.zeros(0, dtype=np.uint8)
+    return out
+
+
+def write_outputs(d, captured):
+    """DIR/<name>.npy: CIGAR / cs text as float32 character codes, everything else float64 (exact: every integer is below 2^53)"""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in captured.items():
+        a = a.astype(np.float32 if name in ("sample_cigar", "sample_cs") else np.float64)
+        np.save(os.path.join(d, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET, total
+    print("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(captured), total / 1e6, d), file=sys.stderr)
 
 
 def main():
@@ -37,14 +134,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=10000, help="reads per GPU (default: the full config #3 batch)")
     ap.add_argument("--read-len", type=int, default=10000)
-    ap.add_argument("--cpu-sample", type=int, default=40, help="reads of the workload timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=40, help="reads of the workload timed on the CPU oracle with --full (0 = skip)")
     ap.add_argument("--workload", choices=["config2", "config3", "config4", "config5"], default="config3",
                     help="config3 (default, the headline line): DRB1-3123; config4: the 19 merged, sorted HLA-zoo loci; config5: 1 Mbp synthetic "
                          "pangenome (same read model); config2: DRB1-3123, 150 bp reads with 1 %% substitutions, map-only "
                          "(anchor + chain kernels; use --reads 1000 for BASELINE's size).  Extra measurements, not the driver's line")
     ap.add_argument("--remain-rule", type=int, choices=[0, 1], default=None,
                     help="vga_poa_params.remain_rule: 0 longest path, 1 first out-edge (default: the library's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: one step under the other remain rule, the device "
+                         "copy rate, the CPU oracle baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (rank 0) to DIR/<name>.npy, float64 / float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -125,14 +229,21 @@ def main():
     poa_params.remain_rule = args.remain_rule
     if os.environ.get("VGA_BENCH_WF"):  # (diagnostics only: another band -- not the workload BASELINE.json names; the line says so)
         poa_params.wf = float(os.environ["VGA_BENCH_WF"])
-    step = batch.map_raw if map_only else (lambda: batch.map_align_raw(poa_params=poa_params))
+    if map_only:
+        step = lambda on_results=None: batch.map_raw(on_results=on_results)  # noqa: E731
+    else:
+        step = lambda on_results=None: batch.map_align_raw(poa_params=poa_params, on_results=on_results)  # noqa: E731
+    captured = {}
+    dump_hook = None
+    if args.dump_outputs and rank == 0:
+        dump_hook = lambda q, r: captured.update(capture_outputs(q, r))  # noqa: E731
     for _ in range(args.warmup):
         last = step()
     barrier()
     t_start = time.perf_counter()
     kern = {}
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        last = step(dump_hook if i == args.steps - 1 else None)
         for k in last["kernels"]:
             e = kern.setdefault(k["name"], {"ms": 0.0, "launches": 0, "bytes": 0, "busy_ms": 0.0})
             e["ms"] += k["ms"]
@@ -143,11 +254,13 @@ def main():
     elapsed = time.perf_counter() - t_start
     elapsed, aligned_all, reads_all = pkg.sharding.reduce_timing(elapsed, last["aligned"], last["n_reads"], world,
                                                                  device="cuda" if world > 1 and not rehearsal else None)
+    if dump_hook is not None:
+        write_outputs(args.dump_outputs, captured)
 
     # the same batch under the OTHER remain rule (vga_poa_params.remain_rule: the open choice of the POA restatement with first-order
-    # effects on cost), one untimed-region step on rank 0: reported beside the line's value, never part of it
+    # effects on cost), one untimed-region step on rank 0 (--full): reported beside the line's value, never part of it
     other_rule = None
-    if rank == 0 and world == 1 and not map_only and not os.environ.get("VGA_BENCH_NO_OTHER_RULE"):
+    if args.full and rank == 0 and world == 1 and not map_only and not os.environ.get("VGA_BENCH_NO_OTHER_RULE"):
         try:
             pp2 = pkg.default_poa_params()
             pp2.remain_rule = 1 - args.remain_rule
@@ -162,9 +275,9 @@ def main():
             other_rule = {"error": str(e)[:200]}
 
     # measured device-to-device copy rate next to the nominal HBM peak (read + write bytes of 1 GiB copies).  After the timed
-    # region: torch allocations made before it leave less HBM for the library's traceback pool (-10 % on the step)
+    # region: torch allocations made before it leave less HBM for the library's traceback pool (-10 % on the step).  --full only
     copy_gbs = None
-    if rank == 0 and not os.environ.get("VGA_BENCH_NO_COPY"):
+    if args.full and rank == 0 and not os.environ.get("VGA_BENCH_NO_COPY"):
         try:
             n_el = 1 << 28  # 2 x 1 GiB of int32
             a = torch.empty(n_el, dtype=torch.int32, device="cuda").random_(0, 1000)
@@ -267,11 +380,11 @@ def main():
                 pass
 
     # ---- CPU baseline: the oracle on a bounded sample of the same reads (N=1 only), run as a child process that never
-    # touches the GPU: one core (the reference is single-threaded), and the same code over all host cores
+    # touches the GPU: one core (the reference is single-threaded), and the same code over all host cores.  --full only
     cpu = None
     cpu_all = None
     cpu_faithful = None
-    if world == 1 and args.cpu_sample > 0 and not map_only:
+    if args.full and world == 1 and args.cpu_sample > 0 and not map_only:
         import subprocess
         import tempfile
 

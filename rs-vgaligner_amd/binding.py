@@ -302,8 +302,9 @@ class Batch:
         self.ctx._check(L.vga_align_batch(self.h, chains._ptr, best_n, C.byref(p), C.byref(out)))
         return AlignOut(L, out)
 
-    def map_raw(self, map_params: Optional[MapParams] = None) -> dict:
-        """One map-only pass (anchors + chains; BASELINE config #2) without numpy conversion.  Counters only."""
+    def map_raw(self, map_params: Optional[MapParams] = None, on_results=None) -> dict:
+        """One map-only pass (anchors + chains; BASELINE config #2) without numpy conversion.  Counters only;
+        on_results(map_result, None), when given, sees the C result before it is freed (bench.py --dump-outputs)."""
         L = self.ctx.L
         mp = map_params
         if mp is None:
@@ -313,6 +314,8 @@ class Batch:
         self.ctx._check(L.vga_map_batch(self.h, C.byref(mp), C.byref(m)))
         try:
             q = m.contents
+            if on_results is not None:
+                on_results(q, None)
             R = int(q.n_reads)
             ph = np.ctypeslib.as_array(q.chain_placeholder, shape=(int(q.n_chains),)) if int(q.n_chains) else np.zeros(0, np.uint8)
             co = np.ctypeslib.as_array(q.chain_off, shape=(R + 1,)) if R else np.zeros(1, np.uint64)
@@ -325,9 +328,10 @@ class Batch:
             L.vga_map_result_free(m)
 
     def map_align_raw(self, map_params: Optional[MapParams] = None, best_n: int = 1,
-                      poa_params: Optional[PoaParams] = None) -> dict:
+                      poa_params: Optional[PoaParams] = None, on_results=None) -> dict:
         """One pass of the whole hot path without converting the results to numpy (bench.py's timed step).
-        Returns counters only."""
+        Returns counters only; on_results(map_result, align_result), when given, sees the C results before they are
+        freed (bench.py --dump-outputs)."""
         import time as _t
         L = self.ctx.L
         mp = map_params
@@ -355,6 +359,8 @@ class Batch:
                        ms_map=float(q.ms_total), ms_probe=float(q.ms_probe), ms_sort=float(q.ms_sort), ms_chain=float(q.ms_chain),
                        ms_align=float(r.ms_total), ms_subgraph=float(r.ms_subgraph), ms_dp_summed_launches=float(r.ms_dp),
                        ms_traceback=float(r.ms_traceback), kernels=kt_map + kt_aln)
+            if on_results is not None:
+                on_results(q, r)
             t3 = _t.perf_counter()
             L.vga_align_result_free(a)
         finally:

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Collects a round's evidence on the GPU box into gpurun_out/prof_<tag>/ (copy the summaries into profiles/ afterwards with
 # tests/summarize_profiles.py):
-#   1. bench.py plain (the driver's command), 2. the same under rocprofv3 --kernel-trace --stats,
+#   1. bench.py --full (the driver's command plus the CPU baselines summarize_profiles.py reads), 2. bench.py under
+#   rocprofv3 --kernel-trace --stats,
 #   3./4. PMC passes FETCH_SIZE and WRITE_SIZE (separate runs, kernel-trace only), one bench step each,
 #   5. a PMC pass with the instruction counters (SQ_INSTS_*), one bench step.
 # usage (on the GPU box, via gpurun):  bash tests/collect_profiles.sh v7 [--workload config4|config5] [--quick]
@@ -20,8 +21,8 @@ REPO=$GRAFT_REPO_ROOT
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# the counter passes look at the timed step only (bench.py otherwise adds two steps under the other remain rule)
-VGA_TRACE=${VGA_TRACE:-0} timeout -k 10 500 python3 $REPO/bench.py $WL $BENCH_EXTRA > $OUT/bench.json 2> $OUT/bench.err
+# the counter passes look at the timed step only (bench.py --full would add two steps under the other remain rule)
+VGA_TRACE=${VGA_TRACE:-0} timeout -k 10 500 python3 $REPO/bench.py $WL $BENCH_EXTRA --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"; tail -c 600 $OUT/bench.json
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $REPO/bench.py $WL $BENCH_EXTRA --cpu-sample 0 > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
 echo "kernel trace done"

@@ -1,6 +1,6 @@
 """one-off fuzz (not collected by pytest): only_forward = 0 mapping, GPU == oracle on reads of both strands"""
 import os, sys, time, tempfile
-ROOT = "/root/repo" if os.path.isdir("/root/repo/tests") else os.environ.get("GRAFT_REPO_ROOT", ".")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from helpers import DATA, pkg, upload_oracle_index, compare_map
 from oracle import oracle_py as o

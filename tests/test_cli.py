@@ -49,7 +49,10 @@ def test_map_without_a_gpu_fails_loudly(tmp_path):
     pkg()
     d = str(tmp_path)
     run(["index", "-i", os.path.join(DATA, "test.gfa"), "-k", "11", "-o", os.path.join(d, "t")], d)
-    p = subprocess.run([EXE, "map", "-i", os.path.join(d, "t"), "-f", os.path.join(DATA, "single-read-test.fa"), "-p", "abpoa"],
+    # a copy of the reads: the default output prefix is the reads path, and a GPU run writes its GAF files there
+    fa = os.path.join(d, "single-read-test.fa")
+    open(fa, "w").write(open(os.path.join(DATA, "single-read-test.fa")).read())
+    p = subprocess.run([EXE, "map", "-i", os.path.join(d, "t"), "-f", fa, "-p", "abpoa"],
                        cwd=d, capture_output=True, text=True, timeout=600)
     if p.returncode == 0:
         pytest.skip("a GPU is present")
