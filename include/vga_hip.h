@@ -93,6 +93,21 @@ typedef struct {
  * (src/index.rs:296-305, 309-382, 388-606): copies the index to HBM once. */
 int vga_index_upload(vga_ctx *ctx, const vga_index_desc *desc);
 
+/* Stands in for generate_kmers_parallel + sort/dedup + generate_pos_on_ref_2 of Index::build
+ * (src/index.rs:162-220, src/kmer.rs:277-505, 816-928).  Reads the graph half of *desc (kmer_length, seq_length,
+ * seq_fwd, n_nodes, node_seq_idx / node_edge_idx / node_edges_to, n_edges, edges) and fills its k-mer half
+ * (n_kmers, kmer_keys, kmer_starts, n_kmer_pos, kmer_pos_table) with arrays the library allocates; release them with
+ * vga_index_kmers_free.  On VGA_OK the context also holds the index, exactly as after vga_index_upload(ctx, desc), with
+ * the probe tables built on the device.  The arrays equal the host builder's byte for byte.
+ * VGA_ERR_UNSUPPORTED: k = 0 or k > 15, a byte of seq_fwd outside upper-case ACGTN, an empty node, a graph beyond 32-bit
+ * device coordinates.  VGA_ERR_NOMEM (with a message, never a fault) when the k-mer paths blow up.  A graph with no
+ * k-mer of this length fails with the host's message.  On failure the context holds no index.  With ctx == NULL:
+ * VGA_ERR_NO_DEVICE when no GPU is visible (there is no CPU path).
+ * (ABI 6 gained these two calls; no existing signature changed.) */
+int vga_index_build_kmers(vga_ctx *ctx, vga_index_desc *desc, uint64_t max_furcations, uint64_t max_degree);
+/* frees the five k-mer fields vga_index_build_kmers filled and zeroes them */
+void vga_index_kmers_free(vga_index_desc *desc);
+
 /* ---- read batches -------------------------------------------------------------------------- */
 typedef struct vga_batch vga_batch;
 /* reads_concat: all read sequences back to back; read_off[i]..read_off[i+1] delimits read i

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "vga_map_result_free", "vga_poa_default_params", "vga_poa_result_free", "vga_poa_batch", "vga_align_batch",
     "vga_align_result_free", "vga_last_kernel_times", "vga_chain_paths_text", "vga_chain_text_free",
     "vga_align_prepare", "vga_ctx_set_pool_fraction", "vga_ctx_set_host_threads",
+    "vga_index_build_kmers", "vga_index_kmers_free",
 ]
 
 
@@ -149,8 +150,42 @@ def load_library():
     L.vga_ctx_set_host_threads.argtypes = [vp, C.c_uint32]
     L.vga_ctx_set_host_threads.restype = C.c_int
     L.vga_chain_text_free.argtypes = [_P(ChainText)]
+    L.vga_index_build_kmers.argtypes = [vp, _P(IndexDesc), C.c_uint64, C.c_uint64]
+    L.vga_index_build_kmers.restype = C.c_int
+    L.vga_index_kmers_free.argtypes = [_P(IndexDesc)]
+    L.vga_index_kmers_free.restype = None
     _lib = L
     return L
+
+
+def graph_desc(k: int, seq_fwd: bytes, node_seq_idx, node_edge_idx, node_edges_to, edges) -> IndexDesc:
+    """an IndexDesc with the graph half filled and the k-mer half empty (the input of vga_index_build_kmers); the numpy
+    arrays it points into are kept on the returned object"""
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (node_seq_idx, node_edge_idx, node_edges_to, edges)]
+    d = IndexDesc()
+    d._keep = (seq_fwd, a)
+    d.kmer_length = k
+    d.seq_length = len(seq_fwd)
+    d.seq_fwd = seq_fwd
+    d.n_nodes = len(a[0]) - 1
+    d.node_seq_idx, d.node_edge_idx, d.node_edges_to = _u64p(a[0]), _u64p(a[1]), _u64p(a[2])
+    d.n_edges = len(a[3])
+    d.edges = _u64p(a[3])
+    return d
+
+
+def kmer_arrays(d: IndexDesc) -> dict:
+    """numpy copies of the k-mer half of a vga_index_desc"""
+    k, nk, npos = int(d.kmer_length), int(d.n_kmers), int(d.n_kmer_pos)
+    tab = (np.ctypeslib.as_array(C.cast(d.kmer_pos_table, _P(C.c_uint8)), shape=(npos * C.sizeof(KmerPos),)).copy().view(KMERPOS_DTYPE)
+           if npos else np.zeros(0, KMERPOS_DTYPE))
+    return dict(kmer_keys=C.string_at(d.kmer_keys, nk * k) if nk else b"", kmer_starts=_np(d.kmer_starts, nk, np.uint64),
+                kmer_pos_table=tab)
+
+
+def index_kmers_free(d: IndexDesc) -> None:
+    """vga_index_kmers_free: releases the k-mer half vga_index_build_kmers filled and zeroes it"""
+    load_library().vga_index_kmers_free(C.byref(d))
 
 
 def _np(ptr, n, dtype):
@@ -427,6 +462,11 @@ class Context:
         d.n_kmer_pos = len(tab)
         d.kmer_pos_table = tab.ctypes.data_as(_P(KmerPos))
         self._check(self.L.vga_index_upload(self.h, C.byref(d)))
+
+    def index_build_kmers(self, desc: IndexDesc, max_furcations: int = 100, max_degree: int = 100) -> None:
+        """vga_index_build_kmers: fills the k-mer half of `desc` (release it with index_kmers_free) and leaves this
+        context holding the index"""
+        self._check(self.L.vga_index_build_kmers(self.h, C.byref(desc), int(max_furcations), int(max_degree)))
 
     def batch(self, seqs: Sequence[str]) -> Batch:
         return Batch(self, seqs)

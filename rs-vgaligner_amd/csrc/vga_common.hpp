@@ -115,6 +115,9 @@ struct vga_batch {
 };
 
 int vga_set_error(vga_ctx *ctx, int code, const char *fmt, ...);
+// frees the context's index (loaded = false); vga_index_load_graph: the graph half of a vga_index_desc onto the context
+void vga_index_release(vga_dev_index &ix);
+int vga_index_load_graph(vga_ctx *ctx, const vga_index_desc *d);
 
 #define VGA_HIP_CHECK(ctx, call)                                                               \
     do {                                                                                       \

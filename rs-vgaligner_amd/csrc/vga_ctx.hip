@@ -142,7 +142,7 @@ extern "C" int vga_ctx_create(int device, vga_ctx **out)
     return VGA_OK;
 }
 
-static void vga_index_release(vga_dev_index &ix)
+void vga_index_release(vga_dev_index &ix)
 {
     if (ix.d_table) (void)hipFree(ix.d_table);
     if (ix.d_pos) (void)hipFree(ix.d_pos);
@@ -297,6 +297,41 @@ static inline int vga_base_code(char c)
     }
 }
 
+// The graph half of *d on the context: the host copies and the device buffers of the subgraph extraction (and of the
+// device index build, vga_index.hip).
+int vga_index_load_graph(vga_ctx *ctx, const vga_index_desc *d)
+{
+    vga_dev_index &ix = ctx->index;
+    ix.seq_length = d->seq_length;
+    ix.n_nodes = d->n_nodes;
+    ix.n_edges = d->n_edges;
+    ix.seq_fwd.assign(d->seq_fwd, d->seq_fwd + d->seq_length);
+    ix.node_start.resize(d->n_nodes + 1);
+    ix.edge_idx.resize(d->n_nodes + 1);
+    ix.edges_to.resize(d->n_nodes + 1);
+    for (uint64_t i = 0; i <= d->n_nodes; i++) {
+        ix.node_start[i] = (uint32_t)d->node_seq_idx[i];
+        ix.edge_idx[i] = (uint32_t)d->node_edge_idx[i];
+        ix.edges_to[i] = (uint32_t)d->node_edges_to[i];
+    }
+    ix.edges.resize(d->n_edges);
+    for (uint64_t i = 0; i < d->n_edges; i++) ix.edges[i] = (uint32_t)d->edges[i];
+    const size_t nn1 = (size_t)d->n_nodes + 1;
+    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_seq_fwd, d->seq_length + 16));
+    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_node_start, nn1 * sizeof(uint32_t)));
+    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edge_idx, nn1 * sizeof(uint32_t)));
+    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edges_to, nn1 * sizeof(uint32_t)));
+    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edges, (d->n_edges + 1) * sizeof(uint32_t)));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_seq_fwd, ix.seq_fwd.data(), d->seq_length, hipMemcpyHostToDevice, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_node_start, ix.node_start.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edge_idx, ix.edge_idx.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edges_to, ix.edges_to.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (d->n_edges)
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edges, ix.edges.data(), d->n_edges * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VGA_OK;
+}
+
 static int vga_index_upload_impl(vga_ctx *ctx, const vga_index_desc *d)
 {
     if (!ctx || !d) return VGA_ERR_ARG;
@@ -313,20 +348,6 @@ static int vga_index_upload_impl(vga_ctx *ctx, const vga_index_desc *d)
     vga_index_release(ctx->index);
     vga_dev_index &ix = ctx->index;
     ix.k = d->kmer_length;
-    ix.seq_length = d->seq_length;
-    ix.n_nodes = d->n_nodes;
-    ix.n_edges = d->n_edges;
-    ix.seq_fwd.assign(d->seq_fwd, d->seq_fwd + d->seq_length);
-    ix.node_start.resize(d->n_nodes + 1);
-    ix.edge_idx.resize(d->n_nodes + 1);
-    ix.edges_to.resize(d->n_nodes + 1);
-    for (uint64_t i = 0; i <= d->n_nodes; i++) {
-        ix.node_start[i] = (uint32_t)d->node_seq_idx[i];
-        ix.edge_idx[i] = (uint32_t)d->node_edge_idx[i];
-        ix.edges_to[i] = (uint32_t)d->node_edges_to[i];
-    }
-    ix.edges.resize(d->n_edges);
-    for (uint64_t i = 0; i < d->n_edges; i++) ix.edges[i] = (uint32_t)d->edges[i];
 
     // Build the probe tables on the host, then copy once: the forward/forward records only (what map_reads asks for,
     // src/map.rs:62) and, for k <= 13, every record with the orientations of its two ends in bit 31 of the positions
@@ -396,20 +417,7 @@ static int vga_index_upload_impl(vga_ctx *ctx, const vga_index_desc *d)
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_pos_all, pos.data(), pos.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
         VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    // the graph for the device-side subgraph extraction
-    const size_t nn1 = (size_t)d->n_nodes + 1;
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_seq_fwd, d->seq_length + 16));
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_node_start, nn1 * sizeof(uint32_t)));
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edge_idx, nn1 * sizeof(uint32_t)));
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edges_to, nn1 * sizeof(uint32_t)));
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_edges, (d->n_edges + 1) * sizeof(uint32_t)));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_seq_fwd, ix.seq_fwd.data(), d->seq_length, hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_node_start, ix.node_start.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edge_idx, ix.edge_idx.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edges_to, ix.edges_to.data(), nn1 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (d->n_edges)
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_edges, ix.edges.data(), d->n_edges * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = vga_index_load_graph(ctx, d)) return rc;
     ix.loaded = true;
     return VGA_OK;
 }

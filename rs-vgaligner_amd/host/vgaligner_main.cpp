@@ -21,7 +21,9 @@ const Flag INDEX_FLAGS[] = {{"-i", "--input", true, "input"}, {"-o", "--output",
                             {"-r", "--sampling-rate", true, "sampling-rate"}, {"-g", "--generate-mappings", false, "generate-mappings"},
                             {"-p", "--mappings-path", true, "mappings-path"}, {"-t", "--threads", true, "n-threads"},
                             // the argument names, accepted as long flags too
-                            {"", "--out-prefix", true, "out-prefix"}, {"", "--n-threads", true, "n-threads"}};
+                            {"", "--out-prefix", true, "out-prefix"}, {"", "--n-threads", true, "n-threads"},
+                            // not in the reference: build the k-mer half of the index on this GPU (vga_index_build_kmers)
+                            {"-d", "--device", true, "device"}};
 const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file", true, "input-file"}, {"-o", "--out", true, "out-prefix"},
                           {"-g", "--max-gap-length", true, "max-gap-length"}, {"-r", "--max-mismatch-rate", true, "max-mismatch-rate"},
                           {"-c", "--chain-overlap-max", true, "chain-overlap-max"}, {"-a", "--chain-min-anchors", true, "chain-min-anchors"},
@@ -73,7 +75,23 @@ int index_main(int argc, char **argv)
     uint64_t furc = std::stoull(opt(m, "max-furcations", "100")), deg = std::stoull(opt(m, "max-degree", "100"));
     if (m.count("sampling-rate")) throw Error("--sampling-rate depends on ahash's hash values and is not supported");
     if (m.count("generate-mappings")) fprintf(stderr, "[vgaligner] --generate-mappings (debug JSON) is not produced by this build\n");
-    Index ix = Index::build(HashGraph::from_gfa(in), k, furc, deg);
+    Index ix;
+    if (m.count("device")) {  // same index, same file: only where the k-mers are enumerated and sorted changes
+        const int dev = std::stoi(m["device"]);
+        vga_ctx *ctx = nullptr;
+        if (int rc = vga_ctx_create(dev, &ctx))
+            throw Error("--device " + std::to_string(dev) + ": vga_ctx_create failed (" +
+                        (rc == VGA_ERR_NO_DEVICE ? std::string("VGA_ERR_NO_DEVICE: no usable MI355X") : "error " + std::to_string(rc)) +
+                        "); the GPU index build has no CPU path");
+        try {
+            ix = Index::build_on_device(HashGraph::from_gfa(in), k, furc, deg, ctx);
+        } catch (...) {
+            vga_ctx_destroy(ctx);
+            throw;
+        }
+        vga_ctx_destroy(ctx);
+    } else
+        ix = Index::build(HashGraph::from_gfa(in), k, furc, deg);
     fprintf(stderr, "[vgaligner] Index with k=%llu built: %llu different kmers, %llu positions\n", (unsigned long long)k,
             (unsigned long long)ix.n_kmers, (unsigned long long)ix.n_kmer_pos);
     bool exact = prefix.size() >= 4 && prefix.compare(prefix.size() - 4, 4, ".idx") == 0;  // index.rs:267-278
@@ -175,7 +193,7 @@ int main(int argc, char **argv)
     try {
         if (argc >= 2 && !strcmp(argv[1], "index")) return index_main(argc, argv);
         if (argc >= 2 && !strcmp(argv[1], "map")) return map_main(argc, argv);
-        fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100]\n"
+        fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n");
         return 2;

@@ -74,6 +74,8 @@ struct Index {
     std::vector<vga_kmerpos> kmer_pos_table;
 
     static Index build(const HashGraph &g, uint64_t kmer_length, uint64_t max_furcations, uint64_t max_degree);
+    // the same index with the k-mer half built on the GPU of `ctx` (vga_index_build_kmers), which keeps it loaded
+    static Index build_on_device(const HashGraph &g, uint64_t kmer_length, uint64_t max_furcations, uint64_t max_degree, vga_ctx *ctx);
     // own container format ("VGAIDX1"); the reference's bincode .idx needs boomphf/bv/ahash internals
     void store(const std::string &path) const;
     static Index load(const std::string &path);

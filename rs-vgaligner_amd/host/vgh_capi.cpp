@@ -35,6 +35,17 @@ void *vgh_index_build_from_gfa(const char *gfa, uint64_t k, uint64_t max_furcati
     } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 
+// the same with Index::build_on_device: the k-mer half on the GPU of ctx, which then holds the index
+void *vgh_index_build_from_gfa_on_device(const char *gfa, uint64_t k, uint64_t max_furcations, uint64_t max_degree, vga_ctx *ctx)
+{
+    try {
+        IndexBox *b = new IndexBox();
+        b->ix = Index::build_on_device(HashGraph::from_gfa(gfa), k, max_furcations, max_degree, ctx);
+        b->ix.describe(b->desc, b->scratch);
+        return b;
+    } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+
 void *vgh_index_load(const char *path)
 {
     try {

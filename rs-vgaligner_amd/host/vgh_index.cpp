@@ -8,9 +8,11 @@
 //   generate_kmers_parallel ............... src/kmer.rs:277-505
 //   generate_pos_on_ref_2 ................. src/kmer.rs:752-770, 816-928
 //   Index::build .......................... src/index.rs:109-281
+//   Index::build_on_device ................ the same, its k-mer half from vga_index_build_kmers (csrc/vga_index.hip)
 #include "vgh.hpp"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -205,7 +207,8 @@ bool kmers_from_handle(const HashGraph &g, Handle start, bool orient, uint64_t k
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ Index
-Index Index::build(const HashGraph &g, uint64_t k, uint64_t max_furcations, uint64_t max_degree)
+// The graph half of Index::build: everything but the k-mers (src/index.rs:109-161, utils.rs:81-146, dna.rs:5-33).
+static Index graph_half(const HashGraph &g, uint64_t k)
 {
     if (k == 0) throw Error("kmer_length must be > 0");
     // NodeRef is addressed by id-1 (src/index.rs:489-491): ids must be exactly 1..n
@@ -240,6 +243,12 @@ Index Index::build(const HashGraph &g, uint64_t k, uint64_t max_furcations, uint
         }
         ix.seq_rev[i] = c;
     }
+    return ix;
+}
+
+Index Index::build(const HashGraph &g, uint64_t k, uint64_t max_furcations, uint64_t max_degree)
+{
+    Index ix = graph_half(g, k);
     // src/kmer.rs:277-304
     std::vector<GraphKmer> kmers;
     for (uint64_t id = 1; id <= g.max_id; id++)
@@ -282,6 +291,29 @@ Index Index::build(const HashGraph &g, uint64_t k, uint64_t max_furcations, uint
     }
     ix.n_kmers = ix.kmer_starts.size();
     ix.n_kmer_pos = ix.kmer_pos_table.size();
+    // the 6 padding bytes after end_orient go into the .idx file as they are: zero them, so that one graph always gives
+    // the same file (the device builder writes them as zeros too)
+    for (vga_kmerpos &p : ix.kmer_pos_table) memset((char *)&p + offsetof(vga_kmerpos, end_orient) + 1, 0, sizeof p - offsetof(vga_kmerpos, end_orient) - 1);
+    return ix;
+}
+
+Index Index::build_on_device(const HashGraph &g, uint64_t k, uint64_t max_furcations, uint64_t max_degree, vga_ctx *ctx)
+{
+    Index ix = graph_half(g, k);
+    DescScratch s;
+    vga_index_desc d;
+    ix.describe(d, s);
+    const int rc = vga_index_build_kmers(ctx, &d, max_furcations, max_degree);
+    if (rc != VGA_OK) {
+        if (rc == VGA_ERR_NO_DEVICE || !ctx) throw Error("vga_index_build_kmers: no usable MI355X (VGA_ERR_NO_DEVICE); the library has no CPU path");
+        throw Error(vga_last_error(ctx));
+    }
+    ix.kmer_keys.assign(d.kmer_keys, d.n_kmers * k);
+    ix.kmer_starts.assign(d.kmer_starts, d.kmer_starts + d.n_kmers);
+    ix.kmer_pos_table.assign(d.kmer_pos_table, d.kmer_pos_table + d.n_kmer_pos);
+    ix.n_kmers = d.n_kmers;
+    ix.n_kmer_pos = d.n_kmer_pos;
+    vga_index_kmers_free(&d);
     return ix;
 }
 

@@ -27,6 +27,8 @@ def load_library():
     L.vgh_last_error.restype = C.c_char_p
     L.vgh_index_build_from_gfa.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64]
     L.vgh_index_build_from_gfa.restype = vp
+    L.vgh_index_build_from_gfa_on_device.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, vp]
+    L.vgh_index_build_from_gfa_on_device.restype = vp
     L.vgh_index_load.argtypes = [C.c_char_p]
     L.vgh_index_load.restype = vp
     L.vgh_index_store.argtypes = [vp, C.c_char_p]
@@ -67,9 +69,15 @@ class HostIndex:
         self.h = handle
 
     @classmethod
-    def build_from_gfa(cls, gfa: str, k: int, max_furcations: int = 100, max_degree: int = 100) -> "HostIndex":
+    def build_from_gfa(cls, gfa: str, k: int, max_furcations: int = 100, max_degree: int = 100,
+                       ctx: Optional[binding.Context] = None) -> "HostIndex":
+        """ctx: build the k-mer half on that context's GPU (vga_index_build_kmers, the same arrays); the context then
+        holds the index, as after upload()"""
         L = load_library()
-        h = L.vgh_index_build_from_gfa(gfa.encode(), k, max_furcations, max_degree)
+        if ctx is not None:
+            h = L.vgh_index_build_from_gfa_on_device(gfa.encode(), k, max_furcations, max_degree, ctx.h)
+        else:
+            h = L.vgh_index_build_from_gfa(gfa.encode(), k, max_furcations, max_degree)
         if not h:
             raise HostError(L.vgh_last_error().decode())
         return cls(h)
