@@ -73,6 +73,15 @@ __device__ __forceinline__ T *t5_own(T *p) { return (T *)t5_own((uint64_t)p); }
 // (the read-only inputs stay kernel parameters of their own: only a __restrict__ PARAMETER tells the compiler that no store of
 // the kernel can change them, which is what lets their loads be scalar loads)
 #define POA_T5_ARGS_OFFSET 40  // the struct's place in the kernarg segment: behind the five pointers
+// The launch arguments read again where a rare path needs them (chunk refill, pool growth, the epilogue): scalar loads out of the
+// kernarg segment, through a pointer the compiler cannot follow back to the kernel's entry -- so it cannot hoist the loads there
+// and keep what they return live over the row loop, in spill lanes that every row reloads from
+__device__ __forceinline__ const poa_t5_args *t5_kargs()
+{
+    uint32_t off = POA_T5_ARGS_OFFSET;
+    asm volatile("" : "+s"(off));  // (the offset, not the pointer: a pointer through an asm operand loses its address space)
+    return (const poa_t5_args *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
 template <int NT, bool DEF>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5)))  // (at most 96 vector registers: five waves per SIMD)
 void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ queries,
@@ -81,8 +90,6 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
 {
     poa_row *rows = A.rows;
     uint8_t *pool_arg = A.pool;
-    unsigned long long *pool_next_arg = A.pool_next;
-    const uint64_t pool_size_arg = A.pool_size;
     const uint32_t lds_cols = t5_own(A.lds_cols), hg_cols = t5_own(A.hg_cols), win_mask = t5_own(A.win_mask);
     // Conditions that hold for the whole problem or are carried from row to row live as bits of ONE scalar register, laundered at
     // the top of every row: as `bool`s the compiler keeps each of them as a 64-bit lane mask (two scalar registers, or two
@@ -125,9 +132,6 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
     // (vga_poa_kernels.hpp: a state region for what must be contiguous, 1 MiB chunks for the direction rows; offsets are
     // device addresses, pool base 0)
     uint8_t *pool = pool_arg;
-    unsigned long long *pool_next = pool_next_arg;
-    uint64_t pool_size = pool_size_arg;
-    uint32_t state_slot = 0;
     uint64_t state_lo = 0, state_hi = 0;
     if (chunked) {
         int got = -1;
@@ -148,12 +152,10 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
             return;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        state_slot = (uint32_t)got;
         pool = nullptr;
-        state_lo = (uint64_t)A.cp.state_base + (uint64_t)state_slot * A.cp.state_size;
+        state_lo = (uint64_t)A.cp.state_base + (uint64_t)(uint32_t)got * A.cp.state_size;  // (the epilogue finds the slot in sSink[1] again)
         state_hi = state_lo + A.cp.state_size;
     }
-    pool_size = t5_own(pool_size);
 
     const int o1 = DEF ? 4 : P.o1, e1 = DEF ? 2 : P.e1, o2 = DEF ? 24 : P.o2, e2 = DEF ? 1 : P.e2;
     // Row state of this kernel (its own: k_poa_dp_t4's differs by one): a cell's word is 4 H + 1, its gap bytes are
@@ -172,7 +174,9 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
     // larger than a chunk takes whole chunks of its own.  A new chunk is taken by one lane and handed round through LDS:
     // every wave reaches this branch in the same row (the condition only depends on replicated state), `slot` keeps the
     // two requests of one row apart.
-    uint32_t own_head = POA_NIL, own_tail = POA_NIL, own_chunks = 0;  // chunk pool: the chunks this workgroup holds (a list through cp.next)
+    // chunk pool: the chunks this workgroup holds, a list through cp.next (the first one taken, the list's tail, waits in sChunk[3]
+    // for the epilogue)
+    uint32_t own_head = POA_NIL, own_chunks = 0;
     // (`rem`: the bytes left of the piece `cur` points into -- a 32-bit count, so that the test of every row is one scalar compare;
     // a 64-bit "cur + bytes > end" goes through the vector ALU.  No request reaches 4 GiB: a row has at most 2^24 + 8 columns of
     // at most 6 bytes, the ring at most POA_RING_SPAN + 1 = 33 such rows, 3.3 GB.)
@@ -182,9 +186,11 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
             if (chunked) {
                 if (slot == 0 && bytes <= POA_CHUNK) {
                     // direction rows: the next chunk from the free list, chained in front of the ones this workgroup holds
+                    const poa_t5_args *ka = t5_kargs();
                     if (tid == 0) {
-                        const uint32_t idx = poa_chunk_pop(A.cp, blockIdx.x);
-                        if (idx != POA_NIL) __hip_atomic_store(A.cp.next + idx, own_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const uint32_t idx = poa_chunk_pop(ka->cp, blockIdx.x);
+                        if (idx != POA_NIL) __hip_atomic_store(ka->cp.next + idx, own_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (own_chunks == 0) sChunk[3] = idx;
                         sChunk[0] = idx;
                     }
                     __syncthreads();
@@ -193,9 +199,8 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
                     if (idx == POA_NIL) st |= ST_FAILED;
                     else {
                         own_head = idx;
-                        if (own_tail == POA_NIL) own_tail = idx;
                         own_chunks++;
-                        cur = poa_uniform_u64(poa_chunk_addr(A.cp, idx));
+                        cur = poa_uniform_u64(poa_chunk_addr(ka->cp, idx));
                         rem = (uint32_t)POA_CHUNK;
                     }
                 } else
@@ -203,11 +208,12 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
                 if (failed) return cur;
             } else {
                 const uint64_t need = bytes > POA_CHUNK ? ((uint64_t)bytes + POA_CHUNK - 1) & ~(POA_CHUNK - 1) : POA_CHUNK;
-                if (tid == 0) sChunk[slot] = atomicAdd(pool_next, (unsigned long long)need);
+                const poa_t5_args *ka = t5_kargs();
+                if (tid == 0) sChunk[slot] = atomicAdd(ka->pool_next, (unsigned long long)need);
                 __syncthreads();
                 const uint64_t b = t5_uniform64(sChunk[slot]);
                 __syncthreads();  // (rare path: the slot may be written again as soon as every wave has read it)
-                if (b + need > pool_size) st |= ST_FAILED;
+                if (b + need > ka->pool_size) st |= ST_FAILED;
                 cur = b;
                 rem = (uint32_t)need;
             }
@@ -241,19 +247,18 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
     uint64_t dcur = 0, vcur = state_lo, wide_scratch = 0, ring_base = 0;
     uint32_t dend = 0, vendp = (uint32_t)(state_hi - state_lo);  // (bytes left, see alloc)
     uint32_t ring_head = 0;  // the slot the next node-end row takes
-    uint32_t ring_size;      // bytes per slot of the ring: one worst-case row
+    // (bytes per slot of the ring -- one worst-case row, (6 ((qlen + 8) & ~3) + 15) & ~15 -- are derived from qlen where used)
     if (win_mask != 0xFFFFFFFFu) wide_scratch = alloc(vcur, vendp, 2u * 6u * lds_cols, 1);
     {
         const uint64_t maxrow = (6ull * (uint64_t)((qlen + 8) & ~3) + 15ull) & ~15ull;
-        ring_size = (uint32_t)maxrow;
         if (chunked) {
             ring_base = alloc(vcur, vendp, (uint32_t)(maxrow * (uint64_t)ring_rows), 1);  // (out of the state region)
         } else {
             const uint64_t rb = (maxrow * (uint64_t)ring_rows + POA_CHUNK - 1) & ~(POA_CHUNK - 1);
-            if (tid == 0) sChunk[2] = atomicAdd(pool_next, (unsigned long long)rb);
+            if (tid == 0) sChunk[2] = atomicAdd(A.pool_next, (unsigned long long)rb);
             __syncthreads();
             const uint64_t b = t5_uniform64(sChunk[2]);
-            if (b + rb > pool_size || rb >= (1ull << 32)) st |= ST_FAILED;
+            if (b + rb > A.pool_size || rb >= (1ull << 32)) st |= ST_FAILED;
             ring_base = b;
         }
     }
@@ -401,16 +406,19 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
             else {
                 // fixed slots of one worst-case row: the rows of the last ring_rows node ends survive whatever their
                 // widths (a byte ring that wraps when a row does not fit can overwrite the row written two slots ago)
-                voff = ring_base + (uint64_t)ring_head * ring_size;
+                voff = ring_base + (uint64_t)ring_head * ((6u * (uint32_t)((qlen + 8) & ~3) + 15u) & ~15u);
                 ring_head = ring_head + 1 == ring_rows ? 0 : ring_head + 1;
             }
         } else if (wide) voff = wide_scratch + (r & 1u) * 6ull * lds_cols;
         if (__builtin_expect(failed, 0)) break;
         if (writer && lane == 0) {
-            R[r].beg = beg; R[r].end = end;
-            R[r].doff = doff; R[r].voff = voff;
-            R[r].pred = ps; R[r].npred = first ? (uint32_t)np : 0u;
-            R[r].base = keep ? 1 : 0;  // (the counters of the result are summed up from the records at the end)
+            // the fields this row sets, as three vector stores off one address: {beg, end, doff} | voff | {pred, npred, base}
+            // (lmax / rmax are stored by the next row, hmax is not k_poa_dp_t5's)
+            uint32_t *rec = (uint32_t *)(R + r);
+            *(uint4 *)rec = make_uint4((uint32_t)beg, (uint32_t)end, (uint32_t)doff, (uint32_t)(doff >> 32));
+            *(uint2 *)(rec + 4) = make_uint2((uint32_t)voff, (uint32_t)(voff >> 32));
+            // (the counters of the result are summed up from the records at the end: base = 1 marks a kept value row)
+            *(HIP_vector_type<uint32_t, 3> *)(rec + 8) = HIP_vector_type<uint32_t, 3>(ps, first ? (uint32_t)np : 0u, keep ? 1u : 0u);
         }
         uint8_t *Vrow = pool + voff;
         uint8_t *drow = pool + doff;
@@ -1039,12 +1047,11 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
         st = (st & ~(ST_PREV_LDS | ST_PREV_FAR_USE)) | (wide ? 0u : ST_PREV_LDS) | (last ? ST_PREV_FAR_USE : 0u);  // (row 0 is the last row of the source entry)
     }
     }
+    POA_MARK("epilogue");
     __syncthreads();
     if (tid >= 64) return;
     // ---- epilogue, first wave: everything it needs is read again (nothing of it was kept in registers over the rows)
-    const poa_t5_args *ap = (const poa_t5_args *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + POA_T5_ARGS_OFFSET);
-    asm volatile("" : "+s"(ap));
-    const poa_t5_args E = *ap;
+    const poa_t5_args E = *t5_kargs();
     const poa_prob pe = E.probs[blockIdx.x];
     poa_out &O = E.outs[blockIdx.x];
     int status = POA_ST_OK;
@@ -1089,7 +1096,9 @@ void k_poa_dp_t5(const poa_prob *__restrict__ probs, const char *__restrict__ qu
         O.t_end = __builtin_amdgcn_s_memrealtime();
         if (E.cp.n_slots) {
             // the chunks go back in one step, then the state region; what this problem took feeds the host's footprint scale
-            if (own_head != POA_NIL) poa_chunk_push(E.cp, blockIdx.x, own_head, own_tail);
+            const uint32_t state_slot = (uint32_t)sSink[1];
+            if (own_head != POA_NIL) poa_chunk_push(E.cp, blockIdx.x, own_head, (uint32_t)sChunk[3]);
+            const uint64_t state_lo = (uint64_t)E.cp.state_base + (uint64_t)state_slot * E.cp.state_size;
             (void)atomicAdd(E.pool_next, (unsigned long long)own_chunks * POA_CHUNK + (vcur - state_lo));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             (void)atomicExch(&E.cp.slot_flag[state_slot], 0u);
