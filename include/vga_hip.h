@@ -132,7 +132,18 @@ typedef struct {
                                    * 0: anchor_id / max_chain_score / best_pred_id are NULL -- the GAF writers and
                                    *    vga_align_batch only read the anchor coordinates and the chain membership, and
                                    *    16 of the 40 bytes per anchor stay on the GPU. */
+    int32_t strands;              /* VGA_STRANDS_*: which orientations of each read are mapped (not in the reference, whose
+                                   * map.rs looks at the read as given).  It occupies what was tail padding: size and offsets
+                                   * are unchanged.  VGA_ERR_ARG for any other value; BOTH needs only_forward = 1
+                                   * (VGA_ERR_UNSUPPORTED otherwise). */
 } vga_map_params;
+/* FORWARD: the read as given (the default).  BOTH: the read and its reverse complement (each byte through the reference's
+ * switch_base, src/dna.rs:20-33, any byte outside it becoming N) are mapped alike; per read the orientation whose chaining
+ * optimum curr_max is larger wins (vga_map_result.strand), a tie going to the read as given, and a side with only the
+ * placeholder chain never winning.  Every per-read field of the result then describes the chosen orientation only, in its
+ * own frame: query coordinates of a reverse read count from the start of its reverse complement. */
+#define VGA_STRANDS_FORWARD 0
+#define VGA_STRANDS_BOTH 1
 void vga_map_default_params(vga_map_params *p);
 
 /* Result of anchors_for_query + chain_anchors for every read of a batch.
@@ -158,7 +169,9 @@ typedef struct {
     uint32_t *chain_anchor_idx; /* index (within the read's sorted anchors) of each chain member, ascending */
     /* timing of the last call, milliseconds, measured with hipEvents on the ctx stream */
     float ms_probe, ms_sort, ms_chain, ms_total;
-    uint64_t n_hits;            /* position records touched (H of the byte model) */
+    uint64_t n_hits;            /* position records touched (H of the byte model); with VGA_STRANDS_BOTH, of both orientations */
+    uint8_t *strand;            /* n_reads: 0 the read as given, 1 its reverse complement (VGA_STRANDS_BOTH); NULL otherwise.
+                                 * vga_align_batch aligns the chosen orientation against the forward graph. */
 } vga_map_result;
 
 /* Stands in for the pass-1 loop of map_reads: anchors_for_query (src/map.rs:62 -> src/chain.rs:134)

@@ -16,6 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VGA_LIB") or os.path.join(_HERE, "libvga_hip.so")  # VGA_LIB: another build of the library (same-box A/B runs)
 
 VGA_OK = 0
+# vga_map_params.strands
+VGA_STRANDS_FORWARD = 0
+VGA_STRANDS_BOTH = 1
 ERR_NAMES = {-1: "VGA_ERR_ARG", -2: "VGA_ERR_HIP", -3: "VGA_ERR_NOMEM", -4: "VGA_ERR_UNSUPPORTED",
              -5: "VGA_ERR_NO_INDEX", -6: "VGA_ERR_NO_DEVICE", -7: "VGA_ERR_POOL"}
 
@@ -56,7 +59,7 @@ class IndexDesc(C.Structure):
 
 class MapParams(C.Structure):
     _fields_ = [("bandwidth", C.c_uint32), ("max_gap", C.c_uint64), ("chain_min_n_anchors", C.c_uint32),
-                ("only_forward", C.c_int), ("emit_dp", C.c_int)]
+                ("only_forward", C.c_int), ("emit_dp", C.c_int), ("strands", C.c_int32)]
 
 
 class PoaParams(C.Structure):
@@ -79,7 +82,7 @@ class MapResult(C.Structure):
         ("n_chains", C.c_uint64), ("chain_off", _P(C.c_uint64)), ("chain_placeholder", _P(C.c_uint8)),
         ("chain_anchor_off", _P(C.c_uint64)), ("chain_anchor_idx", _P(C.c_uint32)),
         ("ms_probe", C.c_float), ("ms_sort", C.c_float), ("ms_chain", C.c_float), ("ms_total", C.c_float),
-        ("n_hits", C.c_uint64),
+        ("n_hits", C.c_uint64), ("strand", _P(C.c_uint8)),
     ]
 
 
@@ -236,6 +239,8 @@ class MapOut:
         self.chain_anchor_idx = _np(r.chain_anchor_idx, int(self.chain_anchor_off[-1]) if nc else 0, np.uint32)
         self.ms = {"probe": r.ms_probe, "sort": r.ms_sort, "chain": r.ms_chain, "total": r.ms_total}
         self.n_hits = int(r.n_hits)
+        # per read 0 (+) / 1 (-: the fields above describe its reverse complement) with VGA_STRANDS_BOTH, else None
+        self.strand = _np(r.strand, R, np.uint8) if r.strand else None
 
     def chains_of(self, read: int):
         """[(is_placeholder, [sorted-anchor index, ...]), ...] for one read"""

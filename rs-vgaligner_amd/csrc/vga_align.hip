@@ -267,6 +267,19 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     const uint32_t k = ctx->index.k;
     auto t0 = std::chrono::steady_clock::now();
     vga_trace tr("align");
+    // VGA_STRANDS_BOTH: a read whose chains came from its reverse complement is aligned as that sequence, taken from the half
+    // of the batch behind the forward bases (vga_strand.hip) -- on the device for the subgraph and text kernels, on the host
+    // for the host routes and the POA staging.  Built here too if this batch was never mapped that way.
+    bool any_rev = false;
+    if (m->strand)
+        for (uint64_t r = 0; r < R && !any_rev; r++) any_rev = m->strand[r] != 0;
+    if (any_rev) {
+        const int rc = vga_batch_revcomp_device(b);
+        if (rc != VGA_OK) return rc;
+        vga_batch_revcomp_host(b);
+        tr.mark("reverse complement");
+    }
+    auto q_off = [&](uint64_t r) -> uint64_t { return (m->strand && m->strand[r] ? b->total_bases : 0) + b->read_off[r]; };
 
     // ---- which (read, chain) pairs become POA problems: first min(best_n, len) chains (align.rs:43-50)
     std::vector<uint64_t> prob_read, prob_chain;
@@ -331,11 +344,11 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
         // the call and, 1 024-thread workgroups that need a CU's 16 wave slots at once, only got their CUs when the bulk launch
         // beside them had nothing left to dispatch: they ended last, 512 ms after their launch
         if (rows >= 0.85 * (double)giant_rows) proxy[p] += 1e13;
-        feed.views[p] = {nullptr, nullptr, 0, nullptr, nullptr, 0, b->reads.data() + b->read_off[r], ql};
+        feed.views[p] = {nullptr, nullptr, 0, nullptr, nullptr, 0, b->reads.data() + q_off(r), ql};
         if (on_device) {
             const uint64_t fa = a0 + m->chain_anchor_idx[c0], la = a0 + m->chain_anchor_idx[c1 - 1];
             descs[p] = {pmin, pmax, m->query_begin[fa], m->target_begin[fa], m->query_begin[la], m->target_end[la], ql, 0u};
-            q_src[p] = b->read_off[r];
+            q_src[p] = q_off(r);
         }
     });
     // Launch order = largest footprint first (poa_run's stable sort by proxy).  The device store is filled in that order,

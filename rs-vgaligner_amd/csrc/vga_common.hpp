@@ -112,7 +112,15 @@ struct vga_batch {
     std::vector<char> reads;         // host copy (subgraph extraction + cs strings need the bases)
     char *d_reads = nullptr;
     uint64_t *d_read_off = nullptr;
+    // VGA_STRANDS_BOTH (vga_strand.hip): the reverse complement of read r sits at total_bases + read_off[r], directly after the
+    // forward bases -- in d_reads once rc_dev is set (d_read_off2: the 2 n_reads + 1 offsets of forward reads, then their
+    // reverse complements), in `reads` once rc_host is set
+    bool rc_dev = false, rc_host = false;
+    uint64_t *d_read_off2 = nullptr;
 };
+// both build what is missing and return at once when it is there
+int vga_batch_revcomp_device(vga_batch *b);
+void vga_batch_revcomp_host(vga_batch *b);
 
 int vga_set_error(vga_ctx *ctx, int code, const char *fmt, ...);
 // frees the context's index (loaded = false); vga_index_load_graph: the graph half of a vga_index_desc onto the context

@@ -165,8 +165,10 @@ extern "C" void vga_ctx_destroy(vga_ctx *ctx)
     for (vga_batch *b : ctx->batches) {
         if (b->d_reads) (void)hipFree(b->d_reads);
         if (b->d_read_off) (void)hipFree(b->d_read_off);
+        if (b->d_read_off2) (void)hipFree(b->d_read_off2);
         b->d_reads = nullptr;
         b->d_read_off = nullptr;
+        b->d_read_off2 = nullptr;
         b->ctx = nullptr;
     }
     if (ctx->map_ws && ctx->map_ws_free) ctx->map_ws_free(ctx->map_ws);
@@ -493,6 +495,7 @@ extern "C" void vga_batch_destroy(vga_batch *b)
     }
     if (b->d_reads) (void)hipFree(b->d_reads);
     if (b->d_read_off) (void)hipFree(b->d_read_off);
+    if (b->d_read_off2) (void)hipFree(b->d_read_off2);
     delete b;
 }
 
@@ -503,6 +506,7 @@ extern "C" void vga_map_default_params(vga_map_params *p)
     p->chain_min_n_anchors = 3;
     p->only_forward = 1;
     p->emit_dp = 1;
+    p->strands = VGA_STRANDS_FORWARD;
 }
 
 extern "C" void vga_poa_default_params(vga_poa_params *p)

@@ -460,6 +460,87 @@ __global__ __launch_bounds__(256) void k_chain_compact(const uint64_t *__restric
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
+// ------------------------------------------------------------------------------------------ strands
+// vga_map_params.strands = VGA_STRANDS_BOTH: K1-K3 ran over 2R virtual reads, read r as given (r) and its reverse complement
+// (R + r).  Per read, the orientation is picked and only its fields are gathered into arrays for R reads, so that what crosses
+// PCIe is what forward mode copies back.
+//
+// The pick: the reverse complement wins when it has a real chain and the read as given has only its placeholder or a smaller
+// curr_max (f64 compare); a tie, or no chain either way, keeps the read as given.  A read without a chain is one whose
+// backtracking found none (chain_cnt 0: the host gives it the placeholder).
+__global__ __launch_bounds__(256) void k_strand_pick(uint32_t R, const uint64_t *__restrict__ anchor_off, const double *__restrict__ curr_max,
+                                                     const uint32_t *__restrict__ chain_cnt, const uint32_t *__restrict__ chain_words,
+                                                     uint8_t *__restrict__ strand, uint32_t *__restrict__ sel, uint32_t *__restrict__ sel_anchors,
+                                                     double *__restrict__ sel_curr_max, uint32_t *__restrict__ sel_chain_cnt,
+                                                     uint32_t *__restrict__ sel_chain_words)
+{
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t rv = R + r;
+    const bool rev = chain_cnt[rv] > 0 && (chain_cnt[r] == 0 || curr_max[rv] > curr_max[r]);
+    const uint32_t s = rev ? rv : r;
+    strand[r] = rev ? 1 : 0;
+    sel[r] = s;
+    sel_anchors[r] = (uint32_t)(anchor_off[s + 1] - anchor_off[s]);
+    sel_curr_max[r] = curr_max[s];
+    sel_chain_cnt[r] = chain_cnt[s];
+    sel_chain_words[r] = chain_words[s];
+}
+
+// one block: the exclusive scan of the chosen orientations' anchor counts (R + 1 offsets)
+__global__ __launch_bounds__(256) void k_strand_scan(uint32_t R, const uint32_t *__restrict__ cnt, uint64_t *__restrict__ off)
+{
+    __shared__ uint32_t ws[4];
+    uint64_t carry = 0;
+    for (uint32_t c0 = 0; c0 < R; c0 += 256) {
+        const uint32_t i = c0 + threadIdx.x;
+        const uint32_t v = i < R ? cnt[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = vga_block_excl_scan_256(v, ws, total);
+        if (i < R) off[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) off[R] = carry;
+}
+
+// one block per read: the chosen orientation's sorted anchors (and, with emit_dp, ids / f(i) / predecessors) to its place in
+// the compact arrays.  Chain members and predecessors are read-local, so they need no translation.
+__global__ __launch_bounds__(256) void k_strand_gather(const uint32_t *__restrict__ sel, const uint64_t *__restrict__ anchor_off,
+                                                       const uint64_t *__restrict__ sel_off, const uint32_t *__restrict__ s_qb,
+                                                       const uint32_t *__restrict__ s_tb, const uint32_t *__restrict__ s_te,
+                                                       const uint32_t *__restrict__ s_id, const double *__restrict__ f,
+                                                       const int32_t *__restrict__ pred, uint32_t *__restrict__ g_qb,
+                                                       uint32_t *__restrict__ g_tb, uint32_t *__restrict__ g_te, uint32_t *__restrict__ g_id,
+                                                       double *__restrict__ g_f, int32_t *__restrict__ g_pred)
+{
+    const uint32_t r = blockIdx.x;
+    const uint64_t a0 = anchor_off[sel[r]], o = sel_off[r];
+    const uint32_t A = (uint32_t)(sel_off[r + 1] - o);
+    for (uint32_t i = threadIdx.x; i < A; i += blockDim.x) {
+        g_qb[o + i] = s_qb[a0 + i];
+        g_tb[o + i] = s_tb[a0 + i];
+        g_te[o + i] = s_te[a0 + i];
+    }
+    if (g_id)
+        for (uint32_t i = threadIdx.x; i < A; i += blockDim.x) {
+            g_id[o + i] = s_id[a0 + i];
+            g_f[o + i] = f[a0 + i];
+            g_pred[o + i] = pred[a0 + i];
+        }
+}
+
+// k_chain_compact for the chosen orientation of each read
+__global__ __launch_bounds__(256) void k_chain_compact_sel(const uint32_t *__restrict__ sel, const uint64_t *__restrict__ anchor_off,
+                                                           const uint32_t *__restrict__ sel_chain_words, const uint64_t *__restrict__ woff,
+                                                           const uint32_t *__restrict__ chain_buf, uint32_t *__restrict__ comp)
+{
+    const uint64_t r = blockIdx.x, s = sel[r];
+    const uint32_t *src = chain_buf + 3 * anchor_off[s] + 2 * s;
+    uint32_t *dst = comp + woff[r];
+    const uint32_t n = sel_chain_words[r];
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
 // ------------------------------------------------------------------------------------------ host
 namespace {
 
@@ -471,6 +552,12 @@ struct map_ws {
     vga_dbuf<int32_t> pred_id, pred_pos;
     vga_dbuf<uint32_t> chain_buf, chain_cnt, chain_words, key_a, chain_comp;
     vga_dbuf<uint64_t> chain_woff;
+    // VGA_STRANDS_BOTH: the pick (per read) and the chosen orientation's anchors
+    vga_dbuf<uint8_t> strand;
+    vga_dbuf<uint32_t> sel, sel_anchors, sel_chain_cnt, sel_chain_words, g_qb, g_tb, g_te, g_id;
+    vga_dbuf<uint64_t> sel_off;
+    vga_dbuf<double> sel_curr_max, g_f;
+    vga_dbuf<int32_t> g_pred;
     vga_hbuf<uint64_t> h_chain_woff;
     // pinned staging for the result copies (pageable D2H runs at a fraction of the PCIe rate)
     vga_hbuf<uint32_t> h_chain_cnt, h_chain_words, h_cnt;
@@ -508,6 +595,7 @@ extern "C" void vga_map_result_free(vga_map_result *r)
     free(r->chain_placeholder);
     free(r->chain_anchor_off);
     free(r->chain_anchor_idx);
+    free(r->strand);
     free(r);
 }
 
@@ -523,6 +611,12 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     // only_forward = 0 (anchors_for_query(..., false), src/chain.rs:154-155): every k-mer record becomes an anchor; the
     // orientation of each end travels in bit 31 of target_begin / target_end.  vga_align_batch accepts forward chains only.
     const bool all_orients = !params->only_forward;
+    if (params->strands != VGA_STRANDS_FORWARD && params->strands != VGA_STRANDS_BOTH)
+        return vga_set_error(ctx, VGA_ERR_ARG, "strands %d: VGA_STRANDS_FORWARD (0) or VGA_STRANDS_BOTH (1)", params->strands);
+    // VGA_STRANDS_BOTH: the read and its reverse complement, each forward-only (vga_strand.hip)
+    const bool both = params->strands == VGA_STRANDS_BOTH;
+    if (both && all_orients)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "strands = VGA_STRANDS_BOTH maps the read and its reverse complement forward-only: it needs only_forward = 1");
     if (all_orients && !ctx->index.d_table_all)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "only_forward=0 needs the all-orientation probe table, which is built for k <= 13");
     if (params->bandwidth == 0 || params->bandwidth > 64)
@@ -549,7 +643,8 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     res->anchor_off = xmalloc<uint64_t>(R + 1);
     res->curr_max = xmalloc<double>(R);
     res->chain_off = xmalloc<uint64_t>(R + 1);
-    if (!res->anchor_off || !res->curr_max || !res->chain_off) return nomem();
+    if (both) res->strand = xmalloc<uint8_t>(R);
+    if (!res->anchor_off || !res->curr_max || !res->chain_off || (both && !res->strand)) return nomem();
     res->anchor_off[0] = 0;
     res->chain_off[0] = 0;
     if (R == 0) {
@@ -572,40 +667,52 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
         }                                                                                            \
     } while (0)
 
+    // K1-K3 run over RV virtual reads: the reads, then (VGA_STRANDS_BOTH) their reverse complements
+    const uint64_t RV = both ? 2 * R : R;
+    if (both) {
+        const int rc = vga_batch_revcomp_device(b);
+        if (rc != VGA_OK) { vga_map_result_free(res); return rc; }
+        tr.mark("reverse complement");
+    }
+    const uint64_t *d_read_off = both ? b->d_read_off2 : b->d_read_off;
+
     // ---- K1 pass 1: count
-    MAP_CHECK(ws.cnt.reserve(R));
-    MAP_CHECK(ws.anchor_off.reserve(R + 1));
+    MAP_CHECK(ws.cnt.reserve(RV));
+    MAP_CHECK(ws.anchor_off.reserve(RV + 1));
     int t_total = vga_timer_begin(ctx, "map_total", 0);
     int t1 = vga_timer_begin(ctx, "kmer_probe_count", 0);
     const uint32_t *probe_table = all_orients ? ix.d_table_all : ix.d_table;
     const uint2 *probe_pos = all_orients ? ix.d_pos_all : ix.d_pos;
-    hipLaunchKernelGGL(k_kmer_probe<false>, dim3((unsigned)R), dim3(VGA_PROBE_NT), 0, st, b->d_reads, b->d_read_off, ix.k,
+    hipLaunchKernelGGL(k_kmer_probe<false>, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st, b->d_reads, d_read_off, ix.k,
                        probe_table, probe_pos, ws.cnt.p, (const uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                        (uint32_t *)nullptr, (uint32_t *)nullptr);
     vga_timer_end(ctx, t1);
-    MAP_CHECK(ws.h_cnt.reserve(R));
+    MAP_CHECK(ws.h_cnt.reserve(RV));
     uint32_t *h_cnt = ws.h_cnt.p;
-    MAP_CHECK(hipMemcpyAsync(h_cnt, ws.cnt.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    MAP_CHECK(hipMemcpyAsync(h_cnt, ws.cnt.p, RV * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     MAP_CHECK(hipStreamSynchronize(st));
     tr.mark("count kernel + sync");
+    // anchor offsets of the virtual reads: the result's own in forward mode
+    std::vector<uint64_t> aoff_v(both ? RV + 1 : 0);
+    uint64_t *h_aoff = both ? aoff_v.data() : res->anchor_off;
     uint64_t total = 0;
-    for (uint64_t r = 0; r < R; r++) {
-        res->anchor_off[r] = total;
+    for (uint64_t r = 0; r < RV; r++) {
+        h_aoff[r] = total;
         total += h_cnt[r];
     }
-    res->anchor_off[R] = total;
+    h_aoff[RV] = total;
     res->n_anchors = total;
     res->n_hits = total;
-    MAP_CHECK(hipMemcpyAsync(ws.anchor_off.p, res->anchor_off, (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MAP_CHECK(hipMemcpyAsync(ws.anchor_off.p, h_aoff, (RV + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 
     const size_t An = (size_t)total;
     MAP_CHECK(ws.a_qb.reserve(An)); MAP_CHECK(ws.a_tb.reserve(An)); MAP_CHECK(ws.a_te.reserve(An));
     MAP_CHECK(ws.a_idx.reserve(An)); MAP_CHECK(ws.key_b.reserve(An)); MAP_CHECK(ws.val_b.reserve(An));
     MAP_CHECK(ws.s_qb.reserve(An)); MAP_CHECK(ws.s_tb.reserve(An)); MAP_CHECK(ws.s_te.reserve(An));
     MAP_CHECK(ws.f.reserve(An)); MAP_CHECK(ws.pred_id.reserve(An)); MAP_CHECK(ws.pred_pos.reserve(An));
-    MAP_CHECK(ws.curr_max.reserve(R));
-    MAP_CHECK(ws.chain_buf.reserve(3 * An + 2 * R + 2));
-    MAP_CHECK(ws.chain_cnt.reserve(R)); MAP_CHECK(ws.chain_words.reserve(R));
+    MAP_CHECK(ws.curr_max.reserve(RV));
+    MAP_CHECK(ws.chain_buf.reserve(3 * An + 2 * RV + 2));
+    MAP_CHECK(ws.chain_cnt.reserve(RV)); MAP_CHECK(ws.chain_words.reserve(RV));
 
     tr.mark("workspace reserve");
     // gap cost table (src/chain.rs:348-354), host libm
@@ -623,8 +730,9 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
         uint64_t L = b->read_off[r + 1] - b->read_off[r];
         if (L >= ix.k) nkm += L - ix.k + 1;
     }
-    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", b->total_bases + 4 * nkm + 8 * total + 16 * total);
-    hipLaunchKernelGGL(k_kmer_probe<true>, dim3((unsigned)R), dim3(VGA_PROBE_NT), 0, st, b->d_reads, b->d_read_off, ix.k,
+    if (both) nkm *= 2;  // (a reverse complement has the k-mers of its read)
+    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", (both ? 2 : 1) * b->total_bases + 4 * nkm + 8 * total + 16 * total);
+    hipLaunchKernelGGL(k_kmer_probe<true>, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st, b->d_reads, d_read_off, ix.k,
                        probe_table, probe_pos, (uint32_t *)nullptr, ws.anchor_off.p, ws.a_qb.p, ws.a_tb.p, ws.a_te.p, ws.a_idx.p);
     vga_timer_end(ctx, t2);
 
@@ -640,10 +748,10 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     if (An) MAP_CHECK(hipMemcpyAsync(key_a.p, ws.a_te.p, An * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     if (An && all_orients) hipLaunchKernelGGL(k_flip_orient_bit, dim3((unsigned)((An + 255) / 256)), dim3(256), 0, st, key_a.p, (uint64_t)An);
     int t3 = vga_timer_begin(ctx, "anchor_sort", (uint64_t)n_pass * 16 * total + 24 * total);
-    hipLaunchKernelGGL(k_anchor_sort, dim3((unsigned)R), dim3(VGA_SORT_NT), 0, st, ws.anchor_off.p, n_pass, key_a.p,
+    hipLaunchKernelGGL(k_anchor_sort, dim3((unsigned)RV), dim3(VGA_SORT_NT), 0, st, ws.anchor_off.p, n_pass, key_a.p,
                        ws.a_idx.p, ws.key_b.p, ws.val_b.p);
     const uint32_t *perm = (n_pass & 1u) ? ws.val_b.p : ws.a_idx.p;
-    hipLaunchKernelGGL(k_anchor_gather_seg, dim3((unsigned)R), dim3(256), 0, st, ws.anchor_off.p, perm, ws.a_qb.p, ws.a_tb.p,
+    hipLaunchKernelGGL(k_anchor_gather_seg, dim3((unsigned)RV), dim3(256), 0, st, ws.anchor_off.p, perm, ws.a_qb.p, ws.a_tb.p,
                        ws.a_te.p, ws.s_qb.p, ws.s_tb.p, ws.s_te.p);
     vga_timer_end(ctx, t3);
     // the sorted coordinates are final: they go back beside the chaining kernel (below, once it is launched)
@@ -670,9 +778,9 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
                    params->chain_min_n_anchors, ws.gap_cost.p, ws.f.p, ws.pred_id.p, ws.pred_pos.p, ws.curr_max.p,         \
                    ws.chain_buf.p, ws.chain_cnt.p, ws.chain_words.p, key_anchors
         if (gap_bytes <= 16 * 1024)  // (8 KB at the default max_gap; bigger tables stay in HBM)
-            hipLaunchKernelGGL(k_chain4<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), gap_bytes, st, (uint32_t)R, CHAIN_ARGS);
+            hipLaunchKernelGGL(k_chain4<true>, dim3((unsigned)((RV + 3) / 4)), dim3(256), gap_bytes, st, (uint32_t)RV, CHAIN_ARGS);
         else
-            hipLaunchKernelGGL(k_chain4<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, (uint32_t)R, CHAIN_ARGS);
+            hipLaunchKernelGGL(k_chain4<false>, dim3((unsigned)((RV + 3) / 4)), dim3(256), 0, st, (uint32_t)RV, CHAIN_ARGS);
 #undef CHAIN_ARGS
     }
     vga_timer_end(ctx, t4);
@@ -684,31 +792,82 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     // same size first (60-90 ms per 400 MB, tests/microbench/pinned_time.hip) and a fan-out copy afterwards.  The small
     // per-read arrays keep their pinned staging.
     const bool emit_dp = params->emit_dp != 0;
-    if (emit_dp) {
-        res->anchor_id = xmalloc<uint32_t>(An);
-        res->max_chain_score = xmalloc<double>(An);
-        res->best_pred_id = xmalloc<int32_t>(An);
-    }
-    res->query_begin = xmalloc<uint32_t>(An);
-    res->target_begin = xmalloc<uint32_t>(An);
-    res->target_end = xmalloc<uint32_t>(An);
-    if ((emit_dp && (!res->anchor_id || !res->max_chain_score || !res->best_pred_id)) || !res->query_begin || !res->target_begin || !res->target_end) {
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamSynchronize(ws.st_copy);
-        return nomem();
-    }
-    if (An) {  // (beside the chaining kernel: these wait for the sort only)
-        MAP_CHECK(hipMemcpyAsync(res->query_begin, ws.s_qb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
-        MAP_CHECK(hipMemcpyAsync(res->target_begin, ws.s_tb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
-        MAP_CHECK(hipMemcpyAsync(res->target_end, ws.s_te.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+    auto alloc_anchor_arrays = [&](size_t n) -> bool {
+        if (emit_dp) {
+            res->anchor_id = xmalloc<uint32_t>(n);
+            res->max_chain_score = xmalloc<double>(n);
+            res->best_pred_id = xmalloc<int32_t>(n);
+        }
+        res->query_begin = xmalloc<uint32_t>(n);
+        res->target_begin = xmalloc<uint32_t>(n);
+        res->target_end = xmalloc<uint32_t>(n);
+        return !((emit_dp && (!res->anchor_id || !res->max_chain_score || !res->best_pred_id)) || !res->query_begin || !res->target_begin ||
+                 !res->target_end);
+    };
+    // where the result's per-read values and per-anchor ids / f(i) / predecessors come from: the chosen orientation's
+    // gathered copies with VGA_STRANDS_BOTH
+    const double *d_curr_max = ws.curr_max.p;
+    const uint32_t *d_chain_cnt = ws.chain_cnt.p, *d_chain_words = ws.chain_words.p;
+    const uint32_t *d_ids = perm;
+    const double *d_f = ws.f.p;
+    const int32_t *d_pred = ws.pred_id.p;
+    if (!both) {
+        if (!alloc_anchor_arrays(An)) {
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamSynchronize(ws.st_copy);
+            return nomem();
+        }
+        if (An) {  // (beside the chaining kernel: these wait for the sort only)
+            MAP_CHECK(hipMemcpyAsync(res->query_begin, ws.s_qb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+            MAP_CHECK(hipMemcpyAsync(res->target_begin, ws.s_tb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+            MAP_CHECK(hipMemcpyAsync(res->target_end, ws.s_te.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+        }
+    } else {
+        // ---- the pick, and the offsets of the chosen orientations' anchors (a count, then an exclusive scan)
+        MAP_CHECK(ws.strand.reserve(R)); MAP_CHECK(ws.sel.reserve(R)); MAP_CHECK(ws.sel_anchors.reserve(R));
+        MAP_CHECK(ws.sel_curr_max.reserve(R)); MAP_CHECK(ws.sel_chain_cnt.reserve(R)); MAP_CHECK(ws.sel_chain_words.reserve(R));
+        MAP_CHECK(ws.sel_off.reserve(R + 1));
+        const int tp = vga_timer_begin(ctx, "strand_pick", 2 * R * (8 + 8 + 4 + 4) + R * (1 + 4 + 4 + 8 + 4 + 4) + R * (4 + 8));
+        hipLaunchKernelGGL(k_strand_pick, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (uint32_t)R, ws.anchor_off.p, ws.curr_max.p,
+                           ws.chain_cnt.p, ws.chain_words.p, ws.strand.p, ws.sel.p, ws.sel_anchors.p, ws.sel_curr_max.p, ws.sel_chain_cnt.p,
+                           ws.sel_chain_words.p);
+        hipLaunchKernelGGL(k_strand_scan, dim3(1), dim3(256), 0, st, (uint32_t)R, ws.sel_anchors.p, ws.sel_off.p);
+        vga_timer_end(ctx, tp);
+        MAP_CHECK(hipMemcpyAsync(res->anchor_off, ws.sel_off.p, (R + 1) * 8, hipMemcpyDeviceToHost, st));
+        MAP_CHECK(hipMemcpyAsync(res->strand, ws.strand.p, R, hipMemcpyDeviceToHost, st));
+        d_curr_max = ws.sel_curr_max.p;
+        d_chain_cnt = ws.sel_chain_cnt.p;
+        d_chain_words = ws.sel_chain_words.p;
     }
     MAP_CHECK(ws.h_curr_max.reserve(R)); MAP_CHECK(ws.h_chain_cnt.reserve(R)); MAP_CHECK(ws.h_chain_words.reserve(R));
     MAP_CHECK(ws.h_chain_woff.reserve(R + 1)); MAP_CHECK(ws.chain_woff.reserve(R + 1));
     // the per-read counts first: they say how much of the chain buffer is in use
-    MAP_CHECK(hipMemcpyAsync(ws.h_curr_max.p, ws.curr_max.p, R * 8, hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipMemcpyAsync(ws.h_chain_cnt.p, ws.chain_cnt.p, R * 4, hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipMemcpyAsync(ws.h_chain_words.p, ws.chain_words.p, R * 4, hipMemcpyDeviceToHost, st));
+    MAP_CHECK(hipMemcpyAsync(ws.h_curr_max.p, d_curr_max, R * 8, hipMemcpyDeviceToHost, st));
+    MAP_CHECK(hipMemcpyAsync(ws.h_chain_cnt.p, d_chain_cnt, R * 4, hipMemcpyDeviceToHost, st));
+    MAP_CHECK(hipMemcpyAsync(ws.h_chain_words.p, d_chain_words, R * 4, hipMemcpyDeviceToHost, st));
     MAP_CHECK(hipStreamSynchronize(st));
+    if (both) {
+        // ---- the chosen orientation's anchors to compact arrays, and from there to the result
+        const size_t As = (size_t)res->anchor_off[R];
+        res->n_anchors = As;
+        if (!alloc_anchor_arrays(As)) return nomem();
+        MAP_CHECK(ws.g_qb.reserve(As)); MAP_CHECK(ws.g_tb.reserve(As)); MAP_CHECK(ws.g_te.reserve(As));
+        if (emit_dp) { MAP_CHECK(ws.g_id.reserve(As)); MAP_CHECK(ws.g_f.reserve(As)); MAP_CHECK(ws.g_pred.reserve(As)); }
+        const int tg = vga_timer_begin(ctx, "strand_gather", (uint64_t)As * 2 * (12 + (emit_dp ? 16 : 0)) + R * 20);
+        hipLaunchKernelGGL(k_strand_gather, dim3((unsigned)R), dim3(256), 0, st, ws.sel.p, ws.anchor_off.p, ws.sel_off.p, ws.s_qb.p, ws.s_tb.p,
+                           ws.s_te.p, perm, ws.f.p, ws.pred_id.p, ws.g_qb.p, ws.g_tb.p, ws.g_te.p, emit_dp ? ws.g_id.p : nullptr,
+                           emit_dp ? ws.g_f.p : nullptr, emit_dp ? ws.g_pred.p : nullptr);
+        vga_timer_end(ctx, tg);
+        if (As) {
+            MAP_CHECK(hipMemcpyAsync(res->query_begin, ws.g_qb.p, As * 4, hipMemcpyDeviceToHost, st));
+            MAP_CHECK(hipMemcpyAsync(res->target_begin, ws.g_tb.p, As * 4, hipMemcpyDeviceToHost, st));
+            MAP_CHECK(hipMemcpyAsync(res->target_end, ws.g_te.p, As * 4, hipMemcpyDeviceToHost, st));
+        }
+        d_ids = ws.g_id.p;
+        d_f = ws.g_f.p;
+        d_pred = ws.g_pred.p;
+    }
+    const size_t An_res = (size_t)res->n_anchors;
     uint64_t chain_total_words = 0;
     for (uint64_t r = 0; r < R; r++) { ws.h_chain_woff.p[r] = chain_total_words; chain_total_words += ws.h_chain_words.p[r]; }
     ws.h_chain_woff.p[R] = chain_total_words;
@@ -717,14 +876,18 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     if (chain_total_words) {
         MAP_CHECK(ws.chain_comp.reserve(chain_total_words + 2));
         MAP_CHECK(hipMemcpyAsync(ws.chain_woff.p, ws.h_chain_woff.p, (R + 1) * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_chain_compact, dim3((unsigned)R), dim3(256), 0, st, ws.anchor_off.p, ws.chain_words.p, ws.chain_woff.p,
-                           ws.chain_buf.p, ws.chain_comp.p);
+        if (both)
+            hipLaunchKernelGGL(k_chain_compact_sel, dim3((unsigned)R), dim3(256), 0, st, ws.sel.p, ws.anchor_off.p, ws.sel_chain_words.p,
+                               ws.chain_woff.p, ws.chain_buf.p, ws.chain_comp.p);
+        else
+            hipLaunchKernelGGL(k_chain_compact, dim3((unsigned)R), dim3(256), 0, st, ws.anchor_off.p, ws.chain_words.p, ws.chain_woff.p,
+                               ws.chain_buf.p, ws.chain_comp.p);
         MAP_CHECK(hipMemcpyAsync(chain_words_host.get(), ws.chain_comp.p, chain_total_words * 4, hipMemcpyDeviceToHost, st));
     }
-    if (An && emit_dp) {
-        MAP_CHECK(hipMemcpyAsync(res->anchor_id, perm, An * 4, hipMemcpyDeviceToHost, st));
-        MAP_CHECK(hipMemcpyAsync(res->max_chain_score, ws.f.p, An * 8, hipMemcpyDeviceToHost, st));
-        MAP_CHECK(hipMemcpyAsync(res->best_pred_id, ws.pred_id.p, An * 4, hipMemcpyDeviceToHost, st));
+    if (An_res && emit_dp) {
+        MAP_CHECK(hipMemcpyAsync(res->anchor_id, d_ids, An_res * 4, hipMemcpyDeviceToHost, st));
+        MAP_CHECK(hipMemcpyAsync(res->max_chain_score, d_f, An_res * 8, hipMemcpyDeviceToHost, st));
+        MAP_CHECK(hipMemcpyAsync(res->best_pred_id, d_pred, An_res * 4, hipMemcpyDeviceToHost, st));
     }
     MAP_CHECK(hipStreamSynchronize(st));
     MAP_CHECK(hipStreamSynchronize(ws.st_copy));

@@ -35,7 +35,9 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: --device one GPU, --devices a list (one context + host thread each; an id may
                           // repeat; --devices all: every visible GPU; default: --device 0), --chunk-reads reads per batch (bounded memory; 0 = one batch)
                           {"-d", "--device", true, "device"}, {"", "--devices", true, "devices"}, {"", "--chunk-reads", true, "chunk-reads"},
-                          {"", "--poa-remain", true, "poa-remain"}};
+                          {"", "--poa-remain", true, "poa-remain"},
+                          // not in the reference: map each read and its reverse complement, keep the orientation that chains better
+                          {"", "--both-strands", false, "both-strands"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -122,6 +124,7 @@ int map_main(int argc, char **argv)
         else if (r == "first-edge") o.poa_remain_rule = VGA_REMAIN_FIRST_OUT_EDGE;
         else throw Error("--poa-remain takes longest or first-edge");
     }
+    o.both_strands = m.count("both-strands") > 0;
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -155,6 +158,8 @@ int map_main(int argc, char **argv)
     MapOutput out = map_reads_multi(ix, reads, o, prefix);
     fprintf(stderr, "[vgaligner] %llu GPU context(s), %llu batch(es)\n", (unsigned long long)out.n_devices, (unsigned long long)out.n_chunks);
     fprintf(stderr, "[vgaligner] Chaining took: %.0f ms\n", out.ms_map);
+    if (o.both_strands)
+        fprintf(stderr, "[vgaligner] %llu of %llu reads on the reverse strand\n", (unsigned long long)out.n_reverse, (unsigned long long)out.n_reads);
     if (o.also_align) fprintf(stderr, "[vgaligner] Alignment took: %.0f ms; Found %llu alignments!\n", out.ms_align, (unsigned long long)out.n_reads);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
@@ -195,7 +200,8 @@ int main(int argc, char **argv)
         if (argc >= 2 && !strcmp(argv[1], "map")) return map_main(argc, argv);
         fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
-                        "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n");
+                        "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
+                        "                [--both-strands]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -100,9 +100,15 @@ std::string gaf_placeholder(const QuerySequence &q);
 std::string gaf_from_chain(const Index &ix, const QuerySequence &q, const vga_map_result *m, uint64_t read, uint64_t chain);
 void gaf_from_chain_text(std::string &out, const Index &ix, const QuerySequence &q, const vga_map_result *m, uint64_t read, uint64_t chain,
                          const char *path, uint64_t path_len);
-std::string gaf_from_alignment(const QuerySequence &q, const vga_align_result *a, uint64_t read);
-void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_align_result *a, uint64_t read);  // (appends)
+// A read mapped on its reverse complement (vga_map_result.strand[read] = 1) gets PAF's '-' convention: column 5 is '-', the
+// reverse complement aligns to the path as written.  The chain writers read the strand from the map result; the query columns of
+// a chain record are then flipped into the read's own frame.  An alignment record keeps 0 / length and the forward path.
+std::string gaf_from_alignment(const QuerySequence &q, const vga_align_result *a, uint64_t read, bool reverse = false);
+void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_align_result *a, uint64_t read, bool reverse = false);  // (appends)
+// the reverse complement of a read (src/dna.rs:20-33 switch_base; a byte outside it becomes N)
+std::string reverse_complement(const std::string &s);
 // ValidationRecord::from_graph_and_alignment + to_string (src/validate.rs:36-102) from one alignments-GAF line
+// A '-' record (--both-strands) carries the reverse complement of the read, the sequence its CIGAR describes.
 std::string validation_record(const Index &ix, const std::string &gaf_line, const std::vector<QuerySequence> &reads);
 
 // ---- map_reads --------------------------------------------------------------------------------
@@ -135,6 +141,9 @@ struct MapOptions {
     bool keep_text = true;
     bool also_validate = false;          // -v: write validation records (src/validate.rs:18-102, map.rs:186-208)
     std::string validation_path;         // -P
+    // --both-strands (not in the reference): map each read and its reverse complement and keep the orientation that chains better
+    // (vga_map_params.strands = VGA_STRANDS_BOTH)
+    bool both_strands = false;
 };
 
 // VGA_TRACE=1: wall-clock marks of the driver's phases on stderr (since the first call)
@@ -143,6 +152,7 @@ void trace_mark(const char *what);
 struct MapOutput {
     std::string chains_gaf, alignments_gaf, validation;
     uint64_t n_reads = 0, n_aligned = 0, n_anchors = 0, poa_cells = 0;
+    uint64_t n_reverse = 0;              // reads mapped on their reverse complement (both_strands)
     double ms_map = 0, ms_align = 0;     // summed over chunks (per device: the maximum over devices)
     uint64_t n_chunks = 0, n_devices = 0;
 };

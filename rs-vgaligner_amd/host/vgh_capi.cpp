@@ -90,6 +90,61 @@ char *vgh_gaf_alignment_record(const char *prefix, const char *name, uint64_t se
     } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 
+// The same for a read that --both-strands mapped on its reverse complement (reverse = 1): column 5 is '-'.
+char *vgh_gaf_alignment_record_strand(const char *name, uint64_t seq_len, int reverse, const uint64_t *handles, uint64_t n_handles,
+                                      uint32_t path_length, uint32_t path_start, uint32_t path_end, uint32_t block_length, const char *cs,
+                                      const char *cigar)
+{
+    try {
+        QuerySequence q{name, std::string((size_t)seq_len, 'A')};
+        vga_align_result a;
+        memset(&a, 0, sizeof a);
+        uint8_t al = 1;
+        uint64_t path_off[2] = {0, n_handles}, cs_off[2] = {0, strlen(cs) + 1}, cg_off[2] = {0, strlen(cigar) + 1};
+        a.n_reads = 1;
+        a.aligned = &al;
+        a.path_off = path_off;
+        a.path_handles = const_cast<uint64_t *>(handles);
+        a.path_length = &path_length; a.path_start = &path_start; a.path_end = &path_end; a.block_length = &block_length;
+        a.cs_off = cs_off; a.cs = const_cast<char *>(cs);
+        a.cigar_off = cg_off; a.cigar = const_cast<char *>(cigar);
+        return dup_str(gaf_from_alignment(q, &a, 0, reverse != 0));
+    } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+
+// The chains-GAF record (gaf_from_chain_text) of one read with one chain made of n_anchors anchors whose query_begin are given,
+// mapped on the strand `strand` (0 as given, 1 its reverse complement: query_begin then counts in the reverse complement's frame),
+// with the path column already written.  Returns malloc'd text (vgh_free).
+char *vgh_gaf_chain_record(const char *name, uint64_t seq_len, uint32_t k, int strand, const uint32_t *query_begin, uint64_t n_anchors,
+                           const char *path)
+{
+    try {
+        if (n_anchors == 0) throw Error("a chain has at least one anchor");
+        QuerySequence q{name, std::string((size_t)seq_len, 'A')};
+        Index ix;
+        ix.kmer_length = k;
+        std::vector<uint32_t> idx(n_anchors);
+        for (uint64_t i = 0; i < n_anchors; i++) idx[i] = (uint32_t)i;
+        uint64_t anchor_off[2] = {0, n_anchors}, chain_off[2] = {0, 1}, chain_anchor_off[2] = {0, n_anchors};
+        uint8_t placeholder = 0, st = strand ? 1 : 0;
+        vga_map_result m;
+        memset(&m, 0, sizeof m);
+        m.n_reads = 1;
+        m.n_anchors = n_anchors;
+        m.anchor_off = anchor_off;
+        m.query_begin = const_cast<uint32_t *>(query_begin);
+        m.n_chains = 1;
+        m.chain_off = chain_off;
+        m.chain_placeholder = &placeholder;
+        m.chain_anchor_off = chain_anchor_off;
+        m.chain_anchor_idx = idx.data();
+        m.strand = &st;
+        std::string out;
+        gaf_from_chain_text(out, ix, q, &m, 0, 0, path, strlen(path));
+        return dup_str(out);
+    } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+
 // map_reads over in-memory reads; returns 0 and malloc'd GAF texts (free with vgh_free)
 int vgh_map_reads(vga_ctx *ctx, void *h, uint64_t n, const char *const *names, const char *const *seqs, uint64_t max_gap,
                   uint64_t chain_min_n_anchors, int also_align, uint64_t align_best_n, const char *out_prefix,

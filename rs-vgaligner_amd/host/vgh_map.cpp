@@ -89,7 +89,34 @@ inline void put_u64(std::string &s, uint64_t v)
     do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
     while (n) s.push_back(t[--n]);
 }
+// columns 3-5 of a chain record: "qs\tqe\t+\t".  A read mapped on its reverse complement (strand 1: qb / qe count from the start of
+// the reverse complement) gets the read's own frame, qs = L - qe and qe = L - qs, and '-'.
+inline void put_chain_query(std::string &s, uint64_t L, const vga_map_result *m, uint64_t read, uint64_t qb, uint64_t qe)
+{
+    const bool rev = m->strand && m->strand[read];
+    put_u64(s, rev ? L - qe : qb); s.push_back('\t'); put_u64(s, rev ? L - qb : qe); s += rev ? "\t-\t" : "\t+\t";
+}
 }  // namespace
+
+std::string reverse_complement(const std::string &s)
+{
+    std::string out(s.rbegin(), s.rend());
+    for (char &c : out)
+        switch (c) {
+        case 'A': c = 'T'; break;
+        case 'C': c = 'G'; break;
+        case 'G': c = 'C'; break;
+        case 'T': c = 'A'; break;
+        case 'U': c = 'A'; break;
+        case 'a': c = 't'; break;
+        case 'c': c = 'g'; break;
+        case 'g': c = 'c'; break;
+        case 't': c = 'a'; break;
+        case 'u': c = 'a'; break;
+        default: c = 'N';
+        }
+    return out;
+}
 
 std::string gaf_from_chain(const Index &ix, const QuerySequence &q, const vga_map_result *m, uint64_t read, uint64_t chain)
 {
@@ -129,8 +156,8 @@ std::string gaf_from_chain(const Index &ix, const QuerySequence &q, const vga_ma
     // plen pstart pend residue block = 0; mapq = min(f64::MIN as u64, 254) = 0 (align.rs:904, chain.rs:203)
     std::string out;
     out.reserve(q.name.size() + path.size() + 96);
-    out += q.name; out.push_back('\t'); put_u64(out, q.seq.size()); out.push_back('\t'); put_u64(out, m->query_begin[first]);
-    out.push_back('\t'); put_u64(out, m->query_begin[last] + k); out += "\t+\t"; out += path;
+    out += q.name; out.push_back('\t'); put_u64(out, q.seq.size()); out.push_back('\t');
+    put_chain_query(out, q.seq.size(), m, read, m->query_begin[first], m->query_begin[last] + k); out += path;
     out += "\t0\t0\t0\t0\t0\t0\tta:Z:chain,n_anchors: "; put_u64(out, c1 - c0); out.push_back('\n');
     return out;
 }
@@ -143,8 +170,8 @@ void gaf_from_chain_text(std::string &out, const Index &ix, const QuerySequence 
     const uint64_t a0 = m->anchor_off[read];
     const uint64_t c0 = m->chain_anchor_off[chain], c1 = m->chain_anchor_off[chain + 1];
     const uint64_t first = a0 + m->chain_anchor_idx[c0], last = a0 + m->chain_anchor_idx[c1 - 1];
-    out += q.name; out.push_back('\t'); put_u64(out, q.seq.size()); out.push_back('\t'); put_u64(out, m->query_begin[first]);
-    out.push_back('\t'); put_u64(out, m->query_begin[last] + ix.kmer_length); out += "\t+\t"; out.append(path, path_len);
+    out += q.name; out.push_back('\t'); put_u64(out, q.seq.size()); out.push_back('\t');
+    put_chain_query(out, q.seq.size(), m, read, m->query_begin[first], m->query_begin[last] + ix.kmer_length); out.append(path, path_len);
     out += "\t0\t0\t0\t0\t0\t0\tta:Z:chain,n_anchors: "; put_u64(out, c1 - c0); out.push_back('\n');
 }
 
@@ -162,7 +189,7 @@ inline char *put_u64_raw(char *p, uint64_t v)
 inline char *put_str_raw(char *p, const char *s, size_t n) { memcpy(p, s, n); return p + n; }
 }  // namespace
 
-void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_align_result *a, uint64_t r)
+void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_align_result *a, uint64_t r, bool reverse)
 {
     if (!a->aligned[r]) { out += gaf_placeholder(q); return; }
     const char *cs = a->cs + a->cs_off[r], *cg = a->cigar + a->cigar_off[r];
@@ -180,7 +207,7 @@ void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_alig
     char *p = &out[old];
     // align.rs:1145-1167: qstart 0, qend len, '+', residue 0, mapq 255, literal "as:i:-30"
     p = put_str_raw(p, q.name.data(), q.name.size()); *p++ = '\t'; p = put_u64_raw(p, q.seq.size()); p = put_str_raw(p, "\t0\t", 3);
-    p = put_u64_raw(p, q.seq.size()); p = put_str_raw(p, "\t+\t", 3);
+    p = put_u64_raw(p, q.seq.size()); p = put_str_raw(p, reverse ? "\t-\t" : "\t+\t", 3);
     for (uint64_t t = a->path_off[r]; t < a->path_off[r + 1]; t++) {
         const Handle h = a->path_handles[t];
         *p++ = is_rev(h) ? '<' : '>';
@@ -192,10 +219,10 @@ void gaf_from_alignment(std::string &out, const QuerySequence &q, const vga_alig
     out.resize((size_t)(p - out.data()));
 }
 
-std::string gaf_from_alignment(const QuerySequence &q, const vga_align_result *a, uint64_t r)
+std::string gaf_from_alignment(const QuerySequence &q, const vga_align_result *a, uint64_t r, bool reverse)
 {
     std::string out;
-    gaf_from_alignment(out, q, a, r);
+    gaf_from_alignment(out, q, a, r, reverse);
     return out;
 }
 
@@ -235,7 +262,8 @@ std::string validation_record(const Index &ix, const std::string &gaf_line, cons
     const bool rev = ids.size() >= 2 && ids.back() < ids.front();
     const std::string &notes = f[12];
     const size_t comma = notes.rfind(',');
-    std::string out = name + "\n" + (comma == std::string::npos ? notes : notes.substr(comma + 1)) + "\n" + read->seq + "\n[";
+    std::string out = name + "\n" + (comma == std::string::npos ? notes : notes.substr(comma + 1)) + "\n" +
+                      (f[4] == "-" ? reverse_complement(read->seq) : read->seq) + "\n[";
     for (size_t i = 0; i < ids.size(); i++) out += (i ? ", " : "") + std::to_string(ids[i]);
     out += "]\n[";
     for (size_t i = 0; i < ids.size(); i++) {
@@ -416,7 +444,7 @@ private:
 
 struct ChunkOut {
     std::vector<std::string> chains, aligns;  // GAF text in read order, in pieces
-    uint64_t n_aligned = 0, n_anchors = 0, poa_cells = 0;
+    uint64_t n_aligned = 0, n_anchors = 0, poa_cells = 0, n_reverse = 0;
     double ms_map = 0, ms_align = 0;
 };
 
@@ -463,10 +491,13 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
     mp.max_gap = opt.max_gap;
     mp.chain_min_n_anchors = (uint32_t)opt.chain_min_n_anchors;
     mp.emit_dp = 0;  // the GAF writers read anchor coordinates and chain membership only
+    if (opt.both_strands) mp.strands = VGA_STRANDS_BOTH;
     vga_map_result *m = nullptr;
     if (vga_map_batch(b, &mp, &m) != VGA_OK) throw Error(vga_last_error(ctx));
     std::unique_ptr<vga_map_result, void (*)(vga_map_result *)> m_owner(m, vga_map_result_free);
     out.n_anchors = m->n_anchors;
+    if (m->strand)
+        for (uint64_t r = 0; r < n; r++) out.n_reverse += m->strand[r];
     out.ms_map = m->ms_total;
     mark("batch + vga_map_batch");
     // chains GAF (map.rs:123-145): every chain of every read, in order.  The path column of every chain is written by the GPU
@@ -529,7 +560,7 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
         wait_k6();
         b_owner.reset();
         if (hooks.gpu_done) hooks.gpu_done();
-        out.aligns = text_of_reads(n, T, [&](uint64_t r, std::string &dst) { gaf_from_alignment(dst, inputs[b0 + r], a, r); },
+        out.aligns = text_of_reads(n, T, [&](uint64_t r, std::string &dst) { gaf_from_alignment(dst, inputs[b0 + r], a, r, m->strand && m->strand[r]); },
                                    [&](uint64_t r) {
                                        return (size_t)(a->cs_off[r + 1] - a->cs_off[r]) + (size_t)(a->cigar_off[r + 1] - a->cigar_off[r]) +
                                               (size_t)(a->path_off[r + 1] - a->path_off[r]) * 8 + inputs[b0 + r].name.size() + 160;
@@ -671,7 +702,7 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         map_chunk(ctx, ix, inputs, s.begin, s.end, opt, c, ChunkHooks(), text_threads(1));
         append_pieces(out.chains_gaf, c.chains);
         append_pieces(out.alignments_gaf, c.aligns);
-        out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells;
+        out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells; out.n_reverse += c.n_reverse;
         out.ms_map += c.ms_map; out.ms_align += c.ms_align;
         out.n_chunks++;
     }
@@ -884,6 +915,7 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
             append_pieces(out.alignments_gaf, parts[i].aligns);
         }
         out.n_aligned += parts[i].n_aligned; out.n_anchors += parts[i].n_anchors; out.poa_cells += parts[i].poa_cells;
+        out.n_reverse += parts[i].n_reverse;
         ms_map[plan[i].slot] += parts[i].ms_map; ms_align[plan[i].slot] += parts[i].ms_align;
     }
     for (uint32_t s = 0; s < n_slots; s++) { out.ms_map = std::max(out.ms_map, ms_map[s]); out.ms_align = std::max(out.ms_align, ms_align[s]); }

@@ -50,6 +50,11 @@ def load_library():
     L.vgh_gaf_alignment_record.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p]
     L.vgh_gaf_alignment_record.restype = vp
+    L.vgh_gaf_alignment_record_strand.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p]
+    L.vgh_gaf_alignment_record_strand.restype = vp
+    L.vgh_gaf_chain_record.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, C.c_char_p]
+    L.vgh_gaf_chain_record.restype = vp
     L.vgh_textpath_replay.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p, C.c_uint32, C.c_uint32,
                                       C.POINTER(C.c_double)]
     L.vgh_free.argtypes = [vp]
@@ -220,3 +225,29 @@ def gaf_alignment_record(name: str, seq_len: int, aligned: bool, handles: Sequen
         return C.string_at(p).decode()
     finally:
         L.vgh_free(p)
+
+
+def _take_text(L, p) -> str:
+    if not p:
+        raise HostError(L.vgh_last_error().decode())
+    try:
+        return C.string_at(p).decode()
+    finally:
+        L.vgh_free(p)
+
+
+def gaf_alignment_record_strand(name: str, seq_len: int, reverse: bool, handles: Sequence[int], path_length: int, path_start: int,
+                                path_end: int, block_length: int, cs: str, cigar: str) -> str:
+    """the alignments-GAF record of an aligned read; reverse: --both-strands mapped it on its reverse complement ('-')"""
+    L = load_library()
+    hs = (C.c_uint64 * max(1, len(handles)))(*handles)
+    return _take_text(L, L.vgh_gaf_alignment_record_strand(name.encode(), seq_len, 1 if reverse else 0, hs, len(handles), path_length,
+                                                           path_start, path_end, block_length, cs.encode(), cigar.encode()))
+
+
+def gaf_chain_record(name: str, seq_len: int, k: int, strand: int, query_begin: Sequence[int], path: str) -> str:
+    """the chains-GAF record of a read with one chain whose anchors start at query_begin (in the frame of the orientation that was
+    mapped: strand 1 = the reverse complement), path column as given (vgh::gaf_from_chain_text)"""
+    L = load_library()
+    qb = (C.c_uint32 * max(1, len(query_begin)))(*query_begin)
+    return _take_text(L, L.vgh_gaf_chain_record(name.encode(), seq_len, k, strand, qb, len(query_begin), path.encode()))

@@ -51,6 +51,15 @@ class SimRead:
     path: str
     offset: int
     template_len: int = 0  # bases of the source path the read was drawn from (before errors)
+    strand: str = "+"      # "-": seq is the reverse complement of the read drawn from the path
+
+
+_SWITCH = {ord(a): b for a, b in zip("ACGTUacgtu", "TGCAAtgcaa")}
+
+
+def reverse_complement(s: str) -> str:
+    """the reference's switch_base over the reversed read (src/dna.rs:20-33): any byte outside it becomes N"""
+    return "".join(_SWITCH.get(ord(c), "N") for c in reversed(s))
 
 
 def _mutate(tpl: np.ndarray, rng: np.random.Generator, sub: float, ins: float, dele: float) -> bytes:
@@ -99,7 +108,9 @@ def _mutate(tpl: np.ndarray, rng: np.random.Generator, sub: float, ins: float, d
 
 
 def simulate_reads(gfa_path: str, n_reads: int, read_len: int, sub: float, ins: float, dele: float,
-                   seed: int = 77, forward_only: bool = True) -> List[SimRead]:
+                   seed: int = 77, forward_only: bool = True, reverse_fraction: float = 0.0) -> List[SimRead]:
+    """reverse_fraction: the share of reads that come out as the reverse complement of what was drawn (strand "-").  The coin
+    comes from a generator of its own, so the draws of the forward reads -- and every read set made without it -- are unchanged."""
     segs, paths = parse_gfa_paths(gfa_path)
     seqs = []
     for name, steps in paths:
@@ -109,6 +120,7 @@ def simulate_reads(gfa_path: str, n_reads: int, read_len: int, sub: float, ins: 
     if not seqs:
         raise ValueError("no forward path in " + gfa_path)
     rng = np.random.Generator(np.random.PCG64(seed))
+    coin = np.random.Generator(np.random.PCG64([seed, 0x5eed])).random(n_reads) if reverse_fraction > 0 else None
     reads: List[SimRead] = []
     for r in range(n_reads):
         pi = int(rng.integers(0, len(seqs)))
@@ -120,7 +132,10 @@ def simulate_reads(gfa_path: str, n_reads: int, read_len: int, sub: float, ins: 
             seq = tpl.tobytes().decode()
         else:
             seq = _mutate(tpl, rng, sub, ins, dele).decode()
-        reads.append(SimRead(f"read{r}", seq, name, off, L))
+        if coin is not None and coin[r] < reverse_fraction:
+            reads.append(SimRead(f"read{r}", reverse_complement(seq), name, off, L, "-"))
+        else:
+            reads.append(SimRead(f"read{r}", seq, name, off, L))
     return reads
 
 
@@ -154,7 +169,7 @@ def truth_gaf(gfa_path: str, reads: List[SimRead]) -> str:
             pos += ln
             if pos >= hi:
                 break
-        out.append("\t".join([r.name, str(len(r.seq)), "0", str(len(r.seq)), "+", "".join(nodes), str(tpl), "0", str(tpl), "0",
+        out.append("\t".join([r.name, str(len(r.seq)), "0", str(len(r.seq)), getattr(r, "strand", "+"), "".join(nodes), str(tpl), "0", str(tpl), "0",
                               str(tpl), "255", "ta:Z:truth"]))
     return "\n".join(out) + ("\n" if out else "")
 
