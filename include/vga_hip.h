@@ -27,12 +27,16 @@ extern "C" {
 #define VGA_ERR_ARG (-1)
 #define VGA_ERR_HIP (-2)          /* a HIP runtime call failed (message has the hipError string) */
 #define VGA_ERR_NOMEM (-3)
-#define VGA_ERR_UNSUPPORTED (-4)  /* k > 15, non-ACGT k-mer in the table, bandwidth > 64, ... */
+#define VGA_ERR_UNSUPPORTED (-4)  /* k > 32, non-ACGT k-mer in the table, bandwidth > 64, ... */
 #define VGA_ERR_NO_INDEX (-5)
 #define VGA_ERR_NO_DEVICE (-6)    /* no gfx950 device visible: the library never falls back to a CPU path */
 #define VGA_ERR_POOL (-7)         /* traceback pool exhausted; retry with a smaller sub-batch */
 
 #define VGA_NO_PRED (-1)
+
+/* the longest k-mer vga_index_upload accepts: k <= 15 is probed through a direct-address table, 16 <= k <= 32 through a
+ * table hashed on the 2-bit packed k-mer (64 bits) */
+#define VGA_MAX_KMER_LENGTH 32
 
 typedef struct vga_ctx vga_ctx;
 
@@ -90,7 +94,9 @@ typedef struct {
 } vga_index_desc;
 
 /* Stands in for Index::load_from_file + every per-read Index accessor
- * (src/index.rs:296-305, 309-382, 388-606): copies the index to HBM once. */
+ * (src/index.rs:296-305, 309-382, 388-606): copies the index to HBM once.
+ * VGA_ERR_UNSUPPORTED: kmer_length outside 1..VGA_MAX_KMER_LENGTH, a k-mer with a base outside upper-case ACGT, a graph
+ * beyond 32-bit device coordinates.  On failure the context holds no index. */
 int vga_index_upload(vga_ctx *ctx, const vga_index_desc *desc);
 
 /* Stands in for generate_kmers_parallel + sort/dedup + generate_pos_on_ref_2 of Index::build
@@ -99,7 +105,8 @@ int vga_index_upload(vga_ctx *ctx, const vga_index_desc *desc);
  * (n_kmers, kmer_keys, kmer_starts, n_kmer_pos, kmer_pos_table) with arrays the library allocates; release them with
  * vga_index_kmers_free.  On VGA_OK the context also holds the index, exactly as after vga_index_upload(ctx, desc), with
  * the probe tables built on the device.  The arrays equal the host builder's byte for byte.
- * VGA_ERR_UNSUPPORTED: k = 0 or k > 15, a byte of seq_fwd outside upper-case ACGTN, an empty node, a graph beyond 32-bit
+ * VGA_ERR_UNSUPPORTED: k = 0 or k > 15 (the k-mer walk on the GPU keeps 32-bit keys: the host builder handles k-mers of up to
+ * VGA_MAX_KMER_LENGTH bases, and vga_index_upload takes its index), a byte of seq_fwd outside upper-case ACGTN, an empty node, a graph beyond 32-bit
  * device coordinates.  VGA_ERR_NOMEM (with a message, never a fault) when the k-mer paths blow up.  A graph with no
  * k-mer of this length fails with the host's message.  On failure the context holds no index.  With ctx == NULL:
  * VGA_ERR_NO_DEVICE when no GPU is visible (there is no CPU path).
@@ -125,7 +132,7 @@ typedef struct {
     uint32_t chain_min_n_anchors; /* 3    (map_main.rs:42-46) */
     int only_forward;             /* 1    (src/map.rs:62).  0 = anchors_for_query(.., false) (src/chain.rs:154-155): every
                                    * k-mer record becomes an anchor and bit 31 of target_begin / target_end is the
-                                   * orientation of that end (1 = reverse strand); k <= 13; such chains cannot be passed
+                                   * orientation of that end (1 = reverse strand); k <= 13 or k >= 16; such chains cannot be passed
                                    * to vga_align_batch unless they are all-forward */
     int emit_dp;                  /* 1: the result also carries Anchor.id, f(i) and the best predecessor of every anchor
                                    *    (what the reference keeps inside chain_anchors; parity checks read them).

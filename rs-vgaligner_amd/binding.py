@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VGA_LIB") or os.path.join(_HERE, "libvga_hip.so")  # 
 
 VGA_OK = 0
 # vga_map_params.strands
+VGA_MAX_KMER_LENGTH = 32  # include/vga_hip.h: the longest k-mer vga_index_upload accepts (hashed probe table from k = 16)
 VGA_STRANDS_FORWARD = 0
 VGA_STRANDS_BOTH = 1
 ERR_NAMES = {-1: "VGA_ERR_ARG", -2: "VGA_ERR_HIP", -3: "VGA_ERR_NOMEM", -4: "VGA_ERR_UNSUPPORTED",

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vga_hip.h"
+#include "vga_probe_hash.hpp"
 
 #define VGA_ABI_VERSION 6
 
@@ -24,7 +25,7 @@ struct vga_dev_index {
     uint32_t k = 0;
     uint64_t seq_length = 0;
     uint64_t n_nodes = 0, n_edges = 0;
-    // k-mer probe: direct-address table on the 2-bit packed k-mer.
+    // k-mer probe, k <= 15: direct-address table on the 2-bit packed k-mer.
     // table[key] = index of the group's header word pair in pos (or 0xFFFFFFFF);
     // pos[h] = {count, 0}, pos[h+1..h+count] = {target_begin, target_end} of the forward/forward
     // records in table order (src/kmer.rs:894 order, src/chain.rs:154 filter).
@@ -35,6 +36,15 @@ struct vga_dev_index {
     // the same with the records of every orientation (k <= 13): bit 31 of target_begin / target_end = reverse strand
     uint32_t *d_table_all = nullptr;
     uint2 *d_pos_all = nullptr;
+    // k-mer probe, 16 <= k <= 32 (and any k under VGA_PROBE_TABLE=hash): one hashed table on the 64-bit packed k-mer
+    // (vga_probe_hash.hpp) in place of d_table and d_table_all; its two header columns index d_pos_all and d_pos, whose
+    // layout is the one above.  hash_mask = capacity - 1.
+    vga_hash_slot *d_hash = nullptr;
+    uint32_t hash_mask = 0;
+    // only_forward = 0 can be served: k <= 13 (direct tables) or k >= 16 (the hashed table costs memory per k-mer present)
+    bool all_view = false;
+    // device bytes of the probe tables (d_table + d_table_all, or d_hash) and of the position arrays
+    uint64_t probe_table_bytes = 0, probe_pos_bytes = 0;
     // the graph itself for the device-side subgraph extraction (vga_subgraph.hip): forward sequence, node starts
     // (n_nodes + 1), per node the first edge / the number of incoming edges, the edge lists as packed handles
     char *d_seq_fwd = nullptr;

@@ -5,6 +5,7 @@
 // (src/index.rs:71,236, src/kmer.rs:931-934) are replaced by a direct-address table on the 2-bit
 // packed k-mer: the reference tests exact membership (index.rs:319) before asking the MPHF, so any
 // exact map gives the same answers, and 4^11 * 4 B = 16 MiB sits in the 256 MiB Infinity Cache.
+// From k = 16 (4^k entries no longer fit) the table is hashed on the 64-bit packed k-mer, vga_probe_hash.hpp.
 #include "vga_common.hpp"
 
 #include <mutex>
@@ -148,6 +149,7 @@ void vga_index_release(vga_dev_index &ix)
     if (ix.d_pos) (void)hipFree(ix.d_pos);
     if (ix.d_table_all) (void)hipFree(ix.d_table_all);
     if (ix.d_pos_all) (void)hipFree(ix.d_pos_all);
+    if (ix.d_hash) (void)hipFree(ix.d_hash);
     if (ix.d_seq_fwd) (void)hipFree(ix.d_seq_fwd);
     if (ix.d_node_start) (void)hipFree(ix.d_node_start);
     if (ix.d_edge_idx) (void)hipFree(ix.d_edge_idx);
@@ -334,46 +336,86 @@ int vga_index_load_graph(vga_ctx *ctx, const vga_index_desc *d)
     return VGA_OK;
 }
 
+// Fills the hashed probe table (vga_probe_hash.hpp): one thread per k-mer of the index.  The keys of an index are distinct,
+// so a thread claims the first empty slot of its probe sequence with a 32-bit atomicCAS on the claim word hdr_all and then
+// stores the key and the second column plainly; nothing reads the table before the kernel has finished.  Which slot a key
+// lands in depends on timing, what a lookup returns does not.  At load <= 1/2 an empty slot always exists; the walk is
+// bounded by the capacity all the same, and a key that found no slot is counted in *n_failed.
+__global__ __launch_bounds__(256) void k_probe_hash_insert(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ hdr_all,
+                                                           const uint32_t *__restrict__ hdr_ff, uint64_t n, vga_hash_slot *slots,
+                                                           uint32_t mask, uint32_t *n_failed)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const uint64_t key = keys[g];
+    const uint32_t ha = hdr_all[g];
+    uint32_t s = vga_hash_first_slot(key, mask);
+    for (uint64_t tries = 0; tries <= mask; tries++, s = vga_hash_next_slot(s, mask)) {
+        if (atomicCAS(&slots[s].hdr_all, VGA_HASH_EMPTY, ha) != VGA_HASH_EMPTY) continue;
+        slots[s].key = key;
+        slots[s].hdr_ff = hdr_ff[g];
+        return;
+    }
+    atomicAdd(n_failed, 1u);
+}
+
 static int vga_index_upload_impl(vga_ctx *ctx, const vga_index_desc *d)
 {
     if (!ctx || !d) return VGA_ERR_ARG;
     (void)hipSetDevice(ctx->device);
-    if (d->kmer_length == 0 || d->kmer_length > 15)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "kmer_length %u: the direct-address probe table supports 1..15",
-                             d->kmer_length);
+    vga_index_release(ctx->index);  // whatever happens next, the previous index is gone: a refused upload leaves no index
+    if (d->kmer_length == 0 || d->kmer_length > VGA_MAX_KMER_LENGTH)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                             "kmer_length %u: the probe tables support 1..%d (direct-address up to 15, hashed on the 64-bit "
+                             "packed k-mer from 16)",
+                             d->kmer_length, VGA_MAX_KMER_LENGTH);
     if (d->seq_length >= (1ull << 31) || d->n_nodes >= (1ull << 30) || d->n_edges >= (1ull << 31))
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "graph too large for 32-bit device coordinates");
     if (!d->seq_fwd || !d->node_seq_idx || !d->node_edge_idx || !d->node_edges_to || (!d->edges && d->n_edges) ||
         !d->kmer_keys || !d->kmer_starts || !d->kmer_pos_table)
         return vga_set_error(ctx, VGA_ERR_ARG, "null array in vga_index_desc");
 
-    vga_index_release(ctx->index);
     vga_dev_index &ix = ctx->index;
     ix.k = d->kmer_length;
+    vga_trace tr("index_upload");
 
     // Build the probe tables on the host, then copy once: the forward/forward records only (what map_reads asks for,
-    // src/map.rs:62) and, for k <= 13, every record with the orientations of its two ends in bit 31 of the positions
-    // (anchors_for_query(..., only_forward = false), src/chain.rs:154-155).
+    // src/map.rs:62) and, for k <= 13 and k >= 16, every record with the orientations of its two ends in bit 31 of the
+    // positions (anchors_for_query(..., only_forward = false), src/chain.rs:154-155).
     const uint32_t k = d->kmer_length;
-    const uint64_t entries = 1ull << (2 * k);
-    auto build = [&](bool all, std::vector<uint32_t> &table, std::vector<uint2> &pos) -> int {
-        table.assign(entries, 0xFFFFFFFFu);
+    // diagnostics: VGA_PROBE_TABLE=hash builds the hashed table for k <= 15 too (the two kinds compared on one index)
+    const char *kind = getenv("VGA_PROBE_TABLE");
+    if (kind && strcmp(kind, "hash") != 0 && strcmp(kind, "direct") != 0)
+        return vga_set_error(ctx, VGA_ERR_ARG, "VGA_PROBE_TABLE=%s: hash or direct", kind);
+    const bool hashed = k > 15 || (kind && strcmp(kind, "hash") == 0);
+    ix.all_view = k <= 13 || k >= 16;
+
+    // the 2-bit packed keys, in index order
+    std::vector<uint64_t> keys(d->n_kmers);
+    for (uint64_t g = 0; g < d->n_kmers; g++) {
+        const char *key = d->kmer_keys + g * k;
+        uint64_t packed = 0;
+        bool acgt = true;
+        for (uint32_t t = 0; t < k; t++) {
+            int c = vga_base_code(key[t]);
+            if (c < 0) { acgt = false; break; }
+            packed = (packed << 2) | (uint64_t)c;
+        }
+        if (!acgt) {
+            vga_index_release(ctx->index);
+            return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                                 "k-mer %llu of the index holds a base outside upper-case A/C/G/T; the 2-bit probe "
+                                 "table cannot represent it",
+                                 (unsigned long long)g);
+        }
+        keys[g] = packed;
+    }
+    // hdr[g]: where the group of k-mer g starts in pos, or 0xFFFFFFFF when it has no record of this view
+    auto build = [&](bool all, std::vector<uint32_t> &hdr, std::vector<uint2> &pos) -> int {
+        hdr.assign(d->n_kmers, 0xFFFFFFFFu);
         pos.clear();
         pos.reserve(d->n_kmer_pos + d->n_kmers);
         for (uint64_t g = 0; g < d->n_kmers; g++) {
-            const char *key = d->kmer_keys + g * k;
-            uint64_t packed = 0;
-            bool acgt = true;
-            for (uint32_t t = 0; t < k; t++) {
-                int c = vga_base_code(key[t]);
-                if (c < 0) { acgt = false; break; }
-                packed = (packed << 2) | (uint64_t)c;
-            }
-            if (!acgt)
-                return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
-                                     "k-mer %llu of the index holds a base outside upper-case A/C/G/T; the 2-bit probe "
-                                     "table cannot represent it",
-                                     (unsigned long long)g);
             uint64_t s = d->kmer_starts[g];
             if (s >= d->n_kmer_pos) return vga_set_error(ctx, VGA_ERR_ARG, "kmer_starts out of range");
             size_t header = pos.size();
@@ -396,29 +438,108 @@ static int vga_index_upload_impl(vga_ctx *ctx, const vga_index_desc *d)
             }
             pos[header].x = cnt;
             if (pos.size() >= 0xFFFFFFFFull) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "position table too large");
-            table[packed] = (uint32_t)header;
+            hdr[g] = (uint32_t)header;
         }
         if (pos.empty()) pos.push_back(make_uint2(0u, 0u));
         return VGA_OK;
     };
-    std::vector<uint32_t> table;
+    std::vector<uint32_t> hdr;
     std::vector<uint2> pos;
-    if (int rc = build(false, table, pos)) { vga_index_release(ctx->index); return rc; }
-    ix.table_entries = entries;
-    ix.n_pos_words = pos.size();
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_table, entries * sizeof(uint32_t)));
-    VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_pos, pos.size() * sizeof(uint2)));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_table, table.data(), entries * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_pos, pos.data(), pos.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (k <= 13) {
-        if (int rc = build(true, table, pos)) { vga_index_release(ctx->index); return rc; }
-        VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_table_all, entries * sizeof(uint32_t)));
-        VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_pos_all, pos.size() * sizeof(uint2)));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_table_all, table.data(), entries * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(ix.d_pos_all, pos.data(), pos.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    auto upload_pos = [&](uint2 **d_pos) -> int {
+        VGA_HIP_CHECK(ctx, hipMalloc((void **)d_pos, pos.size() * sizeof(uint2)));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(*d_pos, pos.data(), pos.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
         VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        ix.probe_pos_bytes += pos.size() * sizeof(uint2);
+        return VGA_OK;
+    };
+    auto fail = [&](int rc) { vga_index_release(ctx->index); return rc; };
+
+    if (!hashed) {
+        const uint64_t entries = 1ull << (2 * k);
+        std::vector<uint32_t> table;
+        auto upload_table = [&](uint32_t **d_table) -> int {
+            table.assign(entries, 0xFFFFFFFFu);
+            for (uint64_t g = 0; g < d->n_kmers; g++)
+                if (hdr[g] != 0xFFFFFFFFu) table[keys[g]] = hdr[g];
+            VGA_HIP_CHECK(ctx, hipMalloc((void **)d_table, entries * sizeof(uint32_t)));
+            VGA_HIP_CHECK(ctx, hipMemcpyAsync(*d_table, table.data(), entries * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            ix.probe_table_bytes += entries * sizeof(uint32_t);
+            return VGA_OK;
+        };
+        if (int rc = build(false, hdr, pos)) return fail(rc);
+        ix.table_entries = entries;
+        ix.n_pos_words = pos.size();
+        if (int rc = upload_table(&ix.d_table)) return fail(rc);
+        if (int rc = upload_pos(&ix.d_pos)) return fail(rc);
+        if (ix.all_view) {
+            if (int rc = build(true, hdr, pos)) return fail(rc);
+            if (int rc = upload_table(&ix.d_table_all)) return fail(rc);
+            if (int rc = upload_pos(&ix.d_pos_all)) return fail(rc);
+        }
+    } else {
+        // the hashed table wants distinct keys (two slots with one key would make a lookup depend on timing); the keys of an
+        // index are sorted, so one pass tells, and a copy is sorted when they are not
+        {
+            bool increasing = true;
+            for (uint64_t g = 1; g < d->n_kmers && increasing; g++) increasing = keys[g - 1] < keys[g];
+            if (!increasing) {
+                std::vector<uint64_t> sorted(keys);
+                std::sort(sorted.begin(), sorted.end());
+                if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+                    return fail(vga_set_error(ctx, VGA_ERR_ARG, "a k-mer occurs twice in kmer_keys"));
+            }
+        }
+        const uint64_t cap = vga_hash_capacity(d->n_kmers);
+        if (cap == 0) return fail(vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%llu k-mers: too many for the hashed probe table", (unsigned long long)d->n_kmers));
+        std::vector<uint32_t> hdr_ff;
+        if (int rc = build(false, hdr_ff, pos)) return fail(rc);
+        ix.n_pos_words = pos.size();
+        if (int rc = upload_pos(&ix.d_pos)) return fail(rc);
+        if (int rc = build(true, hdr, pos)) return fail(rc);
+        if (int rc = upload_pos(&ix.d_pos_all)) return fail(rc);
+        // a k-mer without any record has no group: it stays out of the table (hdr_all is the claim word)
+        uint64_t n_ins = 0;
+        for (uint64_t g = 0; g < d->n_kmers; g++) {
+            if (hdr[g] == 0xFFFFFFFFu) continue;
+            keys[n_ins] = keys[g];
+            hdr[n_ins] = hdr[g];
+            hdr_ff[n_ins] = hdr_ff[g];
+            n_ins++;
+        }
+        ix.hash_mask = (uint32_t)(cap - 1);
+        ix.probe_table_bytes = cap * sizeof(vga_hash_slot);
+        uint64_t *d_keys = nullptr;
+        uint32_t *d_hdr = nullptr;  // hdr_all (n_ins), hdr_ff (n_ins), the failure counter
+        auto insert = [&]() -> int {
+            VGA_HIP_CHECK(ctx, hipMalloc((void **)&ix.d_hash, cap * sizeof(vga_hash_slot)));
+            VGA_HIP_CHECK(ctx, hipMemsetAsync(ix.d_hash, 0xFF, cap * sizeof(vga_hash_slot), ctx->stream));
+            if (n_ins == 0) return VGA_OK;
+            VGA_HIP_CHECK(ctx, hipMalloc((void **)&d_keys, n_ins * sizeof(uint64_t)));
+            VGA_HIP_CHECK(ctx, hipMalloc((void **)&d_hdr, (2 * n_ins + 1) * sizeof(uint32_t)));
+            VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_keys, keys.data(), n_ins * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+            VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_hdr, hdr.data(), n_ins * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_hdr + n_ins, hdr_ff.data(), n_ins * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VGA_HIP_CHECK(ctx, hipMemsetAsync(d_hdr + 2 * n_ins, 0, sizeof(uint32_t), ctx->stream));
+            hipLaunchKernelGGL(k_probe_hash_insert, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)d_keys,
+                               (const uint32_t *)d_hdr, (const uint32_t *)(d_hdr + n_ins), n_ins, ix.d_hash, ix.hash_mask, d_hdr + 2 * n_ins);
+            VGA_HIP_CHECK(ctx, hipGetLastError());
+            uint32_t n_failed = 0;
+            VGA_HIP_CHECK(ctx, hipMemcpyAsync(&n_failed, d_hdr + 2 * n_ins, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            if (n_failed) return vga_set_error(ctx, VGA_ERR_HIP, "k_probe_hash_insert: %u k-mers found no slot", n_failed);
+            return VGA_OK;
+        };
+        const int rc = insert();
+        if (rc != VGA_OK) (void)hipStreamSynchronize(ctx->stream);  // (the staging arrays below may still be read)
+        if (d_keys) (void)hipFree(d_keys);
+        if (d_hdr) (void)hipFree(d_hdr);
+        if (rc != VGA_OK) return fail(rc);
     }
+    if (tr.on)
+        fprintf(stderr, "[vga-trace] index_upload: k %u %s probe table %llu bytes, positions %llu bytes, %llu k-mers\n", k,
+                hashed ? "hashed" : "direct", (unsigned long long)ix.probe_table_bytes, (unsigned long long)ix.probe_pos_bytes,
+                (unsigned long long)d->n_kmers);
+    tr.mark("probe tables");
     if (int rc = vga_index_load_graph(ctx, d)) return rc;
     ix.loaded = true;
     return VGA_OK;

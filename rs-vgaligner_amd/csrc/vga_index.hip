@@ -496,7 +496,10 @@ bool ix_acgtn(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c
 int ix_validate(vga_ctx *ctx, const vga_index_desc *d)
 {
     if (d->kmer_length == 0 || d->kmer_length > 15)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "kmer_length %u: the direct-address probe table supports 1..15", d->kmer_length);
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                             "kmer_length %u: the k-mer walk on the GPU supports 1..15; the host builder handles k-mers of up to %d bases "
+                             "(vgh_index_build, `vgaligner index` without --device)",
+                             d->kmer_length, VGA_MAX_KMER_LENGTH);
     if (d->seq_length >= (1ull << 31) || d->n_nodes >= (1ull << 30) || d->n_edges >= (1ull << 31))
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "graph too large for 32-bit device coordinates");
     if (!d->seq_fwd || !d->node_seq_idx || !d->node_edge_idx || !d->node_edges_to || (!d->edges && d->n_edges) || d->n_nodes == 0)
@@ -647,6 +650,9 @@ int ix_build_impl(vga_ctx *ctx, vga_index_desc *d, uint64_t max_furc, uint64_t m
     }
     ix.table_entries = entries;
     ix.n_pos_words = n_words;
+    ix.all_view = ix.d_table_all != nullptr;
+    ix.probe_table_bytes = (ix.d_table_all ? 2 : 1) * entries * sizeof(uint32_t);
+    ix.probe_pos_bytes = (n_words + (ix.d_pos_all ? NP : 0)) * sizeof(uint2);
     VGA_HIP_CHECK(ctx, hipMemsetAsync(ix.d_table, 0xFF, entries * sizeof(uint32_t), st));
     VGA_HIP_CHECK(ctx, hipMemsetAsync(ix.d_pos, 0, n_words * sizeof(uint2), st));
     if (ix.d_table_all) VGA_HIP_CHECK(ctx, hipMemsetAsync(ix.d_table_all, 0xFF, entries * sizeof(uint32_t), st));

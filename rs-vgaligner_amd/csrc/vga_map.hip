@@ -1,8 +1,9 @@
 // vga_map.hip -- anchors + chaining on gfx950.
 //
-//   K1  k_kmer_probe<false/true>  split_into_kmers + find_positions_for_query_kmer + the forward
+//   K1  k_kmer_probe<EMIT, HASH>  split_into_kmers + find_positions_for_query_kmer + the forward
 //                                 filter and id assignment of anchors_for_query
-//                                 (src/io.rs:41-56, src/index.rs:309-382, src/chain.rs:134-173)
+//                                 (src/io.rs:41-56, src/index.rs:309-382, src/chain.rs:134-173);
+//                                 HASH: the 64-bit-key walk of the hashed table (k >= 16)
 //   K2  k_anchor_sort             the stable sort of chain_anchors (src/chain.rs:386-389)
 //   K3  k_chain4                  the windowed DP (src/chain.rs:398-450, score_anchor 274-368) and
 //                                 the backtracking into chains (src/chain.rs:455-558)
@@ -67,12 +68,17 @@ __device__ __forceinline__ uint32_t vga_base_code_dev(uint8_t c)
 // One block per read.  Pass 1 (EMIT=false) counts the anchors of each read; pass 2 (EMIT=true)
 // writes them at anchor_off[r] in (query position, table order) order, which is the order
 // anchors_for_query assigns ids in (src/chain.rs:146-166): anchor id == index within the read.
-template <bool EMIT>
+//
+// HASH = false: `table` is the direct-address table (const uint32_t *, 4^k entries), the key has 2k <= 30 bits.
+// HASH = true:  `table` is the hashed table (const vga_hash_slot *, hash_mask + 1 slots, vga_probe_hash.hpp), the key has up to
+// 64 bits; a thread walks slots from the key's hash until it meets the key or an empty slot (claim word hdr_all) and takes
+// the header of column hash_ff (1: forward/forward records, 0: every orientation).  A slot is 16 aligned bytes, read as one uint4.
+template <bool EMIT, bool HASH>
 __global__ __launch_bounds__(VGA_PROBE_NT) void k_kmer_probe(
     const char *__restrict__ reads, const uint64_t *__restrict__ read_off, uint32_t k,
-    const uint32_t *__restrict__ table, const uint2 *__restrict__ pos, uint32_t *__restrict__ cnt_out,
+    const void *__restrict__ table, const uint2 *__restrict__ pos, uint32_t *__restrict__ cnt_out,
     const uint64_t *__restrict__ anchor_off, uint32_t *__restrict__ a_qb, uint32_t *__restrict__ a_tb,
-    uint32_t *__restrict__ a_te, uint32_t *__restrict__ a_idx)
+    uint32_t *__restrict__ a_te, uint32_t *__restrict__ a_idx, uint32_t hash_mask, uint32_t hash_ff)
 {
     __shared__ uint8_t codes[VGA_PROBE_NT + 32];
     __shared__ uint32_t ws[4];
@@ -96,15 +102,38 @@ __global__ __launch_bounds__(VGA_PROBE_NT) void k_kmer_probe(
         const uint64_t i = c0 + tid;
         uint32_t cnt = 0, hdr = VGA_NONE32;
         if (i < nk) {
-            uint32_t key = 0, bad = 0;
-            for (uint32_t t = 0; t < k; t++) {
-                uint32_t c = codes[tid + t];
-                bad |= c >> 2;
-                key = (key << 2) | (c & 3u);
-            }
-            if (!bad) {
-                hdr = table[key];
-                if (hdr != VGA_NONE32) cnt = pos[hdr].x;
+            if constexpr (!HASH) {
+                uint32_t key = 0, bad = 0;
+                for (uint32_t t = 0; t < k; t++) {
+                    uint32_t c = codes[tid + t];
+                    bad |= c >> 2;
+                    key = (key << 2) | (c & 3u);
+                }
+                if (!bad) {
+                    hdr = ((const uint32_t *)table)[key];
+                    if (hdr != VGA_NONE32) cnt = pos[hdr].x;
+                }
+            } else {
+                uint64_t key = 0;
+                uint32_t bad = 0;
+                for (uint32_t t = 0; t < k; t++) {
+                    uint32_t c = codes[tid + t];
+                    bad |= c >> 2;
+                    key = (key << 2) | (uint64_t)(c & 3u);
+                }
+                if (!bad) {
+                    const uint4 *slots = (const uint4 *)table;  // vga_hash_slot: {key lo, key hi, hdr_all, hdr_ff}
+                    uint32_t s = vga_hash_first_slot(key, hash_mask);
+                    for (uint32_t tries = 0; tries <= hash_mask; tries++, s = vga_hash_next_slot(s, hash_mask)) {
+                        const uint4 e = slots[s];
+                        if (e.z == VGA_HASH_EMPTY) break;  // an empty slot ends the probe sequence: the key is absent
+                        if ((((uint64_t)e.y << 32) | e.x) == key) {
+                            hdr = hash_ff ? e.w : e.z;
+                            break;
+                        }
+                    }
+                    if (hdr != VGA_NONE32) cnt = pos[hdr].x;
+                }
             }
         }
         uint32_t total;
@@ -617,7 +646,7 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     const bool both = params->strands == VGA_STRANDS_BOTH;
     if (both && all_orients)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "strands = VGA_STRANDS_BOTH maps the read and its reverse complement forward-only: it needs only_forward = 1");
-    if (all_orients && !ctx->index.d_table_all)
+    if (all_orients && !ctx->index.all_view)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "only_forward=0 needs the all-orientation probe table, which is built for k <= 13");
     if (params->bandwidth == 0 || params->bandwidth > 64)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "bandwidth %u: the wavefront chaining kernel supports 1..64", params->bandwidth);
@@ -681,11 +710,16 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     MAP_CHECK(ws.anchor_off.reserve(RV + 1));
     int t_total = vga_timer_begin(ctx, "map_total", 0);
     int t1 = vga_timer_begin(ctx, "kmer_probe_count", 0);
-    const uint32_t *probe_table = all_orients ? ix.d_table_all : ix.d_table;
+    // the loaded index decides the variant: its hashed table (k >= 16) serves both views through its two header columns
+    const bool hashed = ix.d_hash != nullptr;
+    const void *probe_table = hashed ? (const void *)ix.d_hash : (const void *)(all_orients ? ix.d_table_all : ix.d_table);
     const uint2 *probe_pos = all_orients ? ix.d_pos_all : ix.d_pos;
-    hipLaunchKernelGGL(k_kmer_probe<false>, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st, b->d_reads, d_read_off, ix.k,
-                       probe_table, probe_pos, ws.cnt.p, (const uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                       (uint32_t *)nullptr, (uint32_t *)nullptr);
+    const uint32_t hash_ff = all_orients ? 0u : 1u;
+    const auto probe_count = hashed ? k_kmer_probe<false, true> : k_kmer_probe<false, false>;
+    const auto probe_emit = hashed ? k_kmer_probe<true, true> : k_kmer_probe<true, false>;
+    hipLaunchKernelGGL(probe_count, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st,
+                       b->d_reads, d_read_off, ix.k, probe_table, probe_pos, ws.cnt.p, (const uint64_t *)nullptr, (uint32_t *)nullptr,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, ix.hash_mask, hash_ff);
     vga_timer_end(ctx, t1);
     MAP_CHECK(ws.h_cnt.reserve(RV));
     uint32_t *h_cnt = ws.h_cnt.p;
@@ -724,16 +758,18 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     MAP_CHECK(hipMemcpyAsync(ws.gap_cost.p, gc.data(), (mg + 1) * sizeof(double), hipMemcpyHostToDevice, st));
 
     // ---- K1 pass 2: emit
-    // byte model B_map: L + 4(L-k+1) read+table, 8H positions, 16A anchor write
+    // byte model B_map: L + 4(L-k+1) read+table (16 per probe of the hashed table: one slot, more when the walk goes on),
+    // 8H positions, 16A anchor write
     uint64_t nkm = 0;
     for (uint64_t r = 0; r < R; r++) {
         uint64_t L = b->read_off[r + 1] - b->read_off[r];
         if (L >= ix.k) nkm += L - ix.k + 1;
     }
     if (both) nkm *= 2;  // (a reverse complement has the k-mers of its read)
-    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", (both ? 2 : 1) * b->total_bases + 4 * nkm + 8 * total + 16 * total);
-    hipLaunchKernelGGL(k_kmer_probe<true>, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st, b->d_reads, d_read_off, ix.k,
-                       probe_table, probe_pos, (uint32_t *)nullptr, ws.anchor_off.p, ws.a_qb.p, ws.a_tb.p, ws.a_te.p, ws.a_idx.p);
+    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", (both ? 2 : 1) * b->total_bases + (hashed ? 16 : 4) * nkm + 8 * total + 16 * total);
+    hipLaunchKernelGGL(probe_emit, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st,
+                       b->d_reads, d_read_off, ix.k, probe_table, probe_pos, (uint32_t *)nullptr, ws.anchor_off.p, ws.a_qb.p, ws.a_tb.p,
+                       ws.a_te.p, ws.a_idx.p, ix.hash_mask, hash_ff);
     vga_timer_end(ctx, t2);
 
     // ---- K2: sort by target_end
