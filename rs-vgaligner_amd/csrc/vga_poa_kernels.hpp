@@ -1,70 +1,17 @@
-// vga_poa_kernels.hpp -- device side of the POA engine shared by every DP kernel: problem / row / result records, the
-// fallback kernel k_poa_dp_lds<NT,4> (any gap penalties that fit a byte per gap state), the traceback (K4b) and the LDS
-// sizing helpers.  Included by vga_poa.hip only; the default kernels live in vga_poa_t4.hpp / vga_poa_t5.hpp.
+// vga_poa_kernels.hpp -- device side of the POA engine shared by every DP kernel: the chunk pool's device half, the
+// fallback kernel k_poa_dp_lds<NT,4> (any gap penalties that fit a byte per gap state) and the traceback (K4b).
+// Included by vga_poa.hip only; the default kernels live in vga_poa_t4.hpp / vga_poa_t5.hpp.  The problem / row / result
+// records are in vga_poa_launch.hpp (the host code reads them too), the LDS sizes in vga_poa_shape.hpp.
 #pragma once
 
 #define POA_NEG (-(1 << 21))  // "minus infinity"; H stays inside 23 signed bits (see k_poa_dp_pk)
 #define POA_IDENT (INT32_MIN / 2)
-#define POA_CHUNK (1ull << 20)
-#define POA_RING_SPAN 32  // value rows read within this many nodes live in the per-problem ring, the others are kept
-#define POA_SLOTS 4  // most sub-batches in flight (VGA_POA_SLOTS; default 2): own stream, pool segment and staging buffers each
-
-#define POA_ST_OK 0
-#define POA_ST_POOL 1
-#define POA_ST_NOALN 2
-#define POA_ST_TRACE 3
-#define POA_ST_RETRY 5  // a specialised DP kernel hands the problem back: it is re-run by the general one (k_poa_dp_t4)
-
-struct poa_prob {
-    uint64_t node0;  // first entry of the node table (entry 0 of a problem is the virtual source)
-    uint64_t pred0;  // first entry of the predecessor list (row ids)
-    uint64_t sink0;  // first entry of the sink predecessor list
-    uint64_t q0;     // first query byte
-    uint64_t ops0;   // first entry of the traceback output
-    uint64_t row0;   // first entry of the per-row arrays (rows 0..N)
-    uint64_t seq0;   // first byte of the node sequences (row r is byte r-1)
-    uint32_t n_sink;
-    uint32_t qlen;
-    uint32_t N;
-    uint32_t w;      // adaptive band half-width: wb + floor(wf * qlen), computed on the host in double
-    uint32_t n_nodes;  // node-table entries incl. the source
-    uint32_t ring_rows;  // value rows of node-end rows live in a ring of this many worst-case rows (k_poa_dp_pk)
-    uint32_t flags;      // bit 0: too large for an arena (k_poa_dp_pk in arena mode reports POA_ST_POOL at once)
-    uint32_t pad;
-};
-
-struct poa_row {          // per DP row, 48 B
-    int32_t beg, end;     // band
-    uint64_t doff, voff;  // direction row / value row in the pool
-    int32_t lmax, rmax;   // leftmost / rightmost column of the row maximum
-    // the last four words form one aligned 16-byte group: k_poa_rowprep fills them for k_poa_dp_w1, which reads them with a
-    // single scalar load per row
-    uint32_t pred, npred; // predecessor row or predecessor-list slice; npred != 0 only on the first row of a node
-    int32_t base, hmax;   // k_poa_dp_pk<.., H16>: the row's values are stored relative to `base`, hmax = the row maximum.
-                          // k_poa_dp_w1: base = graph bases after this row on the longest path to the sink ("remain"),
-                          // hmax = static flags of the row (POA_RF_*), both written by k_poa_rowprep
-};
-static_assert(sizeof(poa_row) == 48 && offsetof(poa_row, pred) == 32, "poa_row layout");
 #define POA_RF_FIRST 1u    // first base of a node (other than the source)
 #define POA_RF_LAST 2u     // last base of a node
 #define POA_RF_SINK 4u     // ... of a node without successors: the row feeds the sink
 #define POA_RF_KEEP 8u     // its value row is read more than POA_RING_SPAN nodes ahead: kept outside the ring
 #define POA_RF_FAR 16u     // a predecessor is not the row directly above
                            // bits 8..10: code of the row's base (A C G T other), bits 16..23: number of predecessors
-
-struct poa_out {          // per problem, 56 B
-    int32_t score;
-    uint32_t row;         // sink predecessor the traceback starts from
-    int32_t status;
-    uint32_t maxw;        // widest row (storage columns)
-    uint64_t cells, vcells;
-    uint32_t nops, pad;
-    uint64_t t_begin, t_end;  // s_memrealtime (100 MHz) when the DP workgroup started / finished: occupancy diagnostics
-};
-
-struct poa_dev_params {
-    int32_t match, mismatch, o1, e1, o2, e2, banded;
-};
 
 // ---------------------------------------------------------------------------------------------------------
 // K4.  * The row that was just filled stays in LDS, indexed by ABSOLUTE query column and overwritten in place
@@ -95,34 +42,6 @@ __device__ __forceinline__ uint64_t poa_uniform_u64(uint64_t v)
 {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-// The traceback pool of k_poa_dp_t5 (vga_poa.hip: poa_ws owns it).  Direction rows -- nine tenths of a problem's footprint, and
-// unknown in size until the rows have been computed, because the band is adaptive -- come out of 1 MiB CHUNKS that a
-// workgroup pops from a device-wide lock-free free list when it needs one and pushes back, all at once, when its traceback
-// is done: what the pool has to hold is what the resident workgroups have written SO FAR, not a worst-case arena for each
-// (rounds 1-2: 2 000 arenas of 128 MB = 257 GB of HBM for problems that use 20-55 MB; allocating and freeing that much
-// dominated a 10 000-read run of the command line tool).  The chunks live in SEGMENTS that the host allocates on a thread
-// of its own while launches already run (a chunk's address: seg_base[chunk >> cps_log2] + ((chunk & mask) << 20), the table
-// in device memory, an entry written before its chunks are listed).  What must be contiguous -- the value-row ring, the two wide-row scratch rows, kept value rows --
-// sits in a small fixed STATE region per resident workgroup, taken like an arena before (flag 0 -> 1).
-// Offsets stored in the row records are absolute device addresses in this mode (pool base 0).
-#define POA_NIL 0xFFFFFFFFu
-#define POA_LISTS 64        // the free list is sharded: workgroups of a launch start together and run in step, so they ask for
-#define POA_LIST_STRIDE 16  // chunks at the same moments -- one list head would serialise 2 000 compare-and-swap loops
-struct poa_chunk_pool {
-    unsigned long long *head;    // [POA_LISTS * POA_LIST_STRIDE] free lists: change counter << 32 | first free chunk (POA_NIL: none)
-    uint32_t *next;              // per chunk: the next chunk of the list it is in (a free list, or its owner's)
-    const uint64_t *seg_base;    // device address of every segment
-    uint32_t cps_log2;           // chunks per segment, log2
-    uint32_t n_slots;            // state regions (0: classic mode, no chunk pool)
-    uint8_t *state_base;         // n_slots regions of state_size bytes
-    uint64_t state_size;
-    uint32_t *slot_flag;         // 0 free / 1 taken
-    unsigned long long *stats;   // [0] requests that found every list empty (the host adds segments when it grows)
-    uint32_t *owner;             // VGA_POOL_CHECK=1 (diagnostics, else null): per chunk, who holds it (0: a free list) -- a chunk popped while
-                                 // held, or pushed by somebody else, counts in stats[4] / stats[5] and fails the call
-    uint32_t *short_flag;        // pinned host memory: set to 1 with stats[0] -- the host's keeper thread reads (and clears) it
-                                 // without any GPU work of its own (a copy of stats[0] waited 0.1-0.2 s for a slot on a full GPU)
-};
 __device__ __forceinline__ uint64_t poa_chunk_addr(const poa_chunk_pool &C, uint32_t idx)
 {
     // (an agent-scope load: the table grows while this kernel runs -- a new segment's entry is written by a copy on another stream
@@ -740,13 +659,6 @@ __device__ __forceinline__ tb_code tb_decode2(uint32_t d, int k)
 // below that column and extends above it); rows with several predecessors also stage the window of their predecessor
 // choice plane and their first four predecessors -- and then all lanes walk in lock step out of LDS until the path
 // leaves the staged rows or a window (30-60 operations on the HLA graphs).  Same outputs as k_poa_traceback.
-#define TB_WIN 32
-struct tb_lds {  // 6 912 B: what one wave stages per stretch
-    int beg[64], end[64], ws[64];
-    uint64_t doff[64];
-    uint32_t pred[64], np[64];
-    uint32_t dir[64][TB_WIN / 4], pl1[64][TB_WIN / 4], pr4[64][4];
-};
 // LDS traffic of one wave is processed in program order: between the staging stores and the walk's loads (other
 // lanes' data) the wave only has to wait for its own stores to be issued -- no s_barrier, so the function can run in
 // one wave of a larger workgroup whose other waves have finished
@@ -909,12 +821,3 @@ static inline size_t poa_pk_lds_bytes(uint32_t hg_cols, uint32_t lds_cols, int n
     // (the fused traceback reuses the row-state area: at least sizeof(tb_lds) behind the header)
     return std::max<size_t>((h16 ? 3ull : 4ull) * hg_cols + ((lds_cols / 2 + 15u) & ~15u), sizeof(tb_lds)) + (size_t)(3 * nw + 1 + 4 + 6 + 1) * 16 + 16;
 }
-
-static inline uint32_t poa_lds_cols(uint32_t max_q) { return ((max_q + 1 + 15u) & ~15u) + 16u; }
-
-static inline size_t poa_lds_bytes(uint32_t lds_cols, int nt)
-{
-    const int nw = nt / 64;
-    return 7ull * lds_cols + (size_t)(8 * nw + 3 * nw + 2) * 4 + 16;
-}
-

@@ -77,12 +77,6 @@ __device__ __forceinline__ int t4_shr1_mov(int v, int first)  // lanes 1..63: v 
     return r;
 }
 
-static inline size_t poa_t4_lds_bytes(uint32_t hg_cols, uint32_t lds_cols, int nt)
-{
-    const int nw = nt / 64;
-    return std::max<size_t>(6ull * hg_cols + ((lds_cols / 2 + 15u) & ~15u), sizeof(tb_lds)) + (size_t)(3 * nw + 1 + 4 + 6 + 1) * 16 + 16;
-}
-
 template <int NT, bool DEF>
 __global__ __launch_bounds__(NT, 4) void k_poa_dp_t4(
     const poa_prob *__restrict__ probs, const char *__restrict__ queries, const uint4 *__restrict__ node_tab,

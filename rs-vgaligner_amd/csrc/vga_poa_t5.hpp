@@ -33,32 +33,6 @@ __device__ __forceinline__ uint64_t t5_uniform64(uint64_t v)
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
 
-static inline size_t poa_t5_lds_bytes(uint32_t hg_cols, uint32_t lds_cols, int nt)
-{
-    const int nw = nt / 64;
-    return std::max<size_t>(6ull * hg_cols + ((lds_cols / 2 + 15u) & ~15u), sizeof(tb_lds)) + (size_t)(3 * nw + 1 + 1 + 2) * 16 + 16;
-}
-
-// The launch arguments as one by-value struct: the row loop copies the few it needs into scalars of their own, and the
-// epilogue reads the rest again through the kernarg pointer, so that nothing of it has to stay in registers over the rows.
-struct poa_t5_args {
-    const poa_prob *probs;
-    const char *queries;
-    const uint4 *node_tab;
-    const uint32_t *seq32, *preds;
-    poa_row *rows;
-    uint8_t *pool;
-    unsigned long long *pool_next;
-    uint64_t pool_size;
-    poa_out *outs;
-    uint8_t *tb_ops;
-    uint32_t *tb_orow;
-    poa_chunk_pool cp;  // cp.n_slots != 0: direction rows out of the chunk pool, the rest out of a state region
-    uint32_t lds_cols, hg_cols, win_mask;
-    poa_dev_params P;
-    uint32_t prio;  // != 0: the waves of this launch run at raised issue priority (the launch of a call's longest problems: their
-                    // sequential rows decide how long the call takes, so they should not share issue slots evenly with the bulk)
-};
 // a scalar of its own: cuts a uniform value loose from the (wide) load that produced it
 __device__ __forceinline__ int t5_own(int v)
 {

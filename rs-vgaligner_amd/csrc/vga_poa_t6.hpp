@@ -20,12 +20,6 @@
 // a query with characters other than A / C / G / T, anything outside chunk-pool mode.
 #pragma once
 
-template <int CPL>
-static inline size_t poa_t6_lds_bytes(uint32_t lds_cols)
-{
-    return std::max<size_t>(((size_t)lds_cols / 2 + 15u) & ~(size_t)15u, sizeof(tb_lds)) + 64;
-}
-
 // lanes 0..62: v of the lane above; lane 63: fill   (wave_shl:1, bound_ctrl off: the last lane keeps the old value)
 __device__ __forceinline__ int t6_shl1(int v, int fill)
 {

@@ -14,17 +14,6 @@
 // (vga_poa_batch) and as the fallback when the arena is full.
 #pragma once
 
-struct poa_text_out {  // per problem, 48 B
-    uint32_t cs_off, cs_len;      // bytes in the arena ("cs:Z:" included)
-    uint32_t cg_off, cg_len;
-    uint32_t runs_off, n_runs;    // byte offset (4-aligned) of n_runs node indices
-    uint32_t n_path;              // graph-consuming alignment columns (abpoa_nodes.len())
-    uint32_t start_off, end_off;  // aln_start_offset / aln_end_offset (align.rs:1155-1156)
-    uint32_t aligned;             // n_aligned_bases
-    uint32_t flags;               // 1: written; 2: no room in the arena (the host falls back to the operations)
-    uint32_t pad;
-};
-
 __device__ __forceinline__ int ptx_ndigits(uint32_t v)
 {
     return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;

@@ -465,6 +465,17 @@ def test_poa_large_gap_penalties_use_the_unpacked_kernel(oracle, ctx):
     for p_ in (pp, op):
         p_.gap_open1, p_.gap_ext1, p_.gap_open2, p_.gap_ext2 = 6, 3, 200, 1
     _check_poa(oracle, ctx, [_rand_problem(rng, 25, 10) for _ in range(25)] + [_rand_problem(rng, 60, 60) for _ in range(3)], pp, op)
+    # open + extend of the first piece == 64: the last sum k_poa_dp_t4's gap bytes hold and one more than k_poa_dp_t5's -- the whole
+    # call is k_poa_dp_t4's, classic pool included (the chunk pool is k_poa_dp_t5's)
+    for p_ in (pp, op):
+        p_.gap_open1, p_.gap_ext1, p_.gap_open2, p_.gap_ext2 = 31, 33, 24, 1
+    _check_poa(oracle, ctx, [_rand_problem(rng, 25, 10) for _ in range(25)] + [_rand_problem(rng, 60, 60) for _ in range(3)], pp, op)
+    # sums that need more than 8 bits together but each fit k_poa_dp_t5: the query limit is that kernel's (~280 kbp), not the ~22 kbp
+    # of k_poa_dp_lds
+    for p_ in (pp, op):
+        p_.gap_open1, p_.gap_ext1, p_.gap_open2, p_.gap_ext2 = 10, 6, 24, 1
+    long_q = "".join(rng.choice("ACGT") for _ in range(30000))
+    _check_poa(oracle, ctx, [(["ACGT", "TTGA"], [(0, 1)], long_q), _rand_problem(rng, 25, 10)], pp, op)
 
 
 def test_unsupported_inputs_fail_loudly(oracle, ctx, drb1):
@@ -482,6 +493,14 @@ def test_unsupported_inputs_fail_loudly(oracle, ctx, drb1):
     with pytest.raises(p.VgaError) as e:
         ctx.poa_batch([(["ACGT"], [], "A" * 400000)])
     assert e.value.code == -4
+    # penalties only k_poa_dp_lds takes (no extension penalty; a second piece beyond k_poa_dp_t4's gap bytes): it keeps every
+    # column in LDS, so its ~22 kbp limit holds whatever the bit count of the sums
+    for gaps in ((4, 0, 24, 1), (0, 1, 60, 4)):
+        pp = p.default_poa_params()
+        pp.gap_open1, pp.gap_ext1, pp.gap_open2, pp.gap_ext2 = gaps
+        with pytest.raises(p.VgaError) as e:
+            ctx.poa_batch([(["ACGT"], [], "A" * 30000)], pp)
+        assert e.value.code == -4, gaps
 
 
 @_long_ok
