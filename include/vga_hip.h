@@ -295,6 +295,34 @@ void vga_align_result_free(vga_align_result *r);
  * host, src/align.rs:1032-1040). */
 int vga_align_prepare(vga_ctx *ctx, uint64_t n_reads, uint32_t max_read_len);
 
+/* ---- coverage: how many reported alignments cover every base, node and edge of the graph ----------
+ * Stands in for nothing in the reference, whose map.rs ends at the GAF writer: it is what a reader of the alignments GAF
+ * (vg pack, gafpack and their like) computes from the text, counted here while the alignments are still on the GPU.
+ * Coverage is defined on the record vga_align_batch reports for a read (the winner of best_alignment_for_query); a read
+ * with a placeholder record adds nothing.  Along the record's path, from path_start inside its first node:
+ *   an M operation (cs ":N" per base, "*gq")  adds one to base_depth of its graph base;
+ *   a D operation (cs "-g..") skips its graph bases, an I operation (cs "+q..") touches none.
+ *   base_depth[p], p in [0, seq_length): position node_seq_idx[id - 1] + offset of seq_fwd;
+ *   node_reads[id - 1]: reported alignments whose path holds node id (a node crossed only by a deletion counts);
+ *   edge_reads[e], e in [0, n_edges), laid out as vga_index_desc.edges: for each consecutive pair (a, b) of a path one is
+ *     added at the slot of b in the OUTGOING part of a's slice (node_edge_idx[a-1] + node_edges_to[a-1] ...); incoming slots stay 0;
+ *   n_alignments: aligned records counted.
+ * The counters are 32-bit, exact and independent of the order of the additions; they belong to the context's index: uploading
+ * or building another index drops them and turns counting off.
+ *   vga_coverage_begin  needs an index (VGA_ERR_NO_INDEX); allocates and zeroes; every later vga_align_batch on ctx adds its
+ *                       reported alignments.  VGA_SUBGRAPH=host is refused by vga_align_batch while counting is on.
+ *   vga_coverage_read   any pointer may be NULL; does not reset.  VGA_ERR_ARG without _begin; VGA_ERR_UNSUPPORTED once
+ *                       n_alignments has reached 2^32 - 1 (a counter may have wrapped).
+ *   vga_coverage_reset  zero, keep counting (VGA_ERR_ARG without _begin).
+ *   vga_coverage_end    free, stop counting.
+ * With counting off vga_align_batch does what it did before these calls existed: no extra launch, no extra allocation.
+ * vga_poa_batch has no graph coordinates and never counts. */
+int vga_coverage_begin(vga_ctx *ctx);
+int vga_coverage_read(vga_ctx *ctx, uint32_t *base_depth /* seq_length */, uint32_t *node_reads /* n_nodes */,
+                      uint32_t *edge_reads /* n_edges */, uint64_t *n_alignments);
+int vga_coverage_reset(vga_ctx *ctx);
+int vga_coverage_end(vga_ctx *ctx);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

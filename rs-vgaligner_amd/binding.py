@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "vga_align_result_free", "vga_last_kernel_times", "vga_chain_paths_text", "vga_chain_text_free",
     "vga_align_prepare", "vga_ctx_set_pool_fraction", "vga_ctx_set_host_threads",
     "vga_index_build_kmers", "vga_index_kmers_free",
+    "vga_coverage_begin", "vga_coverage_read", "vga_coverage_reset", "vga_coverage_end",
 ]
 
 
@@ -158,6 +159,12 @@ def load_library():
     L.vga_index_build_kmers.restype = C.c_int
     L.vga_index_kmers_free.argtypes = [_P(IndexDesc)]
     L.vga_index_kmers_free.restype = None
+    if hasattr(L, "vga_coverage_begin"):  # (absent from an older build named by VGA_LIB; the Context.coverage_* calls then fail)
+        for name in ("vga_coverage_begin", "vga_coverage_reset", "vga_coverage_end"):
+            getattr(L, name).argtypes = [vp]
+            getattr(L, name).restype = C.c_int
+        L.vga_coverage_read.argtypes = [vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64)]
+        L.vga_coverage_read.restype = C.c_int
     _lib = L
     return L
 
@@ -435,6 +442,7 @@ class Context:
             raise VgaError(rc, f"vga_ctx_create(device={device}) failed: no usable MI355X; this library has no CPU path")
         self.h = h
         self._keep = None
+        self._dims = None  # (seq_length, n_nodes, n_edges) of the index this context holds
 
     def _check(self, rc: int):
         if rc != VGA_OK:
@@ -467,12 +475,16 @@ class Context:
         d.kmer_starts = _u64p(a[4])
         d.n_kmer_pos = len(tab)
         d.kmer_pos_table = tab.ctypes.data_as(_P(KmerPos))
+        self._dims = None
         self._check(self.L.vga_index_upload(self.h, C.byref(d)))
+        self._dims = (int(d.seq_length), int(d.n_nodes), int(d.n_edges))
 
     def index_build_kmers(self, desc: IndexDesc, max_furcations: int = 100, max_degree: int = 100) -> None:
         """vga_index_build_kmers: fills the k-mer half of `desc` (release it with index_kmers_free) and leaves this
         context holding the index"""
+        self._dims = None
         self._check(self.L.vga_index_build_kmers(self.h, C.byref(desc), int(max_furcations), int(max_degree)))
+        self._dims = (int(desc.seq_length), int(desc.n_nodes), int(desc.n_edges))
 
     def batch(self, seqs: Sequence[str]) -> Batch:
         return Batch(self, seqs)
@@ -516,6 +528,26 @@ class Context:
     def align_prepare(self, n_reads: int, max_read_len: int) -> None:
         """vga_align_prepare: start allocating what the first align_batch of this context will need (returns at once)"""
         self._check(self.L.vga_align_prepare(self.h, int(n_reads), int(max_read_len)))
+
+    def coverage_begin(self) -> None:
+        """vga_coverage_begin: from now on every align() of this context adds its reported alignments to the coverage tables"""
+        self._check(self.L.vga_coverage_begin(self.h))
+
+    def coverage(self):
+        """vga_coverage_read -> (base_depth[seq_length], node_reads[n_nodes], edge_reads[n_edges], n_alignments); does not reset"""
+        sl, nn, ne = self._dims if self._dims else (0, 0, 0)
+        base, node, edge = (np.zeros(max(1, x), dtype=np.uint32) for x in (sl, nn, ne))
+        n = C.c_uint64(0)
+        self._check(self.L.vga_coverage_read(self.h, _u32p(base), _u32p(node), _u32p(edge), C.byref(n)))
+        return base[:sl], node[:nn], edge[:ne], int(n.value)
+
+    def coverage_reset(self) -> None:
+        """vga_coverage_reset: zero the tables, keep counting"""
+        self._check(self.L.vga_coverage_reset(self.h))
+
+    def coverage_end(self) -> None:
+        """vga_coverage_end: free the tables, stop counting"""
+        self._check(self.L.vga_coverage_end(self.h))
 
     def chain_paths_text(self, chains: "MapOut") -> List[bytes]:
         """the path column of every chain's GAF record (vga_chain_paths_text), one bytes object per chain"""

@@ -12,6 +12,7 @@
 // the GPU tests use as a second opinion.  The ./subgraphs/*.gfa export side effect of align.rs:104-111 is a debugging
 // aid and is not reproduced.
 #include "vga_common.hpp"
+#include "vga_coverage.hpp"
 #include "vga_poa_internal.hpp"
 
 #include <algorithm>
@@ -300,6 +301,10 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     // order is fixed up front from the span of each chain on the linearised graph.
     const char *sg_env = getenv("VGA_SUBGRAPH");
     const bool on_device = !(sg_env && strstr(sg_env, "host"));
+    cov_state *const cov = cov_active(ctx);
+    if (cov && !on_device)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                             "vga_align_batch: read coverage is not counted under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
     std::vector<subgraph_t> SG(on_device ? 0 : n);
     poa_feed feed;
     feed.views.resize(n);
@@ -506,6 +511,15 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
             path_n[r] = c;
         }
     });
+    if (cov) {
+        // coverage counts the reported record of every read and nothing else
+        std::vector<uint32_t> winners;
+        for (uint64_t r = 0; r < R; r++)
+            if (pick[r] >= 0) winners.push_back((uint32_t)pick[r]);
+        const int rc = cov_add_winners(ctx, cov, winners);
+        if (rc != VGA_OK) { vga_align_result_free(res); return rc; }
+        tr.mark("coverage");
+    }
     uint64_t tp = 0, tc = 0, ts = 0;
     for (uint64_t r = 0; r < R; r++) {
         res->path_off[r] = tp; res->cigar_off[r] = tc; res->cs_off[r] = ts;

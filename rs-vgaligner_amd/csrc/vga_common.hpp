@@ -56,6 +56,9 @@ struct vga_dev_index {
     std::vector<uint32_t> edges_to;    // n_nodes+1
     std::vector<uint32_t> edges;       // packed handles
     bool loaded = false;
+    // read coverage counters of this index while counting is on (vga_coverage.hip): released with the index
+    void *cov = nullptr;
+    void (*cov_free)(void *) = nullptr;
 };
 
 struct vga_timer_entry {

@@ -3,6 +3,7 @@
 // (vga_align_prepare, vga_poa_batch).  No kernel is visible here: launches go through vga_poa_launch.hpp, the launch shape comes
 // from vga_poa_shape.hpp, the traceback pool is vga_poa_pool.hip.  The engine itself is described at the top of vga_poa.hip.
 #include "vga_common.hpp"
+#include "vga_coverage.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_poa_pool.hpp"
 
@@ -268,6 +269,7 @@ struct poa_call {
     vga_trace tr{"poa"};
     poa_ws &W;
     poa_pool pool;
+    cov_state *const cov;  // read coverage is being counted (vga_coverage_begin) and the graphs are in the device store: k_cov_runs beside k_poa_text
     uint32_t max_q = 0;
     // ---- plan: node tables, estimates, launch order
     std::vector<poa_prep> G;
@@ -307,7 +309,7 @@ struct poa_call {
 
     poa_call(vga_ctx *c, poa_feed &f, const vga_poa_params *p, std::vector<poa_item> &o, poa_timing &t)
         : ctx(c), feed(f), params(p), out(o), tm(t), n(f.views.size()), views(f.views), sw(poa_read_switches()),
-          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n) {}
+          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_active(c) : nullptr) {}
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
     void chk(hipError_t e) { if (e != hipSuccess && launch_err == hipSuccess) launch_err = e; }
@@ -334,6 +336,7 @@ struct poa_call {
     void stage(const launch_t &L);
     void launch_dp(launch_t &L);
     void enqueue_results(const launch_t &L);
+    void collect_coverage(const sub_t &cur, const poa_slot::out_set &S);
     void fill();
     // fetch its text, requeue, post-process, account
     void collect();
@@ -743,6 +746,8 @@ void poa_call::enqueue_results(const launch_t &L)
         // 17 KB per problem, instead of a handle lookup per aligned base)
         if (feed.dev) chk(hipMemcpyAsync(O.h_seq.p, S.d_seq32.p, L.tot_seq, hipMemcpyDeviceToHost, st));
     }
+    // coverage: the run list of every problem, while its operations are in the slot (the refill recycles them)
+    if (cov && launch_err == hipSuccess) chk(cov_enqueue_runs(ctx, cov, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
 }
 
 // stage, upload and enqueue DP + traceback + result copies of a sub-batch that starts at launch position i0 and ends
@@ -825,6 +830,9 @@ bool poa_call::fetch_text(const sub_t &cur, poa_slot::out_set &S)
     const uint64_t used = std::min<uint64_t>(S.h_tcur.p[0], SL.d_text.cap);
     bool overflow = false;
     for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || S.h_touts.p[i - cur.i0].flags == 2u;
+    // (coverage: a problem whose run list found no room is served from the operations too)
+    if (cov)
+        for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || cov_launch_recs(cov, cur.slot, cur.oset)[i - cur.i0].flags == 2u;
     hipError_t ce = hipSuccess;
     if (feed.keep_text) {
         // a buffer of the context's that holds the text: the smallest free one that fits, else the largest free one grows
@@ -907,6 +915,23 @@ void poa_call::requeue_handed_back(const sub_t &cur, const poa_slot::out_set &S)
     }
 }
 
+// coverage: the run-list records of a finished sub-batch join the call's; a list that found no room in the buffer is built here,
+// from the operations fetch_text brought back
+void poa_call::collect_coverage(const sub_t &cur, const poa_slot::out_set &S)
+{
+    const cov_rec *recs = cov_launch_recs(cov, cur.slot, cur.oset);
+    for (uint64_t i = cur.i0; i < cur.i1; i++) {
+        const uint32_t p = order[i];
+        const poa_out &ho = S.h_outs.p[i - cur.i0];
+        if (ho.status != POA_ST_OK) continue;
+        const cov_rec &r = recs[i - cur.i0];
+        if (r.flags != 2u) { cov_keep(cov, p, r); continue; }
+        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its run list, built from the operations\n", p);
+        cov_keep_from_ops(cov, p, S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1,
+                          feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start);
+    }
+}
+
 // CIGAR / cs strings / node paths of a finished sub-batch on the host threads, and its share of the call's totals
 void poa_call::post_process(const sub_t &cur, const poa_slot::out_set &S)
 {
@@ -952,6 +977,7 @@ void poa_call::collect()
         poa_slot::out_set &S = W.slot[cur.slot].outs[cur.oset];
         if (launch_err != hipSuccess) break;
         if (!fetch_text(cur, S)) break;
+        if (cov) collect_coverage(cur, S);
         bool pool_fail = false;
         for (uint64_t i = cur.i0; i < cur.i1; i++)
             if (S.h_outs.p[i - cur.i0].status == POA_ST_POOL) {
@@ -1094,6 +1120,11 @@ int poa_run(vga_ctx *ctx, poa_feed &feed, const vga_poa_params *params, std::vec
     poa_call c(ctx, feed, params, out, tm);
     int rc = c.validate();
     if (rc != VGA_OK || c.n == 0) return rc;
+    if (c.cov) {
+        uint64_t total_q = 0;
+        for (const poa_view &v : c.views) total_q += v.qlen;
+        if ((rc = cov_call_begin(ctx, c.cov, c.n, total_q)) != VGA_OK) return rc;
+    }
     if ((rc = c.order_problems()) != VGA_OK) return rc;
     if ((rc = c.size_pool()) != VGA_OK) return rc;
     if ((rc = c.obtain_pool()) != VGA_OK) return rc;

@@ -517,6 +517,7 @@ int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uin
     }
     SG_CHECK(hipStreamSynchronize(st));
     P.d_ntab = B.d_ntab.p; P.d_preds = B.d_preds.p; P.d_sinks = B.d_sinks.p; P.d_seq = B.d_seq.p;
+    P.d_handles = B.d_handles.p;
     P.h_handles = B.h_handles.p; P.h_first_row = B.h_first_row.p;
     P.ready = true;
     return VGA_OK;

@@ -44,6 +44,7 @@ struct sg_part {
     const uint4 *d_ntab = nullptr;
     const uint32_t *d_preds = nullptr, *d_sinks = nullptr;
     const char *d_seq = nullptr;
+    const uint32_t *d_handles = nullptr;  // packed handle of every node, indexed from off[p].node0 (k_cov_runs)
     const uint32_t *h_handles = nullptr, *h_first_row = nullptr;  // host copies (pinned), indexed from off[p].node0
     bool ready = false;
 };

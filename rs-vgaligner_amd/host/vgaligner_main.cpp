@@ -37,7 +37,10 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"-d", "--device", true, "device"}, {"", "--devices", true, "devices"}, {"", "--chunk-reads", true, "chunk-reads"},
                           {"", "--poa-remain", true, "poa-remain"},
                           // not in the reference: map each read and its reverse complement, keep the orientation that chains better
-                          {"", "--both-strands", false, "both-strands"}};
+                          {"", "--both-strands", false, "both-strands"},
+                          // not in the reference: read coverage of bases, nodes and edges, counted on the GPU (three TSV files);
+                          // --coverage-only leaves the alignments GAF unwritten
+                          {"", "--coverage", false, "coverage"}, {"", "--coverage-only", false, "coverage-only"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -125,6 +128,9 @@ int map_main(int argc, char **argv)
         else throw Error("--poa-remain takes longest or first-edge");
     }
     o.both_strands = m.count("both-strands") > 0;
+    o.coverage_only = m.count("coverage-only") > 0;
+    o.coverage = o.coverage_only || m.count("coverage") > 0;
+    if (o.coverage && !o.also_align) throw Error(std::string(o.coverage_only ? "--coverage-only" : "--coverage") + " counts alignments: it needs --also-align");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -161,6 +167,7 @@ int map_main(int argc, char **argv)
     if (o.both_strands)
         fprintf(stderr, "[vgaligner] %llu of %llu reads on the reverse strand\n", (unsigned long long)out.n_reverse, (unsigned long long)out.n_reads);
     if (o.also_align) fprintf(stderr, "[vgaligner] Alignment took: %.0f ms; Found %llu alignments!\n", out.ms_align, (unsigned long long)out.n_reads);
+    if (o.coverage) fprintf(stderr, "[vgaligner] Coverage: %llu alignments counted\n", (unsigned long long)out.n_coverage);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -201,7 +208,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
-                        "                [--both-strands]\n");
+                        "                [--both-strands] [--coverage | --coverage-only]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -144,6 +144,12 @@ struct MapOptions {
     // --both-strands (not in the reference): map each read and its reverse complement and keep the orientation that chains better
     // (vga_map_params.strands = VGA_STRANDS_BOTH)
     bool both_strands = false;
+    // --coverage (not in the reference): count, on the GPU, how many reported alignments cover every base, node and edge of the
+    // graph (vga_coverage_begin / vga_coverage_read) and write <out>-coverage-nodes.tsv, -bases.tsv and -edges.tsv next to the GAF
+    // files.  Needs also_align.  Every context counts its own reads; the arrays are added in 64 bits at the end.
+    bool coverage = false;
+    // --coverage-only: coverage, and the alignments GAF text is neither built nor written (the chains GAF still is)
+    bool coverage_only = false;
 };
 
 // VGA_TRACE=1: wall-clock marks of the driver's phases on stderr (since the first call)
@@ -155,6 +161,7 @@ struct MapOutput {
     uint64_t n_reverse = 0;              // reads mapped on their reverse complement (both_strands)
     double ms_map = 0, ms_align = 0;     // summed over chunks (per device: the maximum over devices)
     uint64_t n_chunks = 0, n_devices = 0;
+    uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
 };
 
 // One [begin, end) range of the read list, the device slot (index into MapOptions::devices) that maps it.

@@ -560,11 +560,12 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
         wait_k6();
         b_owner.reset();
         if (hooks.gpu_done) hooks.gpu_done();
-        out.aligns = text_of_reads(n, T, [&](uint64_t r, std::string &dst) { gaf_from_alignment(dst, inputs[b0 + r], a, r, m->strand && m->strand[r]); },
-                                   [&](uint64_t r) {
-                                       return (size_t)(a->cs_off[r + 1] - a->cs_off[r]) + (size_t)(a->cigar_off[r + 1] - a->cigar_off[r]) +
-                                              (size_t)(a->path_off[r + 1] - a->path_off[r]) * 8 + inputs[b0 + r].name.size() + 160;
-                                   });
+        if (!opt.coverage_only)  // (--coverage-only: the tables are what the caller wants of the alignments)
+            out.aligns = text_of_reads(n, T, [&](uint64_t r, std::string &dst) { gaf_from_alignment(dst, inputs[b0 + r], a, r, m->strand && m->strand[r]); },
+                                       [&](uint64_t r) {
+                                           return (size_t)(a->cs_off[r + 1] - a->cs_off[r]) + (size_t)(a->cigar_off[r + 1] - a->cigar_off[r]) +
+                                                  (size_t)(a->path_off[r + 1] - a->path_off[r]) * 8 + inputs[b0 + r].name.size() + 160;
+                                       });
         for (uint64_t r = 0; r < n; r++) out.n_aligned += a->aligned[r];
         mark("alignments GAF text");
     } else {
@@ -659,8 +660,62 @@ TextReplay textpath_replay(vga_ctx *ctx, const Index &ix, const std::vector<Quer
 
 namespace {
 
+// ---- coverage (MapOptions::coverage): the tables of the contexts, added in 64 bits, and the three TSV files
+struct CoverageSum {
+    std::vector<uint64_t> base, node, edge;
+    uint64_t n = 0;
+    void add(const CoverageSum &o)
+    {
+        if (base.size() < o.base.size()) base.resize(o.base.size(), 0);
+        if (node.size() < o.node.size()) node.resize(o.node.size(), 0);
+        if (edge.size() < o.edge.size()) edge.resize(o.edge.size(), 0);
+        for (size_t i = 0; i < o.base.size(); i++) base[i] += o.base[i];
+        for (size_t i = 0; i < o.node.size(); i++) node[i] += o.node[i];
+        for (size_t i = 0; i < o.edge.size(); i++) edge[i] += o.edge[i];
+        n += o.n;
+    }
+};
+
+// what the context has counted so far joins `s`
+void coverage_take(vga_ctx *ctx, const Index &ix, CoverageSum &s)
+{
+    std::vector<uint32_t> b(ix.seq_length + 1), nd(ix.n_nodes + 1), ed(ix.n_edges + 1);
+    uint64_t n = 0;
+    if (vga_coverage_read(ctx, b.data(), nd.data(), ed.data(), &n) != VGA_OK) throw Error(vga_last_error(ctx));
+    CoverageSum c;
+    c.base.assign(b.begin(), b.begin() + (long)ix.seq_length);
+    c.node.assign(nd.begin(), nd.begin() + (long)ix.n_nodes);
+    c.edge.assign(ed.begin(), ed.begin() + (long)ix.n_edges);
+    c.n = n;
+    s.add(c);
+}
+
+void coverage_write(const Index &ix, CoverageSum s, const std::string &out_prefix)
+{
+    if (out_prefix.empty()) return;
+    s.add(CoverageSum{std::vector<uint64_t>(ix.seq_length, 0), std::vector<uint64_t>(ix.n_nodes, 0), std::vector<uint64_t>(ix.n_edges, 0), 0});
+    std::string nodes = "node\tlength\treads\tbases\n", bases = "node\toffset\tdepth\n", edges = "from\tto\treads\n";
+    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
+        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
+        uint64_t sum = 0;
+        for (uint64_t p = p0; p < p1; p++) {
+            sum += s.base[p];
+            put_u64(bases, id); bases += '\t'; put_u64(bases, p - p0); bases += '\t'; put_u64(bases, s.base[p]); bases += '\n';
+        }
+        put_u64(nodes, id); nodes += '\t'; put_u64(nodes, p1 - p0); nodes += '\t'; put_u64(nodes, s.node[id - 1]); nodes += '\t';
+        put_u64(nodes, sum); nodes += '\n';
+        for (uint64_t e = ix.node_ref[id - 1].edge_idx + ix.node_ref[id - 1].edges_to_node; e < ix.node_ref[id].edge_idx; e++) {
+            put_u64(edges, id); edges += '\t'; put_u64(edges, id_of(ix.edges[e])); edges += '\t'; put_u64(edges, s.edge[e]); edges += '\n';
+        }
+    }
+    write_file(out_prefix + "-coverage-nodes.tsv", nodes);
+    write_file(out_prefix + "-coverage-bases.tsv", bases);
+    write_file(out_prefix + "-coverage-edges.tsv", edges);
+}
+
 void check_aligner(const MapOptions &opt)
 {
+    if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
         throw Error("POA Aligner not recognized");  // map_main.rs:67
@@ -672,7 +727,7 @@ void finish(MapOutput &out, const Index &ix, const std::vector<QuerySequence> &i
 {
     const bool same_file = out_prefix.size() >= 4 && out_prefix.compare(out_prefix.size() - 4, 4, ".gaf") == 0;
     if (!out_prefix.empty()) write_file(same_file ? out_prefix : out_prefix + "-chains.gaf", out.chains_gaf);
-    if (!opt.also_align) return;
+    if (!opt.also_align || opt.coverage_only) return;
     // map.rs:174-178: a prefix ending in .gaf makes the alignments overwrite the chains file
     if (!out_prefix.empty()) write_file(same_file ? out_prefix : out_prefix + "-alignments.gaf", out.alignments_gaf);
     if (opt.also_validate) {  // map.rs:186-208
@@ -692,9 +747,11 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
                     const std::string &out_prefix)
 {
     check_aligner(opt);
+    const bool coverage = opt.coverage || opt.coverage_only;
     MapOutput out;
     out.n_reads = inputs.size();
     out.n_devices = 1;
+    if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
     for (const Shard &s : plan_shards(len, 1, opt.chunk_reads)) {
@@ -705,6 +762,13 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells; out.n_reverse += c.n_reverse;
         out.ms_map += c.ms_map; out.ms_align += c.ms_align;
         out.n_chunks++;
+    }
+    if (coverage) {
+        CoverageSum s;
+        coverage_take(ctx, ix, s);
+        (void)vga_coverage_end(ctx);
+        out.n_coverage = s.n;
+        coverage_write(ix, s, out_prefix);
     }
     finish(out, ix, inputs, opt, out_prefix);
     return out;
@@ -793,6 +857,11 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (vga_ctx *c : ctxs)
             if (vga_index_upload(c, &d) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
     }
+    const bool coverage = opt.coverage || opt.coverage_only;
+    if (coverage)
+        for (vga_ctx *c : ctxs)
+            if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
+    std::vector<CoverageSum> slot_cov(n_slots);
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -845,7 +914,7 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     };
     if (stream) {
         start_writer(0);
-        if (opt.also_align) start_writer(1);
+        if (opt.also_align && !opt.coverage_only) start_writer(1);
     }
     // the last chunk of a slot: once its GPU work is done nothing needs the context any more.  A caller that is about to leave
     // the process (leave_contexts) has it torn down right then, beside the text and file work that is left -- the driver
@@ -863,8 +932,11 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
                         { std::lock_guard<std::mutex> lk(mu); if (abort_workers) break; }
                         ChunkHooks hooks;
                         if (stream) hooks.chains_ready = [&, i]() { { std::lock_guard<std::mutex> lk(mu); chains_done[i] = 1; } cv.notify_all(); };
+                        if (coverage && i == last_of_slot[slot] && !opt.leave_contexts)
+                            hooks.gpu_done = [&, slot]() { coverage_take(ctxs[slot], ix, slot_cov[slot]); };
                         if (opt.leave_contexts && i == last_of_slot[slot])
                             hooks.gpu_done = [&, slot]() {
+                                if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);  // (the slot's last chunk has been counted)
                                 vga_ctx *c = ctxs[slot];
                                 ctxs[slot] = nullptr;
                                 std::lock_guard<std::mutex> lk(destroyers_mu);
@@ -919,6 +991,13 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         ms_map[plan[i].slot] += parts[i].ms_map; ms_align[plan[i].slot] += parts[i].ms_align;
     }
     for (uint32_t s = 0; s < n_slots; s++) { out.ms_map = std::max(out.ms_map, ms_map[s]); out.ms_align = std::max(out.ms_align, ms_align[s]); }
+    if (coverage) {
+        CoverageSum sum;
+        for (const CoverageSum &c : slot_cov) sum.add(c);
+        out.n_coverage = sum.n;
+        coverage_write(ix, sum, out_prefix);
+        trace_mark("coverage tables written");
+    }
     if (stream) return out;
     finish(out, ix, inputs, opt, out_prefix);
     return out;

@@ -85,6 +85,9 @@ class HostIndex:
             h = L.vgh_index_build_from_gfa(gfa.encode(), k, max_furcations, max_degree)
         if not h:
             raise HostError(L.vgh_last_error().decode())
+        if ctx is not None:
+            d = L.vgh_index_desc(h).contents
+            ctx._dims = (int(d.seq_length), int(d.n_nodes), int(d.n_edges))
         return cls(h)
 
     @classmethod
@@ -115,7 +118,10 @@ class HostIndex:
                     kmer_pos_table=tab)
 
     def upload(self, ctx: binding.Context):
+        ctx._dims = None
         ctx._check(self.L.vgh_index_upload(self.h, ctx.h))
+        d = self.desc()
+        ctx._dims = (int(d.seq_length), int(d.n_nodes), int(d.n_edges))  # (Context.coverage sizes its arrays by them)
 
     def map_reads(self, ctx: binding.Context, names: Sequence[str], seqs: Sequence[str], max_gap: int = 1000,
                   chain_min_n_anchors: int = 3, also_align: bool = True, align_best_n: int = 1,
