@@ -147,6 +147,42 @@ int vga_index_load_graph(vga_ctx *ctx, const vga_index_desc *d);
             return vga_set_error((ctx), VGA_ERR_HIP, "%s failed: %s (%s:%d)", #call,           \
                                  hipGetErrorString(e_), __FILE__, __LINE__);                   \
     } while (0)
+// ... for the entry points that report a failed device or pinned allocation as VGA_ERR_NOMEM (sg_prepare, vga_chain_paths_text)
+#define VGA_HIP_CHECK_OOM(ctx, call)                                                         \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return vga_set_error((ctx), e_ == hipErrorOutOfMemory ? VGA_ERR_NOMEM : VGA_ERR_HIP, \
+                                 "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// an array of a result the caller frees with free(); never a null pointer for n == 0
+template <typename T>
+T *xmalloc(size_t n)
+{
+    return (T *)malloc((n ? n : 1) * sizeof(T));
+}
+
+// A result under construction.  Any return before release() frees it -- after the streams named in `wait` have drained, where
+// copies into the result's pageable arrays may still be in flight (an entry is a pointer to the stream handle, so that a stream
+// created later in the call counts from then on; a null handle is skipped).
+template <typename T, void (*FREE)(T *)>
+struct vga_result_guard {
+    T *p = nullptr;
+    const hipStream_t *wait[2] = {nullptr, nullptr};
+    vga_result_guard() = default;
+    vga_result_guard(const vga_result_guard &) = delete;
+    vga_result_guard &operator=(const vga_result_guard &) = delete;
+    ~vga_result_guard()
+    {
+        if (!p) return;
+        for (const hipStream_t *s : wait)
+            if (s && *s) (void)hipStreamSynchronize(*s);
+        FREE(p);
+    }
+    T *operator->() const { return p; }
+    T *release() { T *q = p; p = nullptr; return q; }
+};
 
 // hipFree and hipHostFree wait for every kernel that runs on the device.  A buffer that has to grow while launches are in flight
 // (a sub-batch's staging beside a DP launch that runs for a second) would stall the launch path for as long: it hands its old

@@ -149,69 +149,62 @@ static int vga_chain_paths_text_impl(vga_ctx *ctx, const vga_map_result *m, vga_
     *out = nullptr;
     if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_chain_paths_text: no index uploaded");
     (void)hipSetDevice(ctx->device);
-    hipStream_t st = nullptr;
     auto t_begin = std::chrono::steady_clock::now();
-#define GAF_CHECK(call)                                                                                                                  \
-    do {                                                                                                                                \
-        hipError_t e_ = (call);                                                                                                         \
-        if (e_ != hipSuccess) {                                                                                                         \
-            if (st) (void)hipStreamSynchronize(st);                                                                                     \
-            vga_chain_text_free(res);                                                                                                   \
-            return vga_set_error(ctx, e_ == hipErrorOutOfMemory ? VGA_ERR_NOMEM : VGA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                                                                   \
-        }                                                                                                                               \
-    } while (0)
-    vga_chain_text *res = (vga_chain_text *)calloc(1, sizeof(vga_chain_text));
-    if (!res) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text)");
+    hipStream_t st = nullptr;
+    vga_result_guard<vga_chain_text, vga_chain_text_free> res;  // (an early return waits for `st`, then frees the text)
+    res.wait[0] = &st;
+    res.p = (vga_chain_text *)calloc(1, sizeof(vga_chain_text));
+    if (!res.p) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text)");
     const uint64_t nc = m->n_chains;
     res->n_chains = nc;
     res->text_off = (uint64_t *)calloc(nc + 1, sizeof(uint64_t));
-    if (!res->text_off) { vga_chain_text_free(res); return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text offsets)"); }
+    if (!res->text_off) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text offsets)");
     const uint64_t n_members = nc ? m->chain_anchor_off[nc] : 0;
-    if (nc == 0 || n_members == 0) { *out = res; return VGA_OK; }
-    if (nc >= (1ull << 31)) { vga_chain_text_free(res); return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "too many chains in one call"); }
+    if (nc == 0 || n_members == 0) { *out = res.release(); return VGA_OK; }
+    if (nc >= (1ull << 31)) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "too many chains in one call");
     if (!ctx->gaf_ws) {
         ctx->gaf_ws = new gaf_ws();
         ctx->gaf_ws_free = [](void *q) { delete (gaf_ws *)q; };
     }
     gaf_ws &W = *(gaf_ws *)ctx->gaf_ws;
-    if (!W.st) GAF_CHECK(hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking));
+    if (!W.st) VGA_HIP_CHECK_OOM(ctx, hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking));
     st = W.st;
-    GAF_CHECK(W.h_chains.reserve(nc)); GAF_CHECK(W.d_chains.reserve(nc)); GAF_CHECK(W.h_len.reserve(nc)); GAF_CHECK(W.d_len.reserve(nc));
-    GAF_CHECK(W.d_member.reserve(n_members)); GAF_CHECK(W.d_tb.reserve(m->n_anchors + 1)); GAF_CHECK(W.d_te.reserve(m->n_anchors + 1));
+    VGA_HIP_CHECK_OOM(ctx, W.h_chains.reserve(nc)); VGA_HIP_CHECK_OOM(ctx, W.d_chains.reserve(nc));
+    VGA_HIP_CHECK_OOM(ctx, W.h_len.reserve(nc)); VGA_HIP_CHECK_OOM(ctx, W.d_len.reserve(nc));
+    VGA_HIP_CHECK_OOM(ctx, W.d_member.reserve(n_members)); VGA_HIP_CHECK_OOM(ctx, W.d_tb.reserve(m->n_anchors + 1));
+    VGA_HIP_CHECK_OOM(ctx, W.d_te.reserve(m->n_anchors + 1));
     {
         uint64_t c = 0;
         for (uint64_t r = 0; r < m->n_reads; r++)
             for (c = m->chain_off[r]; c < m->chain_off[r + 1]; c++)
                 W.h_chains.p[c] = {m->anchor_off[r], m->chain_anchor_off[c], m->chain_placeholder[c] ? m->chain_anchor_off[c] : m->chain_anchor_off[c + 1], 0};
     }
-    GAF_CHECK(hipMemcpyAsync(W.d_member.p, m->chain_anchor_idx, n_members * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GAF_CHECK(hipMemcpyAsync(W.d_tb.p, m->target_begin, m->n_anchors * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GAF_CHECK(hipMemcpyAsync(W.d_te.p, m->target_end, m->n_anchors * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GAF_CHECK(hipMemcpyAsync(W.d_chains.p, W.h_chains.p, nc * sizeof(gaf_chain), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_member.p, m->chain_anchor_idx, n_members * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_tb.p, m->target_begin, m->n_anchors * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_te.p, m->target_end, m->n_anchors * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_chains.p, W.h_chains.p, nc * sizeof(gaf_chain), hipMemcpyHostToDevice, st));
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nc, 32ull * (uint64_t)ctx->n_cu);
     const vga_dev_index &ix = ctx->index;
     hipLaunchKernelGGL(k_gaf_chain_len, dim3(grid), dim3(64), 0, st, (uint32_t)nc, W.d_chains.p, W.d_member.p, W.d_tb.p, W.d_te.p, ix.d_node_start,
                        (uint32_t)ix.n_nodes, W.d_len.p);
-    GAF_CHECK(hipGetLastError());
-    GAF_CHECK(hipMemcpyAsync(W.h_len.p, W.d_len.p, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    GAF_CHECK(hipStreamSynchronize(st));
+    VGA_HIP_CHECK_OOM(ctx, hipGetLastError());
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.h_len.p, W.d_len.p, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
     uint64_t tot = 0;
     for (uint64_t c = 0; c < nc; c++) { res->text_off[c] = tot; W.h_chains.p[c].text0 = tot; tot += W.h_len.p[c]; }
     res->text_off[nc] = tot;
-    GAF_CHECK(W.d_text.reserve(tot + 64));
+    VGA_HIP_CHECK_OOM(ctx, W.d_text.reserve(tot + 64));
     // (pageable: the runtime stages the copy at ~20 GB/s; a pinned buffer of this size costs more to allocate than that)
     res->text = (char *)malloc(tot + 64);
-    if (!res->text) { vga_chain_text_free(res); return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text, %llu bytes)", (unsigned long long)tot); }
-    GAF_CHECK(hipMemcpyAsync(W.d_chains.p, W.h_chains.p, nc * sizeof(gaf_chain), hipMemcpyHostToDevice, st));
+    if (!res->text) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (chain text, %llu bytes)", (unsigned long long)tot);
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_chains.p, W.h_chains.p, nc * sizeof(gaf_chain), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_gaf_chain_write, dim3(grid), dim3(64), 0, st, (uint32_t)nc, W.d_chains.p, W.d_member.p, W.d_tb.p, W.d_te.p, ix.d_node_start,
                        (uint32_t)ix.n_nodes, W.d_text.p);
-    GAF_CHECK(hipGetLastError());
-    GAF_CHECK(hipMemcpyAsync(res->text, W.d_text.p, tot, hipMemcpyDeviceToHost, st));
-    GAF_CHECK(hipStreamSynchronize(st));
+    VGA_HIP_CHECK_OOM(ctx, hipGetLastError());
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(res->text, W.d_text.p, tot, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
     res->ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-#undef GAF_CHECK
-    *out = res;
+    *out = res.release();
     return VGA_OK;
 }
 

@@ -601,12 +601,6 @@ struct map_ws {
     }
 };
 
-template <typename T>
-T *xmalloc(size_t n)
-{
-    return (T *)malloc((n ? n : 1) * sizeof(T));
-}
-
 }  // namespace
 
 extern "C" void vga_map_result_free(vga_map_result *r)
@@ -628,23 +622,85 @@ extern "C" void vga_map_result_free(vga_map_result *r)
     free(r);
 }
 
-static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_map_result **out)
-{
-    if (!b || !params || !out || !b->ctx) return VGA_ERR_ARG;  // b->ctx == nullptr: the context was destroyed
-    vga_ctx *ctx = b->ctx;
-    *out = nullptr;
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    vga_release_deferred(ctx);  // (buffers of this context that grew during an earlier call: freed now, while it has nothing in flight)
-    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_map_batch: no index uploaded");
+namespace {
+
+// Where the result's per-read values and, with emit_dp, per-anchor ids / f(i) / predecessors are copied from: K3's own arrays
+// in forward mode, the chosen orientation's copies with VGA_STRANDS_BOTH.
+struct map_source {
+    const double *curr_max = nullptr;
+    const uint32_t *chain_cnt = nullptr, *chain_words = nullptr;
+    const uint32_t *ids = nullptr;
+    const double *f = nullptr;
+    const int32_t *pred = nullptr;
+};
+
+// The state of one vga_map_batch call.  vga_map_batch_impl below is the sequence of its stages.
+struct map_call {
+    vga_ctx *const ctx;
+    vga_batch *const b;
+    const vga_map_params *const params;
+    const vga_dev_index &ix;
+    const uint64_t R;
     // only_forward = 0 (anchors_for_query(..., false), src/chain.rs:154-155): every k-mer record becomes an anchor; the
     // orientation of each end travels in bit 31 of target_begin / target_end.  vga_align_batch accepts forward chains only.
+    const bool all_orients;
+    // VGA_STRANDS_BOTH: the read and its reverse complement, each forward-only (vga_strand.hip).  K1-K3 run over RV virtual
+    // reads: the reads, then their reverse complements
+    const bool both;
+    const uint64_t RV;
+    const bool emit_dp;
+    const hipStream_t st;
+    map_ws &ws;
+    const std::chrono::steady_clock::time_point t_host0 = std::chrono::steady_clock::now();
+    vga_trace tr{"map"};
+    const uint64_t *d_read_off = nullptr;
+    std::vector<uint64_t> aoff_v;  // VGA_STRANDS_BOTH: anchor offsets of the virtual reads (forward mode: the result's own)
+    uint64_t total = 0;            // anchors of all virtual reads
+    std::vector<double> gc;        // the gap-cost table
+    const uint32_t *perm = nullptr;  // the sorted anchors' ids
+    int t_total = -1;
+    map_source src;
+    uint64_t chain_total_words = 0;
+    std::unique_ptr<uint32_t, void (*)(void *)> chain_words_host{nullptr, free};
+    // The result, held from its allocation on: an early return waits for `st` and the side stream (copies into the result's
+    // pageable arrays and into chain_words_host may be in flight), then frees it.  The last member, so that this happens before
+    // anything above goes.
+    vga_result_guard<vga_map_result, vga_map_result_free> res;
+
+    map_call(vga_batch *batch, const vga_map_params *p, map_ws &w)
+        : ctx(batch->ctx), b(batch), params(p), ix(batch->ctx->index), R(batch->n_reads), all_orients(!p->only_forward),
+          both(p->strands == VGA_STRANDS_BOTH), RV(both ? 2 * R : R), emit_dp(p->emit_dp != 0), st(batch->ctx->stream), ws(w)
+    {
+        res.wait[0] = &st;
+        res.wait[1] = &ws.st_copy;
+    }
+
+    // every host allocation of the result is checked before it is written to: VGA_ERR_NOMEM instead of a crash
+    int nomem() { return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (map result of %llu reads)", (unsigned long long)R); }
+    bool alloc_anchor_arrays(size_t n);
+    int begin_result();
+    template <bool EMIT>
+    void launch_probe();
+    int count();
+    int emit_and_sort();
+    template <bool GAP_LDS>
+    void launch_chain(size_t lds_bytes, uint32_t key_anchors);
+    void chain();
+    int source_forward();
+    int source_picked();
+    int fetch_counts();
+    int gather_picked();
+    int fetch_chains();
+    int assemble();
+};
+
+int map_validate(vga_ctx *ctx, const vga_map_params *params)
+{
+    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_map_batch: no index uploaded");
     const bool all_orients = !params->only_forward;
     if (params->strands != VGA_STRANDS_FORWARD && params->strands != VGA_STRANDS_BOTH)
         return vga_set_error(ctx, VGA_ERR_ARG, "strands %d: VGA_STRANDS_FORWARD (0) or VGA_STRANDS_BOTH (1)", params->strands);
-    // VGA_STRANDS_BOTH: the read and its reverse complement, each forward-only (vga_strand.hip)
-    const bool both = params->strands == VGA_STRANDS_BOTH;
-    if (both && all_orients)
+    if (params->strands == VGA_STRANDS_BOTH && all_orients)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "strands = VGA_STRANDS_BOTH maps the read and its reverse complement forward-only: it needs only_forward = 1");
     if (all_orients && !ctx->index.all_view)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "only_forward=0 needs the all-orientation probe table, which is built for k <= 13");
@@ -652,22 +708,14 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "bandwidth %u: the wavefront chaining kernel supports 1..64", params->bandwidth);
     if (params->max_gap > (1u << 22))
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "max_gap too large for the tabulated gap cost");
-    const vga_dev_index &ix = ctx->index;
-    const uint64_t R = b->n_reads;
-    hipStream_t st = ctx->stream;
-    if (!ctx->map_ws) {
-        ctx->map_ws = new map_ws();
-        ctx->map_ws_free = [](void *p) { delete (map_ws *)p; };
-    }
-    map_ws &ws = *(map_ws *)ctx->map_ws;
-    vga_timers_reset(ctx);
-    auto t_host0 = std::chrono::steady_clock::now();
-    vga_trace tr("map");
+    return VGA_OK;
+}
 
-    vga_map_result *res = (vga_map_result *)calloc(1, sizeof(vga_map_result));
-    if (!res) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (map result)");
-    // every host allocation of the result is checked before it is written to: VGA_ERR_NOMEM instead of a crash
-    auto nomem = [&]() { vga_map_result_free(res); return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (map result of %llu reads)", (unsigned long long)R); };
+// the result and its per-read arrays
+int map_call::begin_result()
+{
+    res.p = (vga_map_result *)calloc(1, sizeof(vga_map_result));
+    if (!res.p) return vga_set_error(ctx, VGA_ERR_NOMEM, "out of host memory (map result)");
     res->n_reads = R;
     res->anchor_off = xmalloc<uint64_t>(R + 1);
     res->curr_max = xmalloc<double>(R);
@@ -680,56 +728,46 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
         res->chain_anchor_off = xmalloc<uint64_t>(1);
         if (!res->chain_anchor_off) return nomem();
         res->chain_anchor_off[0] = 0;
-        *out = res;
-        return VGA_OK;
     }
+    return VGA_OK;
+}
 
-#define MAP_CHECK(call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (void)hipStreamSynchronize(st); /* (copies into the result's arrays may be in flight) */ \
-            if (ws.st_copy) (void)hipStreamSynchronize(ws.st_copy);                                  \
-            vga_map_result_free(res);                                                                \
-            return vga_set_error(ctx, VGA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-                                 __LINE__);                                                          \
-        }                                                                                            \
-    } while (0)
+// K1, one of its two passes.  The loaded index decides the variant: its hashed table (k >= 16) serves both views through its two
+// header columns
+template <bool EMIT>
+void map_call::launch_probe()
+{
+    const bool hashed = ix.d_hash != nullptr;
+    const void *table = hashed ? (const void *)ix.d_hash : (const void *)(all_orients ? ix.d_table_all : ix.d_table);
+    const uint2 *pos = all_orients ? ix.d_pos_all : ix.d_pos;
+    const auto kernel = hashed ? k_kmer_probe<EMIT, true> : k_kmer_probe<EMIT, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st, b->d_reads, d_read_off, ix.k, table, pos, EMIT ? nullptr : ws.cnt.p,
+                       EMIT ? ws.anchor_off.p : nullptr, EMIT ? ws.a_qb.p : nullptr, EMIT ? ws.a_tb.p : nullptr, EMIT ? ws.a_te.p : nullptr,
+                       EMIT ? ws.a_idx.p : nullptr, ix.hash_mask, all_orients ? 0u : 1u);
+}
 
-    // K1-K3 run over RV virtual reads: the reads, then (VGA_STRANDS_BOTH) their reverse complements
-    const uint64_t RV = both ? 2 * R : R;
+// K1 pass 1 (count), the anchor offsets of the virtual reads, the workspace for that many anchors, the gap-cost table
+int map_call::count()
+{
     if (both) {
         const int rc = vga_batch_revcomp_device(b);
-        if (rc != VGA_OK) { vga_map_result_free(res); return rc; }
+        if (rc != VGA_OK) return rc;
         tr.mark("reverse complement");
     }
-    const uint64_t *d_read_off = both ? b->d_read_off2 : b->d_read_off;
-
-    // ---- K1 pass 1: count
-    MAP_CHECK(ws.cnt.reserve(RV));
-    MAP_CHECK(ws.anchor_off.reserve(RV + 1));
-    int t_total = vga_timer_begin(ctx, "map_total", 0);
+    d_read_off = both ? b->d_read_off2 : b->d_read_off;
+    VGA_HIP_CHECK(ctx, ws.cnt.reserve(RV));
+    VGA_HIP_CHECK(ctx, ws.anchor_off.reserve(RV + 1));
+    t_total = vga_timer_begin(ctx, "map_total", 0);
     int t1 = vga_timer_begin(ctx, "kmer_probe_count", 0);
-    // the loaded index decides the variant: its hashed table (k >= 16) serves both views through its two header columns
-    const bool hashed = ix.d_hash != nullptr;
-    const void *probe_table = hashed ? (const void *)ix.d_hash : (const void *)(all_orients ? ix.d_table_all : ix.d_table);
-    const uint2 *probe_pos = all_orients ? ix.d_pos_all : ix.d_pos;
-    const uint32_t hash_ff = all_orients ? 0u : 1u;
-    const auto probe_count = hashed ? k_kmer_probe<false, true> : k_kmer_probe<false, false>;
-    const auto probe_emit = hashed ? k_kmer_probe<true, true> : k_kmer_probe<true, false>;
-    hipLaunchKernelGGL(probe_count, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st,
-                       b->d_reads, d_read_off, ix.k, probe_table, probe_pos, ws.cnt.p, (const uint64_t *)nullptr, (uint32_t *)nullptr,
-                       (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, ix.hash_mask, hash_ff);
+    launch_probe<false>();
     vga_timer_end(ctx, t1);
-    MAP_CHECK(ws.h_cnt.reserve(RV));
+    VGA_HIP_CHECK(ctx, ws.h_cnt.reserve(RV));
     uint32_t *h_cnt = ws.h_cnt.p;
-    MAP_CHECK(hipMemcpyAsync(h_cnt, ws.cnt.p, RV * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipStreamSynchronize(st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(h_cnt, ws.cnt.p, RV * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     tr.mark("count kernel + sync");
-    // anchor offsets of the virtual reads: the result's own in forward mode
-    std::vector<uint64_t> aoff_v(both ? RV + 1 : 0);
+    aoff_v.resize(both ? RV + 1 : 0);
     uint64_t *h_aoff = both ? aoff_v.data() : res->anchor_off;
-    uint64_t total = 0;
     for (uint64_t r = 0; r < RV; r++) {
         h_aoff[r] = total;
         total += h_cnt[r];
@@ -737,27 +775,31 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     h_aoff[RV] = total;
     res->n_anchors = total;
     res->n_hits = total;
-    MAP_CHECK(hipMemcpyAsync(ws.anchor_off.p, h_aoff, (RV + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.anchor_off.p, h_aoff, (RV + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 
     const size_t An = (size_t)total;
-    MAP_CHECK(ws.a_qb.reserve(An)); MAP_CHECK(ws.a_tb.reserve(An)); MAP_CHECK(ws.a_te.reserve(An));
-    MAP_CHECK(ws.a_idx.reserve(An)); MAP_CHECK(ws.key_b.reserve(An)); MAP_CHECK(ws.val_b.reserve(An));
-    MAP_CHECK(ws.s_qb.reserve(An)); MAP_CHECK(ws.s_tb.reserve(An)); MAP_CHECK(ws.s_te.reserve(An));
-    MAP_CHECK(ws.f.reserve(An)); MAP_CHECK(ws.pred_id.reserve(An)); MAP_CHECK(ws.pred_pos.reserve(An));
-    MAP_CHECK(ws.curr_max.reserve(RV));
-    MAP_CHECK(ws.chain_buf.reserve(3 * An + 2 * RV + 2));
-    MAP_CHECK(ws.chain_cnt.reserve(RV)); MAP_CHECK(ws.chain_words.reserve(RV));
-
+    VGA_HIP_CHECK(ctx, ws.a_qb.reserve(An)); VGA_HIP_CHECK(ctx, ws.a_tb.reserve(An)); VGA_HIP_CHECK(ctx, ws.a_te.reserve(An));
+    VGA_HIP_CHECK(ctx, ws.a_idx.reserve(An)); VGA_HIP_CHECK(ctx, ws.key_b.reserve(An)); VGA_HIP_CHECK(ctx, ws.val_b.reserve(An));
+    VGA_HIP_CHECK(ctx, ws.s_qb.reserve(An)); VGA_HIP_CHECK(ctx, ws.s_tb.reserve(An)); VGA_HIP_CHECK(ctx, ws.s_te.reserve(An));
+    VGA_HIP_CHECK(ctx, ws.f.reserve(An)); VGA_HIP_CHECK(ctx, ws.pred_id.reserve(An)); VGA_HIP_CHECK(ctx, ws.pred_pos.reserve(An));
+    VGA_HIP_CHECK(ctx, ws.curr_max.reserve(RV));
+    VGA_HIP_CHECK(ctx, ws.chain_buf.reserve(3 * An + 2 * RV + 2));
+    VGA_HIP_CHECK(ctx, ws.chain_cnt.reserve(RV)); VGA_HIP_CHECK(ctx, ws.chain_words.reserve(RV));
     tr.mark("workspace reserve");
     // gap cost table (src/chain.rs:348-354), host libm
     const uint64_t mg = params->max_gap;
-    std::vector<double> gc(mg + 1);
+    gc.resize(mg + 1);
     gc[0] = 0.0;
     for (uint64_t g = 1; g <= mg; g++) gc[g] = 0.01 * (double)ix.k * (double)g + 0.5 * log2((double)g);
-    MAP_CHECK(ws.gap_cost.reserve(mg + 1));
-    MAP_CHECK(hipMemcpyAsync(ws.gap_cost.p, gc.data(), (mg + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, ws.gap_cost.reserve(mg + 1));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.gap_cost.p, gc.data(), (mg + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    return VGA_OK;
+}
 
-    // ---- K1 pass 2: emit
+// K1 pass 2 (emit), K2 (sort by target_end), and the event the side stream's copies of the sorted coordinates wait for
+int map_call::emit_and_sort()
+{
+    const size_t An = (size_t)total;
     // byte model B_map: L + 4(L-k+1) read+table (16 per probe of the hashed table: one slot, more when the walk goes on),
     // 8H positions, 16A anchor write
     uint64_t nkm = 0;
@@ -766,13 +808,10 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
         if (L >= ix.k) nkm += L - ix.k + 1;
     }
     if (both) nkm *= 2;  // (a reverse complement has the k-mers of its read)
-    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", (both ? 2 : 1) * b->total_bases + (hashed ? 16 : 4) * nkm + 8 * total + 16 * total);
-    hipLaunchKernelGGL(probe_emit, dim3((unsigned)RV), dim3(VGA_PROBE_NT), 0, st,
-                       b->d_reads, d_read_off, ix.k, probe_table, probe_pos, (uint32_t *)nullptr, ws.anchor_off.p, ws.a_qb.p, ws.a_tb.p,
-                       ws.a_te.p, ws.a_idx.p, ix.hash_mask, hash_ff);
+    int t2 = vga_timer_begin(ctx, "kmer_probe_emit", (both ? 2 : 1) * b->total_bases + (ix.d_hash ? 16 : 4) * nkm + 8 * total + 16 * total);
+    launch_probe<true>();
     vga_timer_end(ctx, t2);
 
-    // ---- K2: sort by target_end
     uint32_t nbits = 1;
     while ((1ull << nbits) <= ix.seq_length && nbits < 32) nbits++;
     // with both orientations the order is (orientation descending, position ascending), src/chain.rs:386-389: the key is
@@ -780,160 +819,179 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     const uint32_t n_pass = all_orients ? 4 : (nbits + 7) / 8;
     // the keys are sorted in place of a_te (ping) / key_b (pong); the original te is re-gathered from a copy
     vga_dbuf<uint32_t> &key_a = ws.key_a;
-    MAP_CHECK(key_a.reserve(An));
-    if (An) MAP_CHECK(hipMemcpyAsync(key_a.p, ws.a_te.p, An * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    VGA_HIP_CHECK(ctx, key_a.reserve(An));
+    if (An) VGA_HIP_CHECK(ctx, hipMemcpyAsync(key_a.p, ws.a_te.p, An * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     if (An && all_orients) hipLaunchKernelGGL(k_flip_orient_bit, dim3((unsigned)((An + 255) / 256)), dim3(256), 0, st, key_a.p, (uint64_t)An);
     int t3 = vga_timer_begin(ctx, "anchor_sort", (uint64_t)n_pass * 16 * total + 24 * total);
     hipLaunchKernelGGL(k_anchor_sort, dim3((unsigned)RV), dim3(VGA_SORT_NT), 0, st, ws.anchor_off.p, n_pass, key_a.p,
                        ws.a_idx.p, ws.key_b.p, ws.val_b.p);
-    const uint32_t *perm = (n_pass & 1u) ? ws.val_b.p : ws.a_idx.p;
+    perm = (n_pass & 1u) ? ws.val_b.p : ws.a_idx.p;
     hipLaunchKernelGGL(k_anchor_gather_seg, dim3((unsigned)RV), dim3(256), 0, st, ws.anchor_off.p, perm, ws.a_qb.p, ws.a_tb.p,
                        ws.a_te.p, ws.s_qb.p, ws.s_tb.p, ws.s_te.p);
     vga_timer_end(ctx, t3);
-    // the sorted coordinates are final: they go back beside the chaining kernel (below, once it is launched)
+    // the sorted coordinates are final: they go back beside the chaining kernel (source_forward, once it is launched)
     if (!ws.st_copy) {
-        MAP_CHECK(hipStreamCreateWithFlags(&ws.st_copy, hipStreamNonBlocking));
-        MAP_CHECK(hipEventCreateWithFlags(&ws.ev_sorted, hipEventDisableTiming));
+        VGA_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ws.st_copy, hipStreamNonBlocking));
+        VGA_HIP_CHECK(ctx, hipEventCreateWithFlags(&ws.ev_sorted, hipEventDisableTiming));
     }
-    MAP_CHECK(hipEventRecord(ws.ev_sorted, st));
-    MAP_CHECK(hipStreamWaitEvent(ws.st_copy, ws.ev_sorted, 0));
+    VGA_HIP_CHECK(ctx, hipEventRecord(ws.ev_sorted, st));
+    VGA_HIP_CHECK(ctx, hipStreamWaitEvent(ws.st_copy, ws.ev_sorted, 0));
     tr.mark("probe + sort launches");
+    return VGA_OK;
+}
 
-    // ---- K3: chain DP + backtracking
+template <bool GAP_LDS>
+void map_call::launch_chain(size_t lds_bytes, uint32_t key_anchors)
+{
+    hipLaunchKernelGGL(k_chain4<GAP_LDS>, dim3((unsigned)((RV + 3) / 4)), dim3(256), lds_bytes, st, (uint32_t)RV, ws.anchor_off.p, perm, ws.s_qb.p,
+                       ws.s_tb.p, ws.s_te.p, ix.k, params->bandwidth, params->max_gap, params->chain_min_n_anchors, ws.gap_cost.p, ws.f.p,
+                       ws.pred_id.p, ws.pred_pos.p, ws.curr_max.p, ws.chain_buf.p, ws.chain_cnt.p, ws.chain_words.p, key_anchors);
+}
+
+// K3: chain DP + backtracking
+void map_call::chain()
+{
     int t4 = vga_timer_begin(ctx, "chain_dp", 16 * total + 12 * total);
-    {
-        const size_t gap_bytes = (size_t)(params->max_gap + 1) * sizeof(double);
-        // reads with at most this many anchors take their argmax on round(1000 score) as a 32-bit integer (vga_chain_dp):
-        // |score| <= k (A + 1) + gap_cost[max_gap], with room to spare
-        uint32_t key_anchors = 0;
-        {
-            const double room = 2147483647.0 / 1000.0 - gc[mg] - 4.0 * (double)ix.k - 16.0;
-            if (room > 0.0 && !getenv("VGA_CHAIN_F64")) key_anchors = (uint32_t)std::min(room / (double)ix.k, 4.0e9);
-        }
-#define CHAIN_ARGS ws.anchor_off.p, perm, ws.s_qb.p, ws.s_tb.p, ws.s_te.p, ix.k, params->bandwidth, params->max_gap,           \
-                   params->chain_min_n_anchors, ws.gap_cost.p, ws.f.p, ws.pred_id.p, ws.pred_pos.p, ws.curr_max.p,         \
-                   ws.chain_buf.p, ws.chain_cnt.p, ws.chain_words.p, key_anchors
-        if (gap_bytes <= 16 * 1024)  // (8 KB at the default max_gap; bigger tables stay in HBM)
-            hipLaunchKernelGGL(k_chain4<true>, dim3((unsigned)((RV + 3) / 4)), dim3(256), gap_bytes, st, (uint32_t)RV, CHAIN_ARGS);
-        else
-            hipLaunchKernelGGL(k_chain4<false>, dim3((unsigned)((RV + 3) / 4)), dim3(256), 0, st, (uint32_t)RV, CHAIN_ARGS);
-#undef CHAIN_ARGS
-    }
+    const size_t gap_bytes = (size_t)(params->max_gap + 1) * sizeof(double);
+    // reads with at most this many anchors take their argmax on round(1000 score) as a 32-bit integer (vga_chain_dp):
+    // |score| <= k (A + 1) + gap_cost[max_gap], with room to spare
+    uint32_t key_anchors = 0;
+    const double room = 2147483647.0 / 1000.0 - gc[params->max_gap] - 4.0 * (double)ix.k - 16.0;
+    if (room > 0.0 && !getenv("VGA_CHAIN_F64")) key_anchors = (uint32_t)std::min(room / (double)ix.k, 4.0e9);
+    if (gap_bytes <= 16 * 1024)  // (8 KB at the default max_gap; bigger tables stay in HBM)
+        launch_chain<true>(gap_bytes, key_anchors);
+    else
+        launch_chain<false>(0, key_anchors);
     vga_timer_end(ctx, t4);
     vga_timer_end(ctx, t_total);
-
     tr.mark("chain launch");
-    // ---- results to host.  The per-anchor arrays go straight into the result's own (pageable) arrays: the runtime stages
-    // such a copy through its own pinned buffers at ~20 GB/s, where pinned staging of our own costs a hipHostMalloc of the
-    // same size first (60-90 ms per 400 MB, tests/microbench/pinned_time.hip) and a fan-out copy afterwards.  The small
-    // per-read arrays keep their pinned staging.
-    const bool emit_dp = params->emit_dp != 0;
-    auto alloc_anchor_arrays = [&](size_t n) -> bool {
-        if (emit_dp) {
-            res->anchor_id = xmalloc<uint32_t>(n);
-            res->max_chain_score = xmalloc<double>(n);
-            res->best_pred_id = xmalloc<int32_t>(n);
-        }
-        res->query_begin = xmalloc<uint32_t>(n);
-        res->target_begin = xmalloc<uint32_t>(n);
-        res->target_end = xmalloc<uint32_t>(n);
-        return !((emit_dp && (!res->anchor_id || !res->max_chain_score || !res->best_pred_id)) || !res->query_begin || !res->target_begin ||
-                 !res->target_end);
-    };
-    // where the result's per-read values and per-anchor ids / f(i) / predecessors come from: the chosen orientation's
-    // gathered copies with VGA_STRANDS_BOTH
-    const double *d_curr_max = ws.curr_max.p;
-    const uint32_t *d_chain_cnt = ws.chain_cnt.p, *d_chain_words = ws.chain_words.p;
-    const uint32_t *d_ids = perm;
-    const double *d_f = ws.f.p;
-    const int32_t *d_pred = ws.pred_id.p;
-    if (!both) {
-        if (!alloc_anchor_arrays(An)) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamSynchronize(ws.st_copy);
-            return nomem();
-        }
-        if (An) {  // (beside the chaining kernel: these wait for the sort only)
-            MAP_CHECK(hipMemcpyAsync(res->query_begin, ws.s_qb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
-            MAP_CHECK(hipMemcpyAsync(res->target_begin, ws.s_tb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
-            MAP_CHECK(hipMemcpyAsync(res->target_end, ws.s_te.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
-        }
-    } else {
-        // ---- the pick, and the offsets of the chosen orientations' anchors (a count, then an exclusive scan)
-        MAP_CHECK(ws.strand.reserve(R)); MAP_CHECK(ws.sel.reserve(R)); MAP_CHECK(ws.sel_anchors.reserve(R));
-        MAP_CHECK(ws.sel_curr_max.reserve(R)); MAP_CHECK(ws.sel_chain_cnt.reserve(R)); MAP_CHECK(ws.sel_chain_words.reserve(R));
-        MAP_CHECK(ws.sel_off.reserve(R + 1));
-        const int tp = vga_timer_begin(ctx, "strand_pick", 2 * R * (8 + 8 + 4 + 4) + R * (1 + 4 + 4 + 8 + 4 + 4) + R * (4 + 8));
-        hipLaunchKernelGGL(k_strand_pick, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (uint32_t)R, ws.anchor_off.p, ws.curr_max.p,
-                           ws.chain_cnt.p, ws.chain_words.p, ws.strand.p, ws.sel.p, ws.sel_anchors.p, ws.sel_curr_max.p, ws.sel_chain_cnt.p,
-                           ws.sel_chain_words.p);
-        hipLaunchKernelGGL(k_strand_scan, dim3(1), dim3(256), 0, st, (uint32_t)R, ws.sel_anchors.p, ws.sel_off.p);
-        vga_timer_end(ctx, tp);
-        MAP_CHECK(hipMemcpyAsync(res->anchor_off, ws.sel_off.p, (R + 1) * 8, hipMemcpyDeviceToHost, st));
-        MAP_CHECK(hipMemcpyAsync(res->strand, ws.strand.p, R, hipMemcpyDeviceToHost, st));
-        d_curr_max = ws.sel_curr_max.p;
-        d_chain_cnt = ws.sel_chain_cnt.p;
-        d_chain_words = ws.sel_chain_words.p;
+}
+
+// The per-anchor arrays go straight into the result's own (pageable) arrays: the runtime stages such a copy through its own
+// pinned buffers at ~20 GB/s, where pinned staging of our own costs a hipHostMalloc of the same size first (60-90 ms per
+// 400 MB, tests/microbench/pinned_time.hip) and a fan-out copy afterwards.  The small per-read arrays keep their pinned staging.
+bool map_call::alloc_anchor_arrays(size_t n)
+{
+    if (emit_dp) {
+        res->anchor_id = xmalloc<uint32_t>(n);
+        res->max_chain_score = xmalloc<double>(n);
+        res->best_pred_id = xmalloc<int32_t>(n);
     }
-    MAP_CHECK(ws.h_curr_max.reserve(R)); MAP_CHECK(ws.h_chain_cnt.reserve(R)); MAP_CHECK(ws.h_chain_words.reserve(R));
-    MAP_CHECK(ws.h_chain_woff.reserve(R + 1)); MAP_CHECK(ws.chain_woff.reserve(R + 1));
-    // the per-read counts first: they say how much of the chain buffer is in use
-    MAP_CHECK(hipMemcpyAsync(ws.h_curr_max.p, d_curr_max, R * 8, hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipMemcpyAsync(ws.h_chain_cnt.p, d_chain_cnt, R * 4, hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipMemcpyAsync(ws.h_chain_words.p, d_chain_words, R * 4, hipMemcpyDeviceToHost, st));
-    MAP_CHECK(hipStreamSynchronize(st));
-    if (both) {
-        // ---- the chosen orientation's anchors to compact arrays, and from there to the result
-        const size_t As = (size_t)res->anchor_off[R];
-        res->n_anchors = As;
-        if (!alloc_anchor_arrays(As)) return nomem();
-        MAP_CHECK(ws.g_qb.reserve(As)); MAP_CHECK(ws.g_tb.reserve(As)); MAP_CHECK(ws.g_te.reserve(As));
-        if (emit_dp) { MAP_CHECK(ws.g_id.reserve(As)); MAP_CHECK(ws.g_f.reserve(As)); MAP_CHECK(ws.g_pred.reserve(As)); }
-        const int tg = vga_timer_begin(ctx, "strand_gather", (uint64_t)As * 2 * (12 + (emit_dp ? 16 : 0)) + R * 20);
-        hipLaunchKernelGGL(k_strand_gather, dim3((unsigned)R), dim3(256), 0, st, ws.sel.p, ws.anchor_off.p, ws.sel_off.p, ws.s_qb.p, ws.s_tb.p,
-                           ws.s_te.p, perm, ws.f.p, ws.pred_id.p, ws.g_qb.p, ws.g_tb.p, ws.g_te.p, emit_dp ? ws.g_id.p : nullptr,
-                           emit_dp ? ws.g_f.p : nullptr, emit_dp ? ws.g_pred.p : nullptr);
-        vga_timer_end(ctx, tg);
-        if (As) {
-            MAP_CHECK(hipMemcpyAsync(res->query_begin, ws.g_qb.p, As * 4, hipMemcpyDeviceToHost, st));
-            MAP_CHECK(hipMemcpyAsync(res->target_begin, ws.g_tb.p, As * 4, hipMemcpyDeviceToHost, st));
-            MAP_CHECK(hipMemcpyAsync(res->target_end, ws.g_te.p, As * 4, hipMemcpyDeviceToHost, st));
-        }
-        d_ids = ws.g_id.p;
-        d_f = ws.g_f.p;
-        d_pred = ws.g_pred.p;
+    res->query_begin = xmalloc<uint32_t>(n);
+    res->target_begin = xmalloc<uint32_t>(n);
+    res->target_end = xmalloc<uint32_t>(n);
+    return !((emit_dp && (!res->anchor_id || !res->max_chain_score || !res->best_pred_id)) || !res->query_begin || !res->target_begin ||
+             !res->target_end);
+}
+
+// forward mode: the result is K2's sorted arrays and K3's own output; the coordinates are copied beside the chaining kernel
+int map_call::source_forward()
+{
+    src = {ws.curr_max.p, ws.chain_cnt.p, ws.chain_words.p, perm, ws.f.p, ws.pred_id.p};
+    const size_t An = (size_t)total;
+    if (!alloc_anchor_arrays(An)) return nomem();
+    if (An) {  // (these wait for the sort only)
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->query_begin, ws.s_qb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->target_begin, ws.s_tb.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->target_end, ws.s_te.p, An * 4, hipMemcpyDeviceToHost, ws.st_copy));
     }
+    return VGA_OK;
+}
+
+// VGA_STRANDS_BOTH: the pick, and the offsets of the chosen orientations' anchors (a count, then an exclusive scan); the
+// per-read values of the chosen orientation.  Its anchors follow in gather_picked, once their number is known
+int map_call::source_picked()
+{
+    VGA_HIP_CHECK(ctx, ws.strand.reserve(R)); VGA_HIP_CHECK(ctx, ws.sel.reserve(R)); VGA_HIP_CHECK(ctx, ws.sel_anchors.reserve(R));
+    VGA_HIP_CHECK(ctx, ws.sel_curr_max.reserve(R)); VGA_HIP_CHECK(ctx, ws.sel_chain_cnt.reserve(R)); VGA_HIP_CHECK(ctx, ws.sel_chain_words.reserve(R));
+    VGA_HIP_CHECK(ctx, ws.sel_off.reserve(R + 1));
+    const int tp = vga_timer_begin(ctx, "strand_pick", 2 * R * (8 + 8 + 4 + 4) + R * (1 + 4 + 4 + 8 + 4 + 4) + R * (4 + 8));
+    hipLaunchKernelGGL(k_strand_pick, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (uint32_t)R, ws.anchor_off.p, ws.curr_max.p,
+                       ws.chain_cnt.p, ws.chain_words.p, ws.strand.p, ws.sel.p, ws.sel_anchors.p, ws.sel_curr_max.p, ws.sel_chain_cnt.p,
+                       ws.sel_chain_words.p);
+    hipLaunchKernelGGL(k_strand_scan, dim3(1), dim3(256), 0, st, (uint32_t)R, ws.sel_anchors.p, ws.sel_off.p);
+    vga_timer_end(ctx, tp);
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->anchor_off, ws.sel_off.p, (R + 1) * 8, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->strand, ws.strand.p, R, hipMemcpyDeviceToHost, st));
+    src.curr_max = ws.sel_curr_max.p;
+    src.chain_cnt = ws.sel_chain_cnt.p;
+    src.chain_words = ws.sel_chain_words.p;
+    return VGA_OK;
+}
+
+// the per-read counts first: they say how much of the chain buffer is in use
+int map_call::fetch_counts()
+{
+    VGA_HIP_CHECK(ctx, ws.h_curr_max.reserve(R)); VGA_HIP_CHECK(ctx, ws.h_chain_cnt.reserve(R)); VGA_HIP_CHECK(ctx, ws.h_chain_words.reserve(R));
+    VGA_HIP_CHECK(ctx, ws.h_chain_woff.reserve(R + 1)); VGA_HIP_CHECK(ctx, ws.chain_woff.reserve(R + 1));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.h_curr_max.p, src.curr_max, R * 8, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.h_chain_cnt.p, src.chain_cnt, R * 4, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.h_chain_words.p, src.chain_words, R * 4, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return VGA_OK;
+}
+
+// VGA_STRANDS_BOTH: the chosen orientation's anchors to compact arrays, and from there to the result
+int map_call::gather_picked()
+{
+    const size_t As = (size_t)res->anchor_off[R];
+    res->n_anchors = As;
+    if (!alloc_anchor_arrays(As)) return nomem();
+    VGA_HIP_CHECK(ctx, ws.g_qb.reserve(As)); VGA_HIP_CHECK(ctx, ws.g_tb.reserve(As)); VGA_HIP_CHECK(ctx, ws.g_te.reserve(As));
+    if (emit_dp) { VGA_HIP_CHECK(ctx, ws.g_id.reserve(As)); VGA_HIP_CHECK(ctx, ws.g_f.reserve(As)); VGA_HIP_CHECK(ctx, ws.g_pred.reserve(As)); }
+    const int tg = vga_timer_begin(ctx, "strand_gather", (uint64_t)As * 2 * (12 + (emit_dp ? 16 : 0)) + R * 20);
+    hipLaunchKernelGGL(k_strand_gather, dim3((unsigned)R), dim3(256), 0, st, ws.sel.p, ws.anchor_off.p, ws.sel_off.p, ws.s_qb.p, ws.s_tb.p,
+                       ws.s_te.p, perm, ws.f.p, ws.pred_id.p, ws.g_qb.p, ws.g_tb.p, ws.g_te.p, emit_dp ? ws.g_id.p : nullptr,
+                       emit_dp ? ws.g_f.p : nullptr, emit_dp ? ws.g_pred.p : nullptr);
+    vga_timer_end(ctx, tg);
+    if (As) {
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->query_begin, ws.g_qb.p, As * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->target_begin, ws.g_tb.p, As * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->target_end, ws.g_te.p, As * 4, hipMemcpyDeviceToHost, st));
+    }
+    src.ids = ws.g_id.p;
+    src.f = ws.g_f.p;
+    src.pred = ws.g_pred.p;
+    return VGA_OK;
+}
+
+// chain compaction, the emit_dp arrays, and the end of everything the call put on its streams
+int map_call::fetch_chains()
+{
     const size_t An_res = (size_t)res->n_anchors;
-    uint64_t chain_total_words = 0;
     for (uint64_t r = 0; r < R; r++) { ws.h_chain_woff.p[r] = chain_total_words; chain_total_words += ws.h_chain_words.p[r]; }
     ws.h_chain_woff.p[R] = chain_total_words;
-    std::unique_ptr<uint32_t, void (*)(void *)> chain_words_host(xmalloc<uint32_t>(chain_total_words + 2), free);
-    if (!chain_words_host) { (void)hipStreamSynchronize(ws.st_copy); return nomem(); }
+    chain_words_host.reset(xmalloc<uint32_t>(chain_total_words + 2));
+    if (!chain_words_host) return nomem();
     if (chain_total_words) {
-        MAP_CHECK(ws.chain_comp.reserve(chain_total_words + 2));
-        MAP_CHECK(hipMemcpyAsync(ws.chain_woff.p, ws.h_chain_woff.p, (R + 1) * 8, hipMemcpyHostToDevice, st));
+        VGA_HIP_CHECK(ctx, ws.chain_comp.reserve(chain_total_words + 2));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(ws.chain_woff.p, ws.h_chain_woff.p, (R + 1) * 8, hipMemcpyHostToDevice, st));
         if (both)
             hipLaunchKernelGGL(k_chain_compact_sel, dim3((unsigned)R), dim3(256), 0, st, ws.sel.p, ws.anchor_off.p, ws.sel_chain_words.p,
                                ws.chain_woff.p, ws.chain_buf.p, ws.chain_comp.p);
         else
             hipLaunchKernelGGL(k_chain_compact, dim3((unsigned)R), dim3(256), 0, st, ws.anchor_off.p, ws.chain_words.p, ws.chain_woff.p,
                                ws.chain_buf.p, ws.chain_comp.p);
-        MAP_CHECK(hipMemcpyAsync(chain_words_host.get(), ws.chain_comp.p, chain_total_words * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(chain_words_host.get(), ws.chain_comp.p, chain_total_words * 4, hipMemcpyDeviceToHost, st));
     }
     if (An_res && emit_dp) {
-        MAP_CHECK(hipMemcpyAsync(res->anchor_id, d_ids, An_res * 4, hipMemcpyDeviceToHost, st));
-        MAP_CHECK(hipMemcpyAsync(res->max_chain_score, d_f, An_res * 8, hipMemcpyDeviceToHost, st));
-        MAP_CHECK(hipMemcpyAsync(res->best_pred_id, d_pred, An_res * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->anchor_id, src.ids, An_res * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->max_chain_score, src.f, An_res * 8, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(res->best_pred_id, src.pred, An_res * 4, hipMemcpyDeviceToHost, st));
     }
-    MAP_CHECK(hipStreamSynchronize(st));
-    MAP_CHECK(hipStreamSynchronize(ws.st_copy));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ws.st_copy));
     tr.mark("kernels + D2H");
     vga_timers_collect(ctx);
     memcpy(res->curr_max, ws.h_curr_max.p, R * 8);
-    const uint32_t *h_chain_cnt = ws.h_chain_cnt.p, *h_chain_words = ws.h_chain_words.p, *h_chain_buf = chain_words_host.get();
+    return VGA_OK;
+}
 
-    // ---- chains: discovery order per read, members reversed to ascending (src/chain.rs:546);
-    // a read without chains gets one placeholder (src/chain.rs:644-649)
+// chains: discovery order per read, members reversed to ascending (src/chain.rs:546); a read without chains gets one
+// placeholder (src/chain.rs:644-649).  Then the timings.
+int map_call::assemble()
+{
+    const uint32_t *h_chain_cnt = ws.h_chain_cnt.p, *h_chain_words = ws.h_chain_words.p, *h_chain_buf = chain_words_host.get();
     uint64_t n_chains = 0, n_members = 0;
     std::vector<uint64_t> mem0(R);  // first member slot of each read
     for (uint64_t r = 0; r < R; r++) {
@@ -950,20 +1008,21 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     res->chain_anchor_idx = xmalloc<uint32_t>(n_members);
     if (!res->chain_placeholder || !res->chain_anchor_off || !res->chain_anchor_idx) return nomem();
     res->chain_anchor_off[n_chains] = n_members;
+    vga_map_result *const out = res.p;
     vga_parallel_for(R, [&](uint64_t r) {
-        uint64_t ci = res->chain_off[r], mi = mem0[r];
+        uint64_t ci = out->chain_off[r], mi = mem0[r];
         const uint32_t *buf = h_chain_buf + ws.h_chain_woff.p[r];
         uint32_t c = h_chain_cnt[r], wp = 0;
         if (c == 0) {
-            res->chain_placeholder[ci] = 1;
-            res->chain_anchor_off[ci] = mi;
+            out->chain_placeholder[ci] = 1;
+            out->chain_anchor_off[ci] = mi;
             return;
         }
         for (uint32_t q = 0; q < c; q++) {
             uint32_t len = buf[wp++];
-            res->chain_placeholder[ci] = 0;
-            res->chain_anchor_off[ci] = mi;
-            for (uint32_t t = 0; t < len; t++) res->chain_anchor_idx[mi + t] = buf[wp + len - 1 - t];
+            out->chain_placeholder[ci] = 0;
+            out->chain_anchor_off[ci] = mi;
+            for (uint32_t t = 0; t < len; t++) out->chain_anchor_idx[mi + t] = buf[wp + len - 1 - t];
             wp += len;
             mi += len;
             ci++;
@@ -974,8 +1033,39 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     res->ms_sort = vga_timer_sum(ctx, "anchor_sort");
     res->ms_chain = vga_timer_sum(ctx, "chain_dp");
     res->ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-#undef MAP_CHECK
-    *out = res;
+    return VGA_OK;
+}
+
+}  // namespace
+
+static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_map_result **out)
+{
+    if (!b || !params || !out || !b->ctx) return VGA_ERR_ARG;  // b->ctx == nullptr: the context was destroyed
+    vga_ctx *ctx = b->ctx;
+    *out = nullptr;
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    vga_release_deferred(ctx);  // (buffers of this context that grew during an earlier call: freed now, while it has nothing in flight)
+    int rc = map_validate(ctx, params);
+    if (rc != VGA_OK) return rc;
+    if (!ctx->map_ws) {
+        ctx->map_ws = new map_ws();
+        ctx->map_ws_free = [](void *p) { delete (map_ws *)p; };
+    }
+    vga_timers_reset(ctx);
+    map_call c(b, params, *(map_ws *)ctx->map_ws);
+    if ((rc = c.begin_result()) != VGA_OK) return rc;
+    if (c.R > 0) {
+        if ((rc = c.count()) != VGA_OK) return rc;
+        if ((rc = c.emit_and_sort()) != VGA_OK) return rc;
+        c.chain();
+        if ((rc = c.both ? c.source_picked() : c.source_forward()) != VGA_OK) return rc;
+        if ((rc = c.fetch_counts()) != VGA_OK) return rc;
+        if (c.both && (rc = c.gather_picked()) != VGA_OK) return rc;
+        if ((rc = c.fetch_chains()) != VGA_OK) return rc;
+        if ((rc = c.assemble()) != VGA_OK) return rc;
+    }
+    *out = c.res.release();
     return VGA_OK;
 }
 

@@ -73,7 +73,7 @@ void poa_pool_prepare(vga_ctx *ctx, const poa_switches &sw, uint64_t n_reads, ui
 int poa_pool::measure()
 {
     size_t free_b = 0, total_b = 0;
-    POA_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+    VGA_HIP_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
     uint64_t have;
     { std::lock_guard<std::mutex> lk(W.mu); have = free_b + W.pool_size; }
     have += W.classic_size;
@@ -105,12 +105,12 @@ int poa_pool::obtain_chunks(const poa_probe &pr, hipStream_t st)
     if (ns * state_size > avail / 2 || want < 16 * POA_CHUNK) return VGA_OK;
     if (W.state_bytes < ns * state_size) {
         if (W.state) { (void)hipFree(W.state); W.state = nullptr; W.state_bytes = 0; }
-        POA_CHECK(ctx, hipMalloc((void **)&W.state, ns * state_size));
+        VGA_HIP_CHECK(ctx, hipMalloc((void **)&W.state, ns * state_size));
         W.state_bytes = ns * state_size;
     }
     if (W.classic && want > 0) {  // (memory the classic pool holds is memory the segments cannot have)
         size_t free_b = 0, total_b = 0;
-        POA_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+        VGA_HIP_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
         uint64_t have;
         { std::lock_guard<std::mutex> lk(W.mu); have = W.pool_size; }
         if (have < want && free_b < want - have + (8ull << 30)) { (void)hipFree(W.classic); W.classic = nullptr; W.classic_size = 0; }
@@ -122,7 +122,7 @@ int poa_pool::obtain_chunks(const poa_probe &pr, hipStream_t st)
         W.seg_bytes = std::min<uint64_t>(W.seg_bytes, 1ull << POA_SEG_LOG2);  // (chunks are numbered segment << 12 | chunk in segment)
     }
     tr.mark("pool: state regions");
-    POA_CHECK(ctx, W.ensure_tables((uint32_t)ctx->n_cu));
+    VGA_HIP_CHECK(ctx, W.ensure_tables((uint32_t)ctx->n_cu));
     tr.mark("pool: tables");
     W.request(want);
     // The launches start when the pool holds what their resident workgroups need: on memory that was used before, the driver
@@ -138,8 +138,8 @@ int poa_pool::obtain_chunks(const poa_probe &pr, hipStream_t st)
     // done it -- no stream of this library waits for the null stream, and on a GPU that other contexts keep full the
     // flags were cleared AFTER the first workgroups of slots 1 and 2 had taken their state regions: a second workgroup
     // took the same region, and both problems came back with wrong alignments)
-    POA_CHECK(ctx, hipMemsetAsync(W.d_slot_flag.p, 0, ns * sizeof(uint32_t), st));
-    POA_CHECK(ctx, hipStreamSynchronize(st));
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(W.d_slot_flag.p, 0, ns * sizeof(uint32_t), st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     tr.mark("pool: flags cleared");
     n_arenas = (uint32_t)ns;
     CP.head = W.d_head.p; CP.next = W.d_next_chunk.p; CP.seg_base = W.d_seg_base.p;
@@ -148,9 +148,9 @@ int poa_pool::obtain_chunks(const poa_probe &pr, hipStream_t st)
     CP.short_flag = W.h_short.p;
     if (sw.pool_check) {  // (diagnostics: poa_chunk_pool::owner)
         if (!W.d_owner.p) {
-            POA_CHECK(ctx, W.d_owner.reserve(max_chunks));
-            POA_CHECK(ctx, hipMemsetAsync(W.d_owner.p, 0, W.d_owner.cap * sizeof(uint32_t), st));
-            POA_CHECK(ctx, hipStreamSynchronize(st));
+            VGA_HIP_CHECK(ctx, W.d_owner.reserve(max_chunks));
+            VGA_HIP_CHECK(ctx, hipMemsetAsync(W.d_owner.p, 0, W.d_owner.cap * sizeof(uint32_t), st));
+            VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
         }
         CP.owner = W.d_owner.p;
     }

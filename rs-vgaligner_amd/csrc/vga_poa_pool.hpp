@@ -213,13 +213,6 @@ struct poa_ws {
     }
 };
 
-#define POA_CHECK(ctx, call)                                                                                            \
-    do {                                                                                                                \
-        hipError_t e_ = (call);                                                                                         \
-        if (e_ != hipSuccess)                                                                                           \
-            return vga_set_error(ctx, VGA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // the context's workspace, created on first use
 poa_ws &poa_ws_of(vga_ctx *ctx);
 

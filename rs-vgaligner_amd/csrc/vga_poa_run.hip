@@ -479,8 +479,8 @@ int poa_call::size_pool()
     for (auto &hb : W.text_live) W.text_free.push_back(std::move(hb));
     W.text_live.clear();
     W.join_preparer();
-    POA_CHECK(ctx, W.h_next.reserve(POA_SLOTS));
-    POA_CHECK(ctx, W.d_next.reserve(POA_SLOTS));
+    VGA_HIP_CHECK(ctx, W.h_next.reserve(POA_SLOTS));
+    VGA_HIP_CHECK(ctx, W.d_next.reserve(POA_SLOTS));
     // ---- footprint probe: the first prepared problems (the largest, in launch order)
     probe.n = std::min<uint64_t>(n, 512);
     ensure(0, probe.n);
@@ -529,7 +529,7 @@ int poa_call::size_pool()
     pool.n_slots = n_slots;
     sarr[0] = ctx->stream;
     for (int i = 1; i < n_slots; i++) {
-        if (!W.extra[i]) POA_CHECK(ctx, hipStreamCreateWithFlags(&W.extra[i], hipStreamNonBlocking));
+        if (!W.extra[i]) VGA_HIP_CHECK(ctx, hipStreamCreateWithFlags(&W.extra[i], hipStreamNonBlocking));
         sarr[i] = W.extra[i];
     }
     return VGA_OK;
@@ -1025,7 +1025,7 @@ int poa_call::finish()
     if (rc != VGA_OK) return rc;
     if (rc_final != VGA_OK)
         return vga_set_error(ctx, rc_final, "a single POA problem does not fit the %llu byte traceback pool", (unsigned long long)W.pool_size);
-    POA_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     vga_timers_collect(ctx);
     // byte model of the DP kernel: graph bases + query + 1 direction byte per cell
     // + the value rows kept in HBM (6 B per cell), written once and read back at least once

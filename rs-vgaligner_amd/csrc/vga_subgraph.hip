@@ -1,6 +1,6 @@
 // vga_subgraph.hip -- chain -> subgraph -> POA node table on the GPU, one wave per chain.
 //
-// Stands in for (and is checked against the host walk of vga_align.hip, VGA_SUBGRAPH=host, and the oracle's og_align.c):
+// Stands in for (and is checked against the host walk of vga_subgraph_host.hip, VGA_SUBGRAPH=host, and the oracle's og_align.c):
 //   find_range_chain ............ src/align.rs:267-402   handles of the extreme anchor positions, every node id in between
 //   extend_range_chain_2 ........ src/align.rs:523-665   walk up- / downstream of the range while the unaligned part of the
 //                                                        read still has bases left
@@ -458,14 +458,6 @@ struct sg_ws {
     }
 };
 
-#define SG_CHECK(call)                                                                                                              \
-    do {                                                                                                                            \
-        hipError_t e_ = (call);                                                                                                     \
-        if (e_ != hipSuccess)                                                                                                       \
-            return vga_set_error(ctx, e_ == hipErrorOutOfMemory ? VGA_ERR_NOMEM : VGA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                                                               \
-    } while (0)
-
 // mark + counts, offsets, emit and the copies back for problems [p0, p1) on stream st; waits for them
 int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uint64_t p1, hipStream_t st)
 {
@@ -489,9 +481,9 @@ int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uin
     hipLaunchKernelGGL(k_sg_mark, dim3(waves), dim3(64), 0, st, W.d_desc.p + p0, (uint32_t)n, ix, dix.k, words, nh, W.d_bitmaps.p + p0 * words,
                        W.d_scratch.p, W.d_sum.p + p0);
     vga_timer_end(ctx, t_mark);
-    SG_CHECK(hipGetLastError());
-    SG_CHECK(hipMemcpyAsync(W.h_sum.p + p0, W.d_sum.p + p0, n * sizeof(sg_sum), hipMemcpyDeviceToHost, st));
-    SG_CHECK(hipStreamSynchronize(st));
+    VGA_HIP_CHECK_OOM(ctx, hipGetLastError());
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.h_sum.p + p0, W.d_sum.p + p0, n * sizeof(sg_sum), hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
     uint64_t tn = 0, tp = 0, ts = 0, tq = 0;
     for (uint64_t p = p0; p < p1; p++) {
         const sg_sum &s = W.h_sum.p[p];
@@ -500,22 +492,22 @@ int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uin
         if (s.flags & 1u) continue;
         tn += s.n_nodes; tp += s.n_preds; ts += s.n_sinks; tq += ((uint64_t)s.N + 3) & ~3ull;
     }
-    SG_CHECK(B.d_handles.reserve(tn + 1)); SG_CHECK(B.d_first_row.reserve(tn + 1)); SG_CHECK(B.d_ntab.reserve(tn + n));
-    SG_CHECK(B.d_preds.reserve(tp + 1)); SG_CHECK(B.d_sinks.reserve(ts + 1)); SG_CHECK(B.d_seq.reserve(tq + 4));
-    SG_CHECK(B.h_handles.reserve(tn + 1)); SG_CHECK(B.h_first_row.reserve(tn + 1));
-    SG_CHECK(hipMemcpyAsync(W.d_off.p + p0, W.h_off.p + p0, n * sizeof(sg_off), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, B.d_handles.reserve(tn + 1)); VGA_HIP_CHECK_OOM(ctx, B.d_first_row.reserve(tn + 1)); VGA_HIP_CHECK_OOM(ctx, B.d_ntab.reserve(tn + n));
+    VGA_HIP_CHECK_OOM(ctx, B.d_preds.reserve(tp + 1)); VGA_HIP_CHECK_OOM(ctx, B.d_sinks.reserve(ts + 1)); VGA_HIP_CHECK_OOM(ctx, B.d_seq.reserve(tq + 4));
+    VGA_HIP_CHECK_OOM(ctx, B.h_handles.reserve(tn + 1)); VGA_HIP_CHECK_OOM(ctx, B.h_first_row.reserve(tn + 1));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_off.p + p0, W.h_off.p + p0, n * sizeof(sg_off), hipMemcpyHostToDevice, st));
     int t_emit = vga_timer_begin(ctx, "subgraph_emit", 0, st);
     hipLaunchKernelGGL(k_sg_emit, dim3(waves), dim3(64), 0, st, (uint32_t)n, ix, words, nh, W.d_bitmaps.p + p0 * words, W.d_scratch.p, W.d_sum.p + p0,
                        W.d_off.p + p0, B.d_handles.p, B.d_first_row.p, B.d_ntab.p, B.d_preds.p, B.d_sinks.p, B.d_seq.p,
                        store.remain_rule == VGA_REMAIN_FIRST_OUT_EDGE ? 1 : 0);
     vga_timer_end(ctx, t_emit);
-    SG_CHECK(hipGetLastError());
-    SG_CHECK(hipMemcpyAsync(W.h_sum.p + p0, W.d_sum.p + p0, n * sizeof(sg_sum), hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK_OOM(ctx, hipGetLastError());
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.h_sum.p + p0, W.d_sum.p + p0, n * sizeof(sg_sum), hipMemcpyDeviceToHost, st));
     if (tn) {
-        SG_CHECK(hipMemcpyAsync(B.h_handles.p, B.d_handles.p, tn * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        SG_CHECK(hipMemcpyAsync(B.h_first_row.p, B.d_first_row.p, tn * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(B.h_handles.p, B.d_handles.p, tn * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(B.h_first_row.p, B.d_first_row.p, tn * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
-    SG_CHECK(hipStreamSynchronize(st));
+    VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
     P.d_ntab = B.d_ntab.p; P.d_preds = B.d_preds.p; P.d_sinks = B.d_sinks.p; P.d_seq = B.d_seq.p;
     P.d_handles = B.d_handles.p;
     P.h_handles = B.h_handles.p; P.h_first_row = B.h_first_row.p;
@@ -543,7 +535,7 @@ int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, uint64
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         (void)hi;
-        SG_CHECK(hipStreamCreateWithPriority(&W.side, hipStreamNonBlocking, lo));  // (lowest priority: it must not displace DP workgroups)
+        VGA_HIP_CHECK_OOM(ctx, hipStreamCreateWithPriority(&W.side, hipStreamNonBlocking, lo));  // (lowest priority: it must not displace DP workgroups)
     }
     const vga_dev_index &dix = ctx->index;
     W.nh = 2u * ((uint32_t)dix.n_nodes + 2u);
@@ -553,13 +545,13 @@ int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, uint64
     const uint64_t slab = 5ull * W.nh * sizeof(uint32_t);
     W.waves = std::max<uint64_t>(1, std::min<uint64_t>(waves, (4ull << 30) / slab));
     if (split > n) split = n;
-    SG_CHECK(W.d_desc.reserve(n)); SG_CHECK(W.d_sum.reserve(n)); SG_CHECK(W.d_off.reserve(n));
-    SG_CHECK(W.h_desc.reserve(n)); SG_CHECK(W.h_sum.reserve(n)); SG_CHECK(W.h_off.reserve(n));
-    SG_CHECK(W.d_bitmaps.reserve(n * W.words));
-    SG_CHECK(W.d_scratch.reserve(W.waves * 5ull * W.nh));
+    VGA_HIP_CHECK_OOM(ctx, W.d_desc.reserve(n)); VGA_HIP_CHECK_OOM(ctx, W.d_sum.reserve(n)); VGA_HIP_CHECK_OOM(ctx, W.d_off.reserve(n));
+    VGA_HIP_CHECK_OOM(ctx, W.h_desc.reserve(n)); VGA_HIP_CHECK_OOM(ctx, W.h_sum.reserve(n)); VGA_HIP_CHECK_OOM(ctx, W.h_off.reserve(n));
+    VGA_HIP_CHECK_OOM(ctx, W.d_bitmaps.reserve(n * W.words));
+    VGA_HIP_CHECK_OOM(ctx, W.d_scratch.reserve(W.waves * 5ull * W.nh));
     memcpy(W.h_desc.p, descs, n * sizeof(sg_desc));
     W.q_src.assign(q_src, q_src + n);
-    SG_CHECK(hipMemcpyAsync(W.d_desc.p, W.h_desc.p, n * sizeof(sg_desc), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_desc.p, W.h_desc.p, n * sizeof(sg_desc), hipMemcpyHostToDevice, st));
     store.n = n;
     store.split = split;
     store.sum = W.h_sum.p; store.off = W.h_off.p; store.d_off = W.d_off.p;

@@ -7,34 +7,7 @@
 #include <cstdint>
 
 #include "vga_common.hpp"
-
-// one chain, as the host hands it over (the extremes of its anchors; the reduction over the anchors is the one the launch
-// order needs anyway)
-struct sg_desc {
-    uint32_t pmin, pmax;        // smallest / largest forward position among the anchors' begins and inclusive ends
-    uint32_t q_first, t_first;  // first anchor: query_begin, target_begin
-    uint32_t q_last, te_last;   // last anchor: query_begin, target_end (exclusive)
-    uint32_t qlen, pad;
-};
-
-// what the kernels report per problem
-struct sg_sum {
-    uint32_t n_nodes;  // handles of the subgraph
-    uint32_t N;        // rows = graph bases
-    uint32_t n_preds, n_sinks;
-    uint32_t wlo, whi;  // words of the handle bitmap that hold set bits
-    uint32_t longest;   // `remain` of the virtual source: graph bases on the source-sink path the remain rule follows
-    uint32_t life;      // largest edge span (in nodes) among the nodes that use the value-row ring
-    uint32_t flags;     // bit 0: malformed for the POA kernels (in-degree > 255, too many rows)
-    uint32_t pad[3];
-};
-
-// where a problem's pieces live in the store
-struct sg_off {
-    uint64_t node0;  // handles / first_row: node0 .. node0 + n_nodes;  node table: node0 + problem index (one source entry each)
-    uint64_t pred0, sink0, seq0;
-    uint64_t q_src;  // first base of the query in the batch's device copy of the reads
-};
+#include "vga_sg_records.hpp"  // sg_desc, sg_sum, sg_off
 
 // The prepared problems of one vga_align_batch call (device store + what the host needs of it).  The problems come in
 // launch order and are prepared in two parts: [0, split) before the first DP launch, [split, n) beside it on a stream
