@@ -35,6 +35,15 @@ rng = random.Random(77 + seed_off)
 probs = [T._rand_problem(rng, rng.randint(5, 60), 12) for _ in range(400)]
 T._check_poa(o, ctx, probs)
 print("400 random POA problems ok", flush=True)
+# the wider family of tests/poa_topologies.py: in-degree up to 12, edges that reach up to 80 nodes, several sources and sinks
+import poa_topologies
+wrng = random.Random(177 + seed_off)  # (a stream of its own: the reads below stay what they were)
+wide = [poa_topologies.rand_dag_problem(wrng, wrng.randint(5, 160), wrng.choice((3, 6, 12, 40))) for _ in range(300)]
+for rule in (0, 1):
+    pp, op = p.default_poa_params(), o.default_poa_params()
+    pp.remain_rule = op.remain_rule = rule
+    T._check_poa(o, ctx, wide, pp, op)
+print(len(wide), "random DAGs of in-degree <= 12 and reach <= 80 ok under both remain rules", flush=True)
 
 # chimeric / rearranged reads: a stretch of random bases, a large deletion or a large duplication inside a real read --
 # chains that cover part of the read, long extensions, rows that span the whole query, alignments with negative scores
