@@ -24,7 +24,9 @@
 // on the device.  Numerics are 32-bit integer and bit-exact against oracle/og_poa.c (see its header for the
 // specification: recurrences, tie order, band rule).
 //
-// This file holds every POA kernel and one typed launcher per kernel group (vga_poa_launch.hpp).  The host side lives apart and
+// This file holds every POA kernel and one typed launcher per kernel group (vga_poa_launch.hpp): k_poa_dp_lds and the traceback in
+// vga_poa_kernels.hpp, k_poa_dp_t4 ... _t7 in vga_poa_t4.hpp ... vga_poa_t7.hpp, and in vga_poa_row.hpp the instruction helpers
+// they share and the row that k_poa_dp_t6 and k_poa_dp_t7 have in common.  The host side lives apart and
 // includes no kernel header: vga_poa_run.hip (poa_run -- plan, pool, launch, collect -- and vga_poa_batch), vga_poa_pool.hip (the
 // traceback pool), vga_poa_shape.hpp (environment switches, kernel family, launch shape).
 #include "vga_common.hpp"

@@ -4,7 +4,7 @@
 // records are in vga_poa_launch.hpp (the host code reads them too), the LDS sizes in vga_poa_shape.hpp.
 #pragma once
 
-#define POA_NEG (-(1 << 21))  // "minus infinity"; H stays inside 23 signed bits (see k_poa_dp_pk)
+#define POA_NEG (-(1 << 21))  // "minus infinity"; H stays inside 23 signed bits
 #define POA_IDENT (INT32_MIN / 2)
 #define POA_RF_FIRST 1u    // first base of a node (other than the source)
 #define POA_RF_LAST 2u     // last base of a node
@@ -30,7 +30,7 @@
 //        lane parks in `edge` before the barrier.
 //      * Rows with a predecessor that is not the row directly above (bubble arms, multi-predecessor rows) read
 //        that predecessor's value row from HBM; such a row starts with a full __syncthreads() (vmcnt(0)).
-// -DPOA_MARKERS puts region markers into the ISA (tests/isa_regions.py counts instructions between them)
+// -DPOA_MARKERS puts region markers into the ISA (tests/isa_stats.py counts instructions between them)
 #ifdef POA_MARKERS
 #define POA_MARK(name) asm volatile("; MARK " name)
 #else

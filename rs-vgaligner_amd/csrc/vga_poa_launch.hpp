@@ -30,8 +30,8 @@ struct poa_prob {
     uint32_t N;
     uint32_t w;      // adaptive band half-width: wb + floor(wf * qlen), computed on the host in double
     uint32_t n_nodes;  // node-table entries incl. the source
-    uint32_t ring_rows;  // value rows of node-end rows live in a ring of this many worst-case rows (k_poa_dp_pk)
-    uint32_t flags;      // bit 0: too large for an arena (k_poa_dp_pk in arena mode reports POA_ST_POOL at once)
+    uint32_t ring_rows;  // value rows of node-end rows live in a ring of this many worst-case rows
+    uint32_t flags;      // bit 0: too large for an arena (reported as POA_ST_POOL at once)
     uint32_t pad;
 };
 
@@ -39,12 +39,10 @@ struct poa_row {          // per DP row, 48 B
     int32_t beg, end;     // band
     uint64_t doff, voff;  // direction row / value row in the pool
     int32_t lmax, rmax;   // leftmost / rightmost column of the row maximum
-    // the last four words form one aligned 16-byte group: k_poa_rowprep fills them for k_poa_dp_w1, which reads them with a
-    // single scalar load per row
+    // the last four words form one aligned 16-byte group
     uint32_t pred, npred; // predecessor row or predecessor-list slice; npred != 0 only on the first row of a node
-    int32_t base, hmax;   // k_poa_dp_pk<.., H16>: the row's values are stored relative to `base`, hmax = the row maximum.
-                          // k_poa_dp_w1: base = graph bases after this row on the longest path to the sink ("remain"),
-                          // hmax = static flags of the row (POA_RF_*), both written by k_poa_rowprep
+    int32_t base, hmax;   // base: k_poa_dp_t5 marks the rows whose value row is kept (its epilogue counts their cells), k_poa_dp_t4
+                          // writes 0; hmax: unused
 };
 static_assert(sizeof(poa_row) == 48 && offsetof(poa_row, pred) == 32, "poa_row layout");
 

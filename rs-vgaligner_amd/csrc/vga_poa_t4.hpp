@@ -1,7 +1,7 @@
-// vga_poa_t4.hpp -- K4 "t4": the banded POA DP of k_poa_dp_pk (same algorithm, same outputs, bit-exact against
+// vga_poa_t4.hpp -- K4 "t4": the banded POA DP of k_poa_dp_lds (same algorithm, same outputs, bit-exact against
 // oracle/og_poa.c) re-formulated for fewer VALU instructions per cell.  gfx950 issues the instruction kinds this kernel
 // is made of at one wave64 instruction per ~4 cycles per SIMD whatever the mix (profiles/r02_valu_issue_microbench.txt),
-// so the instruction count is the only lever.  What changed against k_poa_dp_pk:
+// so the instruction count is the only lever.  What changed against k_poa_dp_lds:
 //   * every score is carried SCALED BY 4; the two free low bits hold an argmax TAG at the two places a maximum of three
 //     candidates is taken:   Ht' = max3(4M + 2, 4E1 + 1, 4E2 + 0),   H'' = max3(4Ht + 3, 4F1 + 1, 4F2 + 0).
 //     One v_max3_i32 yields the value (bits 31..2) and, with the spec's tie order M > E1 > E2 and Ht > F1 > F2, the
@@ -19,63 +19,11 @@
 // Direction byte (ENC 1 of poa_traceback_*):  [7:6] tag of H'' (3 Ht, 1 F1, 0 F2), [5:4] tag of Ht' (2 M, 1 E1, 0 E2),
 // [3] E1 of a successor opens from this cell, [2] same for E2, [1] F1 of this cell did NOT open at j-1, [0] same for F2.
 // Value rows in HBM (node-end rows, rows wider than the LDS window): int32 4H plane [W] then uint16 G plane [W].
-// Limits (the host falls back to k_poa_dp_pk / k_poa_dp_lds otherwise): 4 (o1+e1) - 1 <= 255, 4 (o2+e2) <= 255, e1 >= 1,
+// Limits (the host falls back to k_poa_dp_lds otherwise): 4 (o1+e1) - 1 <= 255, 4 (o2+e2) <= 255, e1 >= 1,
 // match + mismatch >= 0.
 #pragma once
 
-#define T4_NEG (4 * POA_NEG)
-
-template <int B>
-__device__ __forceinline__ int t4_sub_byte(int a, int g)  // a - byte B of g
-{
-    int r;
-    if constexpr (B == 0) asm("v_sub_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(a), "v"(g));
-    if constexpr (B == 1) asm("v_sub_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(a), "v"(g));
-    if constexpr (B == 2) asm("v_sub_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(a), "v"(g));
-    if constexpr (B == 3) asm("v_sub_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(a), "v"(g));
-    return r;
-}
-// byte B of dst = min(t, c) (unsigned; c <= 255), and  acc = 2 acc + (t >= c)
-template <int B>
-__device__ __forceinline__ void t4_gap_byte(int &dst, int &acc, int t, int c)
-{
-    if constexpr (B == 0) asm("v_min_u32_sdwa %0, %2, %3 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\tv_cmp_le_u32 vcc, %3, %2\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc" : "+v"(dst), "+v"(acc) : "v"(t), "s"(c) : "vcc");
-    if constexpr (B == 1) asm("v_min_u32_sdwa %0, %2, %3 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\tv_cmp_le_u32 vcc, %3, %2\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc" : "+v"(dst), "+v"(acc) : "v"(t), "s"(c) : "vcc");
-    if constexpr (B == 2) asm("v_min_u32_sdwa %0, %2, %3 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\tv_cmp_le_u32 vcc, %3, %2\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc" : "+v"(dst), "+v"(acc) : "v"(t), "s"(c) : "vcc");
-    if constexpr (B == 3) asm("v_min_u32_sdwa %0, %2, %3 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\tv_cmp_le_u32 vcc, %3, %2\n\tv_addc_co_u32 %1, vcc, %1, %1, vcc" : "+v"(dst), "+v"(acc) : "v"(t), "s"(c) : "vcc");
-}
-__device__ __forceinline__ void t4_flag_ne(int &acc, int a, int b)  // acc = 2 acc + (a != b)
-{
-    asm("v_cmp_ne_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
-}
-// byte B of dst = low byte of (2 acc + (a != b))
-template <int B>
-__device__ __forceinline__ void t4_flag_ne_dep(int &dst, int acc, int a, int b)
-{
-    if constexpr (B == 0) asm("v_cmp_ne_u32 vcc, %2, %3\n\tv_addc_co_u32_sdwa %0, vcc, %1, %1, vcc dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(acc), "v"(a), "v"(b) : "vcc");
-    if constexpr (B == 1) asm("v_cmp_ne_u32 vcc, %2, %3\n\tv_addc_co_u32_sdwa %0, vcc, %1, %1, vcc dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(acc), "v"(a), "v"(b) : "vcc");
-    if constexpr (B == 2) asm("v_cmp_ne_u32 vcc, %2, %3\n\tv_addc_co_u32_sdwa %0, vcc, %1, %1, vcc dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(acc), "v"(a), "v"(b) : "vcc");
-    if constexpr (B == 3) asm("v_cmp_ne_u32 vcc, %2, %3\n\tv_addc_co_u32_sdwa %0, vcc, %1, %1, vcc dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(acc), "v"(a), "v"(b) : "vcc");
-}
-__device__ __forceinline__ int t4_max3(int a, int b, int c)
-{
-    int r;
-    asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// lanes 1..63: max(v of the lane below, pre); lane 0: pre   (wave_shr:1, bound_ctrl off: lane 0 keeps the old value)
-__device__ __forceinline__ int t4_shr1_max(int v, int pre)
-{
-    int r = pre;
-    asm("s_nop 1\n\tv_max_i32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(r) : "v"(v), "v"(pre));  // (s_nop: the compiler does not see that %1 is read through DPP)
-    return r;
-}
-__device__ __forceinline__ int t4_shr1_mov(int v, int first)  // lanes 1..63: v of the lane below; lane 0: first
-{
-    int r = first;
-    asm("s_nop 1\n\tv_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(r) : "v"(v));
-    return r;
-}
+#include "vga_poa_row.hpp"
 
 template <int NT, bool DEF>
 __global__ __launch_bounds__(NT, 4) void k_poa_dp_t4(
@@ -109,7 +57,7 @@ __global__ __launch_bounds__(NT, 4) void k_poa_dp_t4(
     const uint32_t *plist = preds + pb.pred0;
     poa_row *R = rows + pb.row0;
 
-    // ---- pool: classic (chunks of the launch's segment) or arena mode, as in k_poa_dp_pk
+    // ---- pool: classic (chunks of the launch's segment) or arena mode, as in k_poa_dp_lds
     uint8_t *pool = pool_arg;
     unsigned long long *pool_next = pool_next_arg;
     uint64_t pool_size = pool_size_arg;
@@ -406,7 +354,7 @@ __global__ __launch_bounds__(NT, 4) void k_poa_dp_t4(
             for (int k = 0; k < 4; k++) { htt[k] = T4_NEG + 2; ht4[k] = T4_NEG; e1t[k] = T4_NEG + 1; e2t[k] = T4_NEG; pmeta[k] = 0; }
             uint32_t qn = 0u;
             if (wave_act) qn = (uint32_t)Qn[j0 >> 2];
-            // the mask-free path and its edge patches (lp / rp / lq): see k_poa_dp_pk
+            // the mask-free path and its edge patches (lp / rp / lq): see k_poa_dp_lds
             const int jw0 = bal + c0 + 256 * wv, jw1 = jw0 + 255;
             const bool lp = jw0 < beg;
             const bool rp = jw1 > end || jw1 > pend;

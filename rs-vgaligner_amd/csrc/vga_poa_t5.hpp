@@ -19,30 +19,12 @@
 // are those of k_poa_dp_t4, so the two kernels are interchangeable problem by problem (VGA_POA_KERNEL=t4 selects the old one).
 #pragma once
 
-// byte B of dst = min(t, c)   (unsigned; c <= 255)
-template <int B>
-__device__ __forceinline__ void t5_min_byte(int &dst, int t, int c)
-{
-    if constexpr (B == 0) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(t), "s"(c));
-    if constexpr (B == 1) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(t), "s"(c));
-    if constexpr (B == 2) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(t), "s"(c));
-    if constexpr (B == 3) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(dst) : "v"(t), "s"(c));
-}
+#include "vga_poa_row.hpp"
+
 __device__ __forceinline__ uint64_t t5_uniform64(uint64_t v)
 {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-
-// a scalar of its own: cuts a uniform value loose from the (wide) load that produced it
-__device__ __forceinline__ int t5_own(int v)
-{
-    asm volatile("" : "+v"(v));  // (through a vector register: the prologue can afford it, and nothing can be folded away)
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint32_t t5_own(uint32_t v) { return (uint32_t)t5_own((int)v); }
-__device__ __forceinline__ uint64_t t5_own(uint64_t v) { return ((uint64_t)t5_own((uint32_t)(v >> 32)) << 32) | t5_own((uint32_t)v); }
-template <typename T>
-__device__ __forceinline__ T *t5_own(T *p) { return (T *)t5_own((uint64_t)p); }
 
 // (the read-only inputs stay kernel parameters of their own: only a __restrict__ PARAMETER tells the compiler that no store of
 // the kernel can change them, which is what lets their loads be scalar loads)
