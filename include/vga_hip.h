@@ -323,6 +323,48 @@ int vga_coverage_read(vga_ctx *ctx, uint32_t *base_depth /* seq_length */, uint3
 int vga_coverage_reset(vga_ctx *ctx);
 int vga_coverage_end(vga_ctx *ctx);
 
+/* ---- path support: how well every reported alignment fits every haplotype path (P line) of the graph ----------
+ * Stands in for nothing in the reference, whose map.rs ends at the GAF writer: it is the input of allele typing, a reads x
+ * paths table computed while the alignments are still on the GPU.  It is defined on the text of the alignments GAF plus the
+ * GFA's S and P lines and on nothing else (tests/path_support_ref.py recomputes it from them).  For the record vga_align_batch
+ * reports for read r (path >w0>w1.., path_start, cs) and path p (steps "id+" / "id-"):
+ *   bases[r][p]  graph bases under r's M operations (cs ":N" and "*gq": coverage's notion of covered) that lie in a node p
+ *                visits as "id+".  A node p visits twice counts once; an "id-" step sets nothing.
+ *   edges[r][p]  consecutive pairs (w_i, w_i+1) of r's path for which p has the step w_i+ immediately followed by w_i+1+
+ *                (bases alone cannot tell an allele from its deletion variant, whose nodes are a subset).
+ *   top paths of r: the paths whose key (bases, edges) is the lexicographic maximum, unless that maximum is (0, 0).
+ * A read with a placeholder record has a zero row and adds nothing.  With VGA_STRANDS_BOTH a '-' record carries the forward
+ * path, so the same rule applies.  Per path, accumulated over calls like coverage (64-bit, exact, order-independent):
+ *   sum_bases[p], sum_edges[p]; top[p]: alignments with p among their top paths; top_alone[p]: alignments whose only top path
+ *   is p; and the scalars n_alignments and n_unplaced (alignments whose keys are all (0, 0)).
+ * The state belongs to the context's index: uploading or building another index drops it and turns path support off.
+ *   vga_path_support_begin  needs an index (VGA_ERR_NO_INDEX).  steps[step_off[p] .. step_off[p+1]) are the packed handles
+ *                           (id << 1 | is_reverse) of path p.  VGA_ERR_ARG: n_paths == 0, a step_off that decreases, a handle
+ *                           whose id is outside 1..n_nodes.  VGA_ERR_UNSUPPORTED: more than 4096 paths.  A step pair "a+,b+"
+ *                           without an edge a -> b in the index (no L line) can never match a record and sets nothing;
+ *                           *n_pairs_without_edge (may be NULL) says how many there were.  Every later vga_align_batch on ctx
+ *                           scores its reported alignments; VGA_SUBGRAPH=host is refused by it while path support is on.  A
+ *                           second begin starts over with the new paths.
+ *   vga_path_support_read   the accumulators, n_paths values each; any pointer may be NULL; does not reset.
+ *   vga_path_support_last   the n_reads x n_paths matrices (row-major) of the most recent vga_align_batch on ctx; either may
+ *                           be NULL.  VGA_ERR_ARG if n_reads is not that batch's or there has been none since begin.
+ *   vga_path_support_reset  zero the accumulators, stay on.        vga_path_support_end  free, turn off.
+ *   vga_path_support_lists  the kernel seam, as vga_poa_batch is for POA: scores n explicit lists -- node ids in path order
+ *                           (list i: node_ids[node_off[i] .. node_off[i+1])) and, per node, how many of its bases are covered
+ *                           (at most its length, VGA_ERR_ARG otherwise) -- through the same kernel into bases_out / edges_out
+ *                           (n x n_paths), and does not touch the accumulators.  A pair that is no edge of the index scores 0.
+ * read, last, reset and lists return VGA_ERR_ARG while path support is off.  With it off vga_align_batch does what it did
+ * before these calls existed: no extra launch, no extra allocation. */
+int vga_path_support_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off /* n_paths + 1 */, const uint64_t *steps,
+                           uint64_t *n_pairs_without_edge);
+int vga_path_support_read(vga_ctx *ctx, uint64_t *sum_bases, uint64_t *sum_edges, uint64_t *top, uint64_t *top_alone,
+                          uint64_t *n_alignments, uint64_t *n_unplaced);
+int vga_path_support_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *bases, uint32_t *edges);
+int vga_path_support_reset(vga_ctx *ctx);
+int vga_path_support_end(vga_ctx *ctx);
+int vga_path_support_lists(vga_ctx *ctx, uint64_t n, const uint64_t *node_off /* n + 1 */, const uint32_t *node_ids,
+                           const uint32_t *node_bases, uint32_t *bases_out, uint32_t *edges_out);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "vga_align_prepare", "vga_ctx_set_pool_fraction", "vga_ctx_set_host_threads",
     "vga_index_build_kmers", "vga_index_kmers_free",
     "vga_coverage_begin", "vga_coverage_read", "vga_coverage_reset", "vga_coverage_end",
+    "vga_path_support_begin", "vga_path_support_read", "vga_path_support_last", "vga_path_support_reset", "vga_path_support_end",
+    "vga_path_support_lists",
 ]
 
 
@@ -165,6 +167,17 @@ def load_library():
             getattr(L, name).restype = C.c_int
         L.vga_coverage_read.argtypes = [vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint64)]
         L.vga_coverage_read.restype = C.c_int
+    if hasattr(L, "vga_path_support_begin"):  # (absent from an older build named by VGA_LIB; the Context.path_support_* calls then fail)
+        u64p, u32p = _P(C.c_uint64), _P(C.c_uint32)
+        L.vga_path_support_begin.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
+        L.vga_path_support_read.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, u64p]
+        L.vga_path_support_last.argtypes = [vp, C.c_uint64, u32p, u32p]
+        L.vga_path_support_reset.argtypes = [vp]
+        L.vga_path_support_end.argtypes = [vp]
+        L.vga_path_support_lists.argtypes = [vp, C.c_uint64, u64p, u32p, u32p, u32p, u32p]
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_path_support_"):
+                getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -348,6 +361,7 @@ class Batch:
         p = params or default_poa_params()
         out = _P(AlignResult)()
         self.ctx._check(L.vga_align_batch(self.h, chains._ptr, best_n, C.byref(p), C.byref(out)))
+        self.ctx._last_reads = len(self.seqs)
         return AlignOut(L, out)
 
     def map_raw(self, map_params: Optional[MapParams] = None, on_results=None) -> dict:
@@ -395,6 +409,7 @@ class Batch:
         try:
             a = _P(AlignResult)()
             self.ctx._check(L.vga_align_batch(self.h, m, best_n, C.byref(pp), C.byref(a)))
+            self.ctx._last_reads = len(self.seqs)
             t2 = _t.perf_counter()
             kt_aln = self.ctx.kernel_times()
             r, q = a.contents, m.contents
@@ -443,6 +458,8 @@ class Context:
         self.h = h
         self._keep = None
         self._dims = None  # (seq_length, n_nodes, n_edges) of the index this context holds
+        self._n_paths = 0  # paths of the last path_support_begin
+        self._last_reads = 0  # reads of the last Batch.align
 
     def _check(self, rc: int):
         if rc != VGA_OK:
@@ -548,6 +565,61 @@ class Context:
     def coverage_end(self) -> None:
         """vga_coverage_end: free the tables, stop counting"""
         self._check(self.L.vga_coverage_end(self.h))
+
+    def path_support_begin(self, step_off, steps) -> int:
+        """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path
+        (hostlib.gfa_paths).  From now on every align() of this context scores its reported alignments against the paths.
+        Returns the number of forward step pairs that are no edge of the index."""
+        off = np.ascontiguousarray(step_off, dtype=np.uint64)
+        st = np.ascontiguousarray(steps, dtype=np.uint64)
+        if len(st) == 0:
+            st = np.zeros(1, dtype=np.uint64)
+        missing = C.c_uint64(0)
+        self._n_paths = 0
+        self._check(self.L.vga_path_support_begin(self.h, max(0, len(off) - 1), _u64p(off), _u64p(st), C.byref(missing)))
+        self._n_paths = len(off) - 1
+        return int(missing.value)
+
+    def path_support(self) -> dict:
+        """vga_path_support_read -> {sum_bases, sum_edges, top, top_alone: uint64[n_paths], n_alignments, n_unplaced}; does not reset"""
+        a = [np.zeros(max(1, self._n_paths), dtype=np.uint64) for _ in range(4)]
+        n, un = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_path_support_read(self.h, _u64p(a[0]), _u64p(a[1]), _u64p(a[2]), _u64p(a[3]), C.byref(n), C.byref(un)))
+        out = {k: v[:self._n_paths] for k, v in zip(("sum_bases", "sum_edges", "top", "top_alone"), a)}
+        out.update(n_alignments=int(n.value), n_unplaced=int(un.value))
+        return out
+
+    def path_support_last(self, n_reads: Optional[int] = None):
+        """vga_path_support_last -> (bases, edges), uint32[n_reads, n_paths] of the most recent align() of this context"""
+        n = self._last_reads if n_reads is None else int(n_reads)
+        b, e = (np.zeros((max(1, n), max(1, self._n_paths)), dtype=np.uint32) for _ in range(2))
+        self._check(self.L.vga_path_support_last(self.h, n, _u32p(b), _u32p(e)))
+        shape = (n, self._n_paths)
+        return b.ravel()[:n * self._n_paths].reshape(shape), e.ravel()[:n * self._n_paths].reshape(shape)
+
+    def path_support_reset(self) -> None:
+        """vga_path_support_reset: zero the accumulators, keep scoring"""
+        self._check(self.L.vga_path_support_reset(self.h))
+
+    def path_support_end(self) -> None:
+        """vga_path_support_end: free the state, stop scoring"""
+        self._check(self.L.vga_path_support_end(self.h))
+        self._n_paths = 0
+
+    def path_support_lists(self, lists, bases):
+        """vga_path_support_lists, the kernel seam: lists[i] the node ids of list i in path order, bases[i] the covered bases of
+        each of them -> (bases, edges), uint32[len(lists), n_paths]; the accumulators are not touched"""
+        n = len(lists)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        for i, l in enumerate(lists):
+            assert len(l) == len(bases[i])
+            off[i + 1] = off[i] + len(l)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.uint32) for l in lists] + [np.zeros(1, np.uint32)]))
+        nb = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.uint32) for l in bases] + [np.zeros(1, np.uint32)]))
+        b, e = (np.zeros(max(1, n * self._n_paths), dtype=np.uint32) for _ in range(2))
+        self._check(self.L.vga_path_support_lists(self.h, n, _u64p(off), _u32p(ids), _u32p(nb), _u32p(b), _u32p(e)))
+        shape = (n, self._n_paths)
+        return b[:n * self._n_paths].reshape(shape), e[:n * self._n_paths].reshape(shape)
 
     def chain_paths_text(self, chains: "MapOut") -> List[bytes]:
         """the path column of every chain's GAF record (vga_chain_paths_text), one bytes object per chain"""

@@ -14,6 +14,7 @@
 #include "vga_align_plan.hpp"
 #include "vga_common.hpp"
 #include "vga_coverage.hpp"
+#include "vga_path_support.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_subgraph_host.hpp"
 
@@ -45,7 +46,9 @@ struct align_call {
     const bool on_device = !sw.sg_host;
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     vga_trace tr{"align"};
+    cov_state *const lists;  // the run lists of the problems are kept: coverage or path support is on
     cov_state *const cov;
+    ps_state *const ps;
     // ---- plan (vga_align_plan.hpp); the per-problem arrays are in launch order on the device route, in list order on the host's
     std::vector<uint64_t> prob_read, prob_chain, read_prob0;
     std::vector<uint32_t> slot_of;  // where the q-th (read, chain) pair of the selection sits among the problems
@@ -69,7 +72,8 @@ struct align_call {
     vga_result_guard<vga_align_result, vga_align_result_free> res;
 
     align_call(vga_batch *batch, const vga_map_result *chains, uint32_t best_n, const vga_poa_params *p)
-        : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), cov(cov_active(batch->ctx)) {}
+        : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), lists(cov_lists_active(batch->ctx)), cov(cov_active(batch->ctx)),
+          ps(ps_active(batch->ctx)) {}
 
     uint32_t qlen(uint64_t r) const { return (uint32_t)(b->read_off[r + 1] - b->read_off[r]); }
     // VGA_STRANDS_BOTH: a read whose chains came from its reverse complement is aligned as that sequence
@@ -85,7 +89,7 @@ struct align_call {
     int run_poa();
     int begin_result();
     void pick_winners();
-    int count_coverage();
+    int count_winners();
     int fill_result();
 };
 
@@ -113,6 +117,9 @@ int align_call::plan()
     if (cov && !on_device)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
                              "vga_align_batch: read coverage is not counted under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
+    if (ps && !on_device)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                             "vga_align_batch: path support is not scored under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
     align_select(m, align_best_n, prob_read, prob_chain, read_prob0);
     n = prob_read.size();
     proxy.resize(n);
@@ -262,15 +269,23 @@ void align_call::pick_winners()
     });
 }
 
-// coverage counts the reported record of every read and nothing else
-int align_call::count_coverage()
+// coverage and path support count the reported record of every read and nothing else
+int align_call::count_winners()
 {
-    std::vector<uint32_t> winners;
+    std::vector<uint32_t> winners, reads;
     for (uint64_t r = 0; r < R; r++)
-        if (pick[r] >= 0) winners.push_back((uint32_t)pick[r]);
-    const int rc = cov_add_winners(ctx, cov, winners);
+        if (pick[r] >= 0) { winners.push_back((uint32_t)pick[r]); reads.push_back((uint32_t)r); }
+    cov_win_view v;
+    int rc = cov_stage_winners(ctx, lists, winners, v);
     if (rc != VGA_OK) return rc;
-    tr.mark("coverage");
+    if (cov) {
+        if ((rc = cov_add_winners(ctx, cov, winners.size())) != VGA_OK) return rc;
+        tr.mark("coverage");
+    }
+    if (ps) {
+        if ((rc = ps_score_winners(ctx, ps, v, reads, R)) != VGA_OK) return rc;
+        tr.mark("path support");
+    }
     return VGA_OK;
 }
 
@@ -357,7 +372,7 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     if ((rc = c.run_poa()) != VGA_OK) return rc;
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     c.pick_winners();
-    if (c.cov && (rc = c.count_coverage()) != VGA_OK) return rc;
+    if (c.lists && (rc = c.count_winners()) != VGA_OK) return rc;
     if ((rc = c.fill_result()) != VGA_OK) return rc;
     *out = c.res.release();
     return VGA_OK;

@@ -56,9 +56,12 @@ struct vga_dev_index {
     std::vector<uint32_t> edges_to;    // n_nodes+1
     std::vector<uint32_t> edges;       // packed handles
     bool loaded = false;
-    // read coverage counters of this index while counting is on (vga_coverage.hip): released with the index
+    // run lists and read coverage counters of this index while coverage or path support is on (vga_coverage.hip): released with the index
     void *cov = nullptr;
     void (*cov_free)(void *) = nullptr;
+    // path support of this index while it is on (vga_path_support.hip): the path bitsets and the accumulators, released with the index
+    void *ps = nullptr;
+    void (*ps_free)(void *) = nullptr;
 };
 
 struct vga_timer_entry {

@@ -198,6 +198,7 @@ __global__ __launch_bounds__(1024) void k_cov_depth(const uint32_t *__restrict__
 // The counters of a context's index while counting is on (vga_dev_index::cov: released with the index), and the lists of the
 // vga_align_batch call in progress.
 struct cov_state {
+    uint32_t users = 0;  // COV_USER_*: who reads the lists (the counters below exist while COV_USER_COVERAGE is among them)
     uint32_t seq_length = 0, n_nodes = 0, n_edges = 0;
     vga_dbuf<uint32_t> d_diff, d_node, d_edge, d_depth;
     uint64_t n_alignments = 0;
@@ -214,7 +215,42 @@ struct cov_state {
     vga_hbuf<cov_rec> h_win;
 };
 
-cov_state *cov_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (cov_state *)ctx->index.cov : nullptr; }
+cov_state *cov_lists_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (cov_state *)ctx->index.cov : nullptr; }
+cov_state *cov_active(vga_ctx *ctx)
+{
+    cov_state *cv = cov_lists_active(ctx);
+    return cv && (cv->users & COV_USER_COVERAGE) ? cv : nullptr;
+}
+
+static void cov_release(vga_ctx *ctx)
+{
+    if (ctx->index.cov && ctx->index.cov_free) ctx->index.cov_free(ctx->index.cov);
+    ctx->index.cov = nullptr;
+    ctx->index.cov_free = nullptr;
+}
+
+int cov_lists_acquire(vga_ctx *ctx, uint32_t user, const char *who)
+{
+    try {
+        if (!ctx->index.cov) {
+            ctx->index.cov = new cov_state();
+            ctx->index.cov_free = [](void *q) { delete (cov_state *)q; };
+        }
+    } catch (const std::bad_alloc &) {
+        return vga_set_error(ctx, VGA_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    ((cov_state *)ctx->index.cov)->users |= user;
+    return VGA_OK;
+}
+
+void cov_lists_release(vga_ctx *ctx, uint32_t user)
+{
+    cov_state *cv = (cov_state *)ctx->index.cov;
+    if (!cv) return;
+    cv->users &= ~user;
+    if (!cv->users) { cov_release(ctx); return; }
+    if (user == COV_USER_COVERAGE) { cv->d_diff.release(); cv->d_node.release(); cv->d_edge.release(); cv->d_depth.release(); }
+}
 
 int cov_call_begin(vga_ctx *ctx, cov_state *cv, uint64_t n, uint64_t total_q)
 {
@@ -288,9 +324,10 @@ void cov_keep_from_ops(cov_state *cv, uint32_t p, const uint8_t *ops, const uint
     cv->recs[p] = rc;
 }
 
-int cov_add_winners(vga_ctx *ctx, cov_state *cv, const std::vector<uint32_t> &winners)
+int cov_stage_winners(vga_ctx *ctx, cov_state *cv, const std::vector<uint32_t> &winners, cov_win_view &v)
 {
     const size_t nw = winners.size();
+    v = cov_win_view{nullptr, nullptr, nullptr};
     if (nw == 0) return VGA_OK;
     VGA_HIP_CHECK(ctx, cv->h_win.reserve(nw));
     VGA_HIP_CHECK(ctx, cv->d_win.reserve(nw));
@@ -305,6 +342,14 @@ int cov_add_winners(vga_ctx *ctx, cov_state *cv, const std::vector<uint32_t> &wi
     if (!cv->host_lists.empty())
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(cv->d_host_lists.p, cv->host_lists.data(), cv->host_lists.size() * 4, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(cv->d_win.p, cv->h_win.p, nw * sizeof(cov_rec), hipMemcpyHostToDevice, st));
+    v = cov_win_view{cv->d_win.p, cv->d_lists.p, cv->d_host_lists.p};
+    return VGA_OK;
+}
+
+int cov_add_winners(vga_ctx *ctx, cov_state *cv, size_t nw)
+{
+    if (nw == 0) return VGA_OK;
+    hipStream_t st = ctx->stream;
     const vga_dev_index &ix = ctx->index;
     const int t = vga_timer_begin(ctx, "k_cov_add", 0, st);
     hipLaunchKernelGGL(k_cov_add, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, cv->d_win.p, cv->d_lists.p, cv->d_host_lists.p, ix.d_edge_idx,
@@ -328,13 +373,6 @@ static int cov_zero(vga_ctx *ctx, cov_state *cv)
     return VGA_OK;
 }
 
-static void cov_release(vga_ctx *ctx)
-{
-    if (ctx->index.cov && ctx->index.cov_free) ctx->index.cov_free(ctx->index.cov);
-    ctx->index.cov = nullptr;
-    ctx->index.cov_free = nullptr;
-}
-
 extern "C" int vga_coverage_begin(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
@@ -344,22 +382,16 @@ extern "C" int vga_coverage_begin(vga_ctx *ctx)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_coverage_begin: graph too large for 32-bit positions");
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
-    try {
-        if (!ctx->index.cov) {
-            ctx->index.cov = new cov_state();
-            ctx->index.cov_free = [](void *q) { delete (cov_state *)q; };
-        }
-    } catch (const std::bad_alloc &) {
-        return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_coverage_begin: out of host memory");
-    }
+    int rc = cov_lists_acquire(ctx, COV_USER_COVERAGE, "vga_coverage_begin");
+    if (rc != VGA_OK) return rc;
     cov_state *cv = (cov_state *)ctx->index.cov;
     cv->seq_length = (uint32_t)ix.seq_length; cv->n_nodes = (uint32_t)ix.n_nodes; cv->n_edges = (uint32_t)ix.n_edges;
     hipError_t e = cv->d_diff.reserve((size_t)cv->seq_length + 1);
     if (e == hipSuccess) e = cv->d_node.reserve((size_t)cv->n_nodes + 1);
     if (e == hipSuccess) e = cv->d_edge.reserve((size_t)cv->n_edges + 1);
     if (e == hipSuccess) e = cv->d_depth.reserve((size_t)cv->seq_length + 1);
-    int rc = e == hipSuccess ? cov_zero(ctx, cv) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_coverage_begin: %s", hipGetErrorString(e));
-    if (rc != VGA_OK) cov_release(ctx);
+    rc = e == hipSuccess ? cov_zero(ctx, cv) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_coverage_begin: %s", hipGetErrorString(e));
+    if (rc != VGA_OK) cov_lists_release(ctx, COV_USER_COVERAGE);
     return rc;
 }
 
@@ -377,7 +409,7 @@ extern "C" int vga_coverage_end(vga_ctx *ctx)
     if (!ctx) return VGA_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    cov_release(ctx);
+    cov_lists_release(ctx, COV_USER_COVERAGE);
     return VGA_OK;
 }
 

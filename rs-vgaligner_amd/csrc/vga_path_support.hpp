@@ -1,0 +1,32 @@
+// vga_path_support.hpp -- how well every reported alignment fits every haplotype path of the graph (vga_path_support.hip), as
+// vga_align_batch sees it.
+//
+// Nothing in the reference stands behind this: its map.rs ends at the GAF writer.  Path support is defined on the record the
+// alignments GAF reports for a read and on the GFA's S and P lines, and can be recomputed from those texts alone
+// (tests/path_support_ref.py).  It reads what coverage reads -- the list k_cov_runs condenses every finished problem into (the
+// ids of the nodes its path enters, then the events of its runs of matched bases on the linearised graph; vga_coverage.hpp) --
+// and the lists are made while either of the two is on.  k_ps_build, once per vga_path_support_begin, turns the paths into one
+// bitset per node (bit p: path p visits the node forward) and one per edge slot (bit p: path p steps over that edge, forward to
+// forward); k_ps_score, once the host has picked the winners, gives each winner one wave.
+//
+// k_ps_score puts the PATHS across the lanes and walks the list: lane l of path block q owns path 64 q + l and keeps its two sums.
+// The wave takes 64 list items at a time (a piece of a run inside one node with its length, or a consecutive pair of nodes with
+// the slot of its edge), every lane fetches the bitset words of its own item, and the items are then handed round one by one
+// (v_readlane): the owner of a path adds the item's value when its bit is set.  No atomics and no reduction on the way; LDS only
+// holds the sums between rounds (each lane reads and writes its own words, so there is no barrier).  Per alignment of W nodes
+// and R runs cut into E pieces, with PW = ceil(n_paths / 32) words per bitset, it reads (W - 1 + E) PW bitset words, the W + 2 R
+// words of its list, and for every pair the outgoing edge slice of its first node.
+#pragma once
+
+#include "vga_common.hpp"
+#include "vga_coverage.hpp"
+
+// LDS of k_ps_score: two 32-bit sums per path
+#define PS_MAX_PATHS 4096u
+
+struct ps_state;
+// the context's path support state while it is on (vga_path_support_begin), else null
+ps_state *ps_active(vga_ctx *ctx);
+// k_ps_score over the staged winners of the call that just ended (reads[i]: the read winner i is reported for), on the context's
+// stream; waits for it.  The call's two n_reads x n_paths matrices are kept on the device for vga_path_support_last.
+int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const std::vector<uint32_t> &reads, uint64_t n_reads);

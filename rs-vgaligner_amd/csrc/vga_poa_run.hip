@@ -269,7 +269,7 @@ struct poa_call {
     vga_trace tr{"poa"};
     poa_ws &W;
     poa_pool pool;
-    cov_state *const cov;  // read coverage is being counted (vga_coverage_begin) and the graphs are in the device store: k_cov_runs beside k_poa_text
+    cov_state *const cov;  // coverage or path support is on (cov_lists_active) and the graphs are in the device store: k_cov_runs beside k_poa_text
     uint32_t max_q = 0;
     // ---- plan: node tables, estimates, launch order
     std::vector<poa_prep> G;
@@ -309,7 +309,7 @@ struct poa_call {
 
     poa_call(vga_ctx *c, poa_feed &f, const vga_poa_params *p, std::vector<poa_item> &o, poa_timing &t)
         : ctx(c), feed(f), params(p), out(o), tm(t), n(f.views.size()), views(f.views), sw(poa_read_switches()),
-          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_active(c) : nullptr) {}
+          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_lists_active(c) : nullptr) {}
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
     void chk(hipError_t e) { if (e != hipSuccess && launch_err == hipSuccess) launch_err = e; }

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <unistd.h>
 
 using namespace vgh;
@@ -40,7 +41,9 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"", "--both-strands", false, "both-strands"},
                           // not in the reference: read coverage of bases, nodes and edges, counted on the GPU (three TSV files);
                           // --coverage-only leaves the alignments GAF unwritten
-                          {"", "--coverage", false, "coverage"}, {"", "--coverage-only", false, "coverage-only"}};
+                          {"", "--coverage", false, "coverage"}, {"", "--coverage-only", false, "coverage-only"},
+                          // not in the reference: every reported alignment scored against the P lines of --graph on the GPU (two TSV files)
+                          {"", "--path-support", false, "path-support"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -131,6 +134,8 @@ int map_main(int argc, char **argv)
     o.coverage_only = m.count("coverage-only") > 0;
     o.coverage = o.coverage_only || m.count("coverage") > 0;
     if (o.coverage && !o.also_align) throw Error(std::string(o.coverage_only ? "--coverage-only" : "--coverage") + " counts alignments: it needs --also-align");
+    o.path_support = m.count("path-support") > 0;
+    if (o.path_support && !o.also_align) throw Error("--path-support scores alignments: it needs --also-align");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -152,8 +157,20 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
+    // --path-support: the P lines of --graph, and the graph checked against the index, before any device is opened
+    std::unique_ptr<HashGraph> graph;
+    if (o.path_support) {
+        graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
+        o.paths = path_table(*graph);
+        if (o.paths.n_paths() == 0) throw Error("--path-support: " + m["graph"] + " has no P line");
+    } else
+        prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
+    if (o.path_support) {
+        check_graph_matches_index(*graph, ix);
+        graph.reset();
+        prewarm_contexts(o);
+    }
     trace_mark("index loaded");
     std::vector<QuerySequence> reads = read_seqs_from_file(in);
     trace_mark("reads parsed");
@@ -168,6 +185,9 @@ int map_main(int argc, char **argv)
         fprintf(stderr, "[vgaligner] %llu of %llu reads on the reverse strand\n", (unsigned long long)out.n_reverse, (unsigned long long)out.n_reads);
     if (o.also_align) fprintf(stderr, "[vgaligner] Alignment took: %.0f ms; Found %llu alignments!\n", out.ms_align, (unsigned long long)out.n_reads);
     if (o.coverage) fprintf(stderr, "[vgaligner] Coverage: %llu alignments counted\n", (unsigned long long)out.n_coverage);
+    if (o.path_support)
+        fprintf(stderr, "[vgaligner] Path support: %llu alignments scored, %llu unplaced\n", (unsigned long long)out.n_path_scored,
+                (unsigned long long)out.n_path_unplaced);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -208,7 +228,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
-                        "                [--both-strands] [--coverage | --coverage-only]\n");
+                        "                [--both-strands] [--coverage | --coverage-only] [--path-support]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

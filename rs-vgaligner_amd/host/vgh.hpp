@@ -58,6 +58,16 @@ class HashGraph {
     static HashGraph from_gfa(const std::string &path);
 };
 
+// The P lines of a graph as vga_path_support_begin takes them: path p has the packed handles steps[step_off[p] .. step_off[p+1]).
+struct PathTable {
+    std::vector<std::string> names;
+    std::vector<uint64_t> step_off;  // n_paths + 1
+    std::vector<Handle> steps;
+    std::vector<uint64_t> length;    // bases of the forward ("id+") steps of each path
+    size_t n_paths() const { return names.size(); }
+};
+PathTable path_table(const HashGraph &g);
+
 // ---- index ------------------------------------------------------------------------------------
 struct NodeRef {
     uint64_t seq_idx, edge_idx, edges_to_node;
@@ -150,6 +160,12 @@ struct MapOptions {
     bool coverage = false;
     // --coverage-only: coverage, and the alignments GAF text is neither built nor written (the chains GAF still is)
     bool coverage_only = false;
+    // --path-support (not in the reference): score, on the GPU, every reported alignment against every P line of the graph
+    // (vga_path_support_begin / _read / _last; `paths` is path_table() of the GFA the index was built from) and write
+    // <out>-path-support.tsv and <out>-path-support-reads.tsv next to the GAF files.  Needs also_align.  Every context scores its own
+    // reads; the per-path totals are added in 64 bits at the end.
+    bool path_support = false;
+    PathTable paths;
 };
 
 // VGA_TRACE=1: wall-clock marks of the driver's phases on stderr (since the first call)
@@ -162,6 +178,7 @@ struct MapOutput {
     double ms_map = 0, ms_align = 0;     // summed over chunks (per device: the maximum over devices)
     uint64_t n_chunks = 0, n_devices = 0;
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
+    uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)
 };
 
 // One [begin, end) range of the read list, the device slot (index into MapOptions::devices) that maps it.
@@ -185,6 +202,8 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
 // concurrently; GAF order = read order (src/map.rs:123-133, 174-184).
 MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inputs, const MapOptions &opt,
                           const std::string &out_prefix);
+// throws unless `g` has the nodes of `ix`: the same count and the same lengths (what --path-support asks of --graph)
+void check_graph_matches_index(const HashGraph &g, const Index &ix);
 // Begins to create the contexts map_reads_multi(.., opt, ..) will use, on a thread of its own: starting HIP takes 0.1-0.3 s,
 // which a caller can spend reading its index and reads.  The next map_reads_multi call picks them up (and reports any error).
 void prewarm_contexts(const MapOptions &opt);

@@ -252,5 +252,24 @@ int vgh_textpath_replay(vga_ctx *ctx, void *h, uint64_t n, const char *const *na
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// the P lines of a GFA (path_table): returns the number of paths or -1.  names: the path names joined by '\n'; step_off
+// (n_paths + 1), steps (packed handles) and length (n_paths) are malloc'd arrays; all four are released with vgh_free
+int64_t vgh_gfa_paths(const char *gfa, char **names, uint64_t **step_off, uint64_t **steps, uint64_t **length)
+{
+    try {
+        const PathTable t = path_table(HashGraph::from_gfa(gfa));
+        std::string joined;
+        for (size_t p = 0; p < t.n_paths(); p++) { if (p) joined += '\n'; joined += t.names[p]; }
+        *names = dup_str(joined);
+        *step_off = (uint64_t *)malloc(t.step_off.size() * sizeof(uint64_t));
+        *steps = (uint64_t *)malloc((t.steps.size() + 1) * sizeof(uint64_t));
+        *length = (uint64_t *)malloc((t.length.size() + 1) * sizeof(uint64_t));
+        memcpy(*step_off, t.step_off.data(), t.step_off.size() * sizeof(uint64_t));
+        if (!t.steps.empty()) memcpy(*steps, t.steps.data(), t.steps.size() * sizeof(uint64_t));
+        if (!t.length.empty()) memcpy(*length, t.length.data(), t.length.size() * sizeof(uint64_t));
+        return (int64_t)t.n_paths();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
 void vgh_free(void *p) { free(p); }
 }

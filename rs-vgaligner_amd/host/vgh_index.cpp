@@ -130,6 +130,24 @@ HashGraph HashGraph::from_gfa(const std::string &path)
     return g;
 }
 
+PathTable path_table(const HashGraph &g)
+{
+    PathTable t;
+    t.step_off.push_back(0);
+    for (const Path &p : g.paths) {
+        uint64_t len = 0;
+        for (Handle h : p.steps) {
+            if (id_of(h) >= g.nodes.size() || !g.nodes[id_of(h)].present) throw Error("path " + p.name + " steps on node " + std::to_string(id_of(h)) + ", which has no S line");
+            if (!is_rev(h)) len += g.node_len(id_of(h));
+        }
+        t.names.push_back(p.name);
+        t.steps.insert(t.steps.end(), p.steps.begin(), p.steps.end());
+        t.step_off.push_back(t.steps.size());
+        t.length.push_back(len);
+    }
+    return t;
+}
+
 // ------------------------------------------------------------------------------------------ k-mers
 namespace {
 

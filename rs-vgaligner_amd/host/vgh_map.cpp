@@ -444,6 +444,7 @@ private:
 
 struct ChunkOut {
     std::vector<std::string> chains, aligns;  // GAF text in read order, in pieces
+    std::string path_rows;                    // MapOptions::path_support: the chunk's lines of <out>-path-support-reads.tsv
     uint64_t n_aligned = 0, n_anchors = 0, poa_cells = 0, n_reverse = 0;
     double ms_map = 0, ms_align = 0;
 };
@@ -556,6 +557,22 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
         out.ms_align = a->ms_total;
         out.poa_cells = a->poa_cells;
         mark("vga_align_batch");
+        if (opt.path_support) {  // the chunk's rows of the reads x paths table, while the context still holds them
+            const size_t np = opt.paths.n_paths();
+            std::vector<uint32_t> pb(n * np + 1), pe(n * np + 1);
+            if (vga_path_support_last(ctx, n, pb.data(), pe.data()) != VGA_OK) {
+                const std::string e = vga_last_error(ctx);
+                wait_k6();
+                throw Error(e);
+            }
+            for (uint64_t r = 0; r < n; r++)
+                for (size_t p = 0; a->aligned[r] && p < np; p++)
+                    if (pb[r * np + p] || pe[r * np + p]) {
+                        put_u64(out.path_rows, b0 + r); out.path_rows += '\t'; put_u64(out.path_rows, p); out.path_rows += '\t';
+                        put_u64(out.path_rows, pb[r * np + p]); out.path_rows += '\t'; put_u64(out.path_rows, pe[r * np + p]); out.path_rows += '\n';
+                    }
+            mark("path support rows");
+        }
         // everything the text needs is in host memory now: the batch and, if the caller says so, the context can go
         wait_k6();
         b_owner.reset();
@@ -713,8 +730,53 @@ void coverage_write(const Index &ix, CoverageSum s, const std::string &out_prefi
     write_file(out_prefix + "-coverage-edges.tsv", edges);
 }
 
+// ---- path support (MapOptions::path_support): the per-path totals of the contexts, added in 64 bits, and the two TSV files
+struct PathSum {
+    std::vector<uint64_t> v[4];  // sum_bases, sum_edges, top, top_alone
+    uint64_t n = 0, unplaced = 0;
+};
+
+void path_support_begin(vga_ctx *ctx, const MapOptions &opt)
+{
+    if (vga_path_support_begin(ctx, (uint32_t)opt.paths.n_paths(), opt.paths.step_off.data(), opt.paths.steps.data(), nullptr) != VGA_OK)
+        throw Error(vga_last_error(ctx));
+}
+
+// what the context has accumulated so far joins `s`
+void path_support_take(vga_ctx *ctx, const MapOptions &opt, PathSum &s)
+{
+    const size_t np = opt.paths.n_paths();
+    std::vector<uint64_t> t[4];
+    for (auto &x : t) x.assign(np + 1, 0);
+    uint64_t n = 0, un = 0;
+    if (vga_path_support_read(ctx, t[0].data(), t[1].data(), t[2].data(), t[3].data(), &n, &un) != VGA_OK) throw Error(vga_last_error(ctx));
+    for (int k = 0; k < 4; k++) {
+        s.v[k].resize(np, 0);
+        for (size_t p = 0; p < np; p++) s.v[k][p] += t[k][p];
+    }
+    s.n += n;
+    s.unplaced += un;
+}
+
+void path_support_write(const MapOptions &opt, PathSum s, const std::string &rows, const std::string &out_prefix)
+{
+    if (out_prefix.empty()) return;
+    const size_t np = opt.paths.n_paths();
+    std::string paths = "path\tsteps\tlength\tsum_bases\tsum_edges\ttop\ttop_alone\n";
+    for (size_t p = 0; p < np; p++) {
+        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
+        put_u64(paths, opt.paths.length[p]);
+        for (auto &x : s.v) { x.resize(np, 0); paths += '\t'; put_u64(paths, x[p]); }
+        paths += '\n';
+    }
+    write_file(out_prefix + "-path-support.tsv", paths);
+    write_file(out_prefix + "-path-support-reads.tsv", "read\tpath\tbases\tedges\n" + rows);
+}
+
 void check_aligner(const MapOptions &opt)
 {
+    if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
+    if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -752,6 +814,8 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     out.n_reads = inputs.size();
     out.n_devices = 1;
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
+    if (opt.path_support) path_support_begin(ctx, opt);
+    std::string path_rows;
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
     for (const Shard &s : plan_shards(len, 1, opt.chunk_reads)) {
@@ -759,6 +823,7 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         map_chunk(ctx, ix, inputs, s.begin, s.end, opt, c, ChunkHooks(), text_threads(1));
         append_pieces(out.chains_gaf, c.chains);
         append_pieces(out.alignments_gaf, c.aligns);
+        path_rows += c.path_rows;
         out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells; out.n_reverse += c.n_reverse;
         out.ms_map += c.ms_map; out.ms_align += c.ms_align;
         out.n_chunks++;
@@ -769,6 +834,13 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         (void)vga_coverage_end(ctx);
         out.n_coverage = s.n;
         coverage_write(ix, s, out_prefix);
+    }
+    if (opt.path_support) {
+        PathSum s;
+        path_support_take(ctx, opt, s);
+        (void)vga_path_support_end(ctx);
+        out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
+        path_support_write(opt, s, path_rows, out_prefix);
     }
     finish(out, ix, inputs, opt, out_prefix);
     return out;
@@ -861,7 +933,18 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     if (coverage)
         for (vga_ctx *c : ctxs)
             if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
+    if (opt.path_support)
+        for (vga_ctx *c : ctxs) {
+            try { path_support_begin(c, opt); } catch (const Error &) { release(); throw; }
+        }
     std::vector<CoverageSum> slot_cov(n_slots);
+    std::vector<PathSum> slot_paths(n_slots);
+    // what the slot's context has counted and scored, read once its last chunk is off the GPU
+    auto take_tables = [&](uint32_t slot) {
+        if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
+        if (opt.path_support) path_support_take(ctxs[slot], opt, slot_paths[slot]);
+    };
+    const bool tables = coverage || opt.path_support;
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -932,11 +1015,11 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
                         { std::lock_guard<std::mutex> lk(mu); if (abort_workers) break; }
                         ChunkHooks hooks;
                         if (stream) hooks.chains_ready = [&, i]() { { std::lock_guard<std::mutex> lk(mu); chains_done[i] = 1; } cv.notify_all(); };
-                        if (coverage && i == last_of_slot[slot] && !opt.leave_contexts)
-                            hooks.gpu_done = [&, slot]() { coverage_take(ctxs[slot], ix, slot_cov[slot]); };
+                        if (tables && i == last_of_slot[slot] && !opt.leave_contexts)
+                            hooks.gpu_done = [&, slot]() { take_tables(slot); };
                         if (opt.leave_contexts && i == last_of_slot[slot])
                             hooks.gpu_done = [&, slot]() {
-                                if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);  // (the slot's last chunk has been counted)
+                                take_tables(slot);  // (the slot's last chunk has been counted)
                                 vga_ctx *c = ctxs[slot];
                                 ctxs[slot] = nullptr;
                                 std::lock_guard<std::mutex> lk(destroyers_mu);
@@ -998,9 +1081,35 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         coverage_write(ix, sum, out_prefix);
         trace_mark("coverage tables written");
     }
+    if (opt.path_support) {
+        PathSum sum;
+        sum.v[0].assign(opt.paths.n_paths(), 0);
+        for (const PathSum &c : slot_paths) {
+            for (int k = 0; k < 4; k++) {
+                sum.v[k].resize(opt.paths.n_paths(), 0);
+                for (size_t p = 0; p < c.v[k].size(); p++) sum.v[k][p] += c.v[k][p];
+            }
+            sum.n += c.n; sum.unplaced += c.unplaced;
+        }
+        out.n_path_scored = sum.n; out.n_path_unplaced = sum.unplaced;
+        std::string rows;
+        for (size_t i = 0; i < plan.size(); i++) rows += parts[i].path_rows;  // read order
+        path_support_write(opt, sum, rows, out_prefix);
+        trace_mark("path support tables written");
+    }
     if (stream) return out;
     finish(out, ix, inputs, opt, out_prefix);
     return out;
+}
+
+void check_graph_matches_index(const HashGraph &g, const Index &ix)
+{
+    if (g.n_nodes != ix.n_nodes || g.min_id != 1 || g.max_id != g.n_nodes)
+        throw Error("the graph has " + std::to_string(g.n_nodes) + " nodes, the index " + std::to_string(ix.n_nodes) + ": not the graph the index was built from");
+    for (uint64_t id = 1; id <= ix.n_nodes; id++)
+        if (g.node_len(id) != ix.node_ref[id].seq_idx - ix.node_ref[id - 1].seq_idx)
+            throw Error("node " + std::to_string(id) + " has " + std::to_string(g.node_len(id)) + " bases in the graph and " +
+                        std::to_string(ix.node_ref[id].seq_idx - ix.node_ref[id - 1].seq_idx) + " in the index: not the graph the index was built from");
 }
 
 }  // namespace vgh

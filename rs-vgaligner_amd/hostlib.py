@@ -57,6 +57,9 @@ def load_library():
     L.vgh_gaf_chain_record.restype = vp
     L.vgh_textpath_replay.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p, C.c_uint32, C.c_uint32,
                                       C.POINTER(C.c_double)]
+    u64pp = C.POINTER(C.POINTER(C.c_uint64))
+    L.vgh_gfa_paths.argtypes = [C.c_char_p, C.POINTER(vp), u64pp, u64pp, u64pp]
+    L.vgh_gfa_paths.restype = C.c_int64
     L.vgh_free.argtypes = [vp]
     _lib = L
     return L
@@ -216,6 +219,27 @@ def read_seqs_from_file(path: str) -> List[Tuple[str, str]]:
         raise HostError(L.vgh_last_error().decode())
     out = [(names[i].decode(), seqs[i].decode()) for i in range(n)]
     return out
+
+
+def gfa_paths(path: str) -> dict:
+    """the P lines of a GFA as Context.path_support_begin takes them: {names, step_off: uint64[n_paths + 1], steps: uint64 packed
+    handles (id << 1 | is_reverse), length: uint64[n_paths], the bases of each path's forward steps}"""
+    L = load_library()
+    names = C.c_void_p()
+    off, steps, length = (C.POINTER(C.c_uint64)() for _ in range(3))
+    n = L.vgh_gfa_paths(path.encode(), C.byref(names), C.byref(off), C.byref(steps), C.byref(length))
+    if n < 0:
+        raise HostError(L.vgh_last_error().decode())
+    try:
+        text = C.string_at(names).decode()
+        step_off = np.ctypeslib.as_array(off, shape=(n + 1,)).astype(np.uint64, copy=True)
+        total = int(step_off[n])
+        return dict(names=text.split("\n") if n else [], step_off=step_off,
+                    steps=np.ctypeslib.as_array(steps, shape=(total,)).astype(np.uint64, copy=True) if total else np.zeros(0, np.uint64),
+                    length=np.ctypeslib.as_array(length, shape=(n,)).astype(np.uint64, copy=True) if n else np.zeros(0, np.uint64))
+    finally:
+        for q in (names, off, steps, length):
+            L.vgh_free(C.cast(q, C.c_void_p))
 
 
 def gaf_alignment_record(name: str, seq_len: int, aligned: bool, handles: Sequence[int], path_length: int, path_start: int, path_end: int,
