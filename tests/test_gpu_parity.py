@@ -487,6 +487,18 @@ def test_unsupported_inputs_fail_loudly(oracle, ctx, drb1):
     with pytest.raises(p.VgaError) as e:
         ctx.batch(["ACGT" * 10]).map(mp)
     assert e.value.code == -4
+    # the ends of what map_validate takes: bandwidth 1..64 (the wavefront's window), max_gap up to 1 << 22 (the tabulated gap cost);
+    # a refused call leaves the context as good as before
+    seqs = [r.seq for r in p.readsim.config2_reads(DRB1, 8)]
+    b = ctx.batch(seqs)
+    for bw, mg in ((0, 1000), (65, 1000), (50, (1 << 22) + 1)):
+        mp = p.default_map_params()
+        mp.bandwidth, mp.max_gap = bw, mg
+        with pytest.raises(p.VgaError) as e:
+            b.map(mp)
+        assert e.value.code == -4, (bw, mg)
+        mp.bandwidth, mp.max_gap = min(max(bw, 1), 64), min(mg, 1 << 22)
+        compare_map(oracle, ix, b.map(mp), seqs, mp.bandwidth, mp.max_gap)
     with pytest.raises(p.VgaError):  # edge with src >= dst
         ctx.poa_batch([(["AC", "GT"], [(1, 0)], "ACGT")])
     # a query whose column codes no longer fit the LDS next to the row window
