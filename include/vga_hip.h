@@ -365,6 +365,34 @@ int vga_path_support_end(vga_ctx *ctx);
 int vga_path_support_lists(vga_ctx *ctx, uint64_t n, const uint64_t *node_off /* n + 1 */, const uint32_t *node_ids,
                            const uint32_t *node_bases, uint32_t *bases_out, uint32_t *edges_out);
 
+/* ---- pileup: what the reported alignments say at every base of the graph ----------
+ * Stands in for nothing in the reference, whose map.rs ends at the GAF writer: it is the table a SNP / indel caller, a consensus
+ * polisher or novel-allele discovery builds from the cs strings of the alignments GAF, counted here while the alignments are still
+ * on the GPU.  It is defined on that text alone (tests/pileup_ref.py recomputes it).  Along the record reported for a read, from
+ * path_start inside its first node, with seven counters per graph base in the order A C G T N del ins:
+ *   cs ":N"    adds one, at each of its N graph bases, to the column of that base's own letter;
+ *   cs "*gq"   adds one, at its graph base, to the column of q (N for any read letter other than a c g t);
+ *   cs "-g.."  adds one to del at each of its graph bases;
+ *   cs "+q.."  adds one to ins at the graph base consumed most recently before it, covered or deleted; an insertion before the
+ *              first consumed base belongs to no base and adds one to leading_ins.
+ * So A + C + G + T + N at a base is coverage's base_depth there.  A read with a placeholder record adds nothing.  With
+ * VGA_STRANDS_BOTH a '-' record carries the forward path and the cs of the reverse complement: alleles are on the graph's forward
+ * strand.  The counters are 32-bit, exact and independent of the order of the additions; they belong to the context's index:
+ * uploading or building another index drops them and turns counting off.
+ *   vga_pileup_begin  needs an index (VGA_ERR_NO_INDEX); VGA_ERR_UNSUPPORTED for a graph of 2^29 bases or more; allocates and
+ *                     zeroes; every later vga_align_batch on ctx adds its reported alignments.  VGA_SUBGRAPH=host is refused
+ *                     by vga_align_batch while counting is on.
+ *   vga_pileup_read   counts: seq_length x 7, row-major, a row per base of seq_fwd; any pointer may be NULL; does not reset.
+ *                     VGA_ERR_ARG without _begin; VGA_ERR_UNSUPPORTED once n_alignments has reached 2^32 - 1.
+ *   vga_pileup_reset  zero, keep counting (VGA_ERR_ARG without _begin).
+ *   vga_pileup_end    free, stop counting.
+ * With counting off vga_align_batch does what it did before these calls existed: no extra launch, no extra allocation.
+ * vga_poa_batch has no graph coordinates and never counts. */
+int vga_pileup_begin(vga_ctx *ctx);
+int vga_pileup_read(vga_ctx *ctx, uint32_t *counts /* seq_length * 7 */, uint64_t *n_alignments, uint64_t *leading_ins);
+int vga_pileup_reset(vga_ctx *ctx);
+int vga_pileup_end(vga_ctx *ctx);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

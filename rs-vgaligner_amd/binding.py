@@ -23,6 +23,9 @@ VGA_STRANDS_BOTH = 1
 ERR_NAMES = {-1: "VGA_ERR_ARG", -2: "VGA_ERR_HIP", -3: "VGA_ERR_NOMEM", -4: "VGA_ERR_UNSUPPORTED",
              -5: "VGA_ERR_NO_INDEX", -6: "VGA_ERR_NO_DEVICE", -7: "VGA_ERR_POOL"}
 
+# the columns of vga_pileup_read's table
+PILEUP_COLUMNS = ("A", "C", "G", "T", "N", "del", "ins")
+
 # every symbol include/vga_hip.h declares
 ABI_SYMBOLS = [
     "vga_ctx_create", "vga_ctx_destroy", "vga_last_error", "vga_ctx_synchronize", "vga_abi_version",
@@ -34,6 +37,7 @@ ABI_SYMBOLS = [
     "vga_coverage_begin", "vga_coverage_read", "vga_coverage_reset", "vga_coverage_end",
     "vga_path_support_begin", "vga_path_support_read", "vga_path_support_last", "vga_path_support_reset", "vga_path_support_end",
     "vga_path_support_lists",
+    "vga_pileup_begin", "vga_pileup_read", "vga_pileup_reset", "vga_pileup_end",
 ]
 
 
@@ -178,6 +182,12 @@ def load_library():
         for name in ABI_SYMBOLS:
             if name.startswith("vga_path_support_"):
                 getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_pileup_begin"):  # (absent from an older build named by VGA_LIB; the Context.pileup* calls then fail)
+        for name in ("vga_pileup_begin", "vga_pileup_reset", "vga_pileup_end"):
+            getattr(L, name).argtypes = [vp]
+            getattr(L, name).restype = C.c_int
+        L.vga_pileup_read.argtypes = [vp, _P(C.c_uint32), _P(C.c_uint64), _P(C.c_uint64)]
+        L.vga_pileup_read.restype = C.c_int
     _lib = L
     return L
 
@@ -565,6 +575,26 @@ class Context:
     def coverage_end(self) -> None:
         """vga_coverage_end: free the tables, stop counting"""
         self._check(self.L.vga_coverage_end(self.h))
+
+    def pileup_begin(self) -> None:
+        """vga_pileup_begin: from now on every align() of this context adds its reported alignments to the pileup table"""
+        self._check(self.L.vga_pileup_begin(self.h))
+
+    def pileup(self):
+        """vga_pileup_read -> (counts[seq_length, 7] in the column order PILEUP_COLUMNS, n_alignments, leading_ins); does not reset"""
+        sl = self._dims[0] if self._dims else 0
+        counts = np.zeros((max(1, sl), len(PILEUP_COLUMNS)), dtype=np.uint32)
+        n, lead = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_pileup_read(self.h, _u32p(counts), C.byref(n), C.byref(lead)))
+        return counts[:sl], int(n.value), int(lead.value)
+
+    def pileup_reset(self) -> None:
+        """vga_pileup_reset: zero the table, keep counting"""
+        self._check(self.L.vga_pileup_reset(self.h))
+
+    def pileup_end(self) -> None:
+        """vga_pileup_end: free the table, stop counting"""
+        self._check(self.L.vga_pileup_end(self.h))
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

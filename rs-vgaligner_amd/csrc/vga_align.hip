@@ -15,6 +15,7 @@
 #include "vga_common.hpp"
 #include "vga_coverage.hpp"
 #include "vga_path_support.hpp"
+#include "vga_pileup.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_subgraph_host.hpp"
 
@@ -49,6 +50,7 @@ struct align_call {
     cov_state *const lists;  // the run lists of the problems are kept: coverage or path support is on
     cov_state *const cov;
     ps_state *const ps;
+    pu_state *const pu;      // the pileup is counted: event lists of its own
     // ---- plan (vga_align_plan.hpp); the per-problem arrays are in launch order on the device route, in list order on the host's
     std::vector<uint64_t> prob_read, prob_chain, read_prob0;
     std::vector<uint32_t> slot_of;  // where the q-th (read, chain) pair of the selection sits among the problems
@@ -73,7 +75,7 @@ struct align_call {
 
     align_call(vga_batch *batch, const vga_map_result *chains, uint32_t best_n, const vga_poa_params *p)
         : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), lists(cov_lists_active(batch->ctx)), cov(cov_active(batch->ctx)),
-          ps(ps_active(batch->ctx)) {}
+          ps(ps_active(batch->ctx)), pu(pu_active(batch->ctx)) {}
 
     uint32_t qlen(uint64_t r) const { return (uint32_t)(b->read_off[r + 1] - b->read_off[r]); }
     // VGA_STRANDS_BOTH: a read whose chains came from its reverse complement is aligned as that sequence
@@ -90,6 +92,7 @@ struct align_call {
     int begin_result();
     void pick_winners();
     int count_winners();
+    int pile_up_winners();
     int fill_result();
 };
 
@@ -120,6 +123,9 @@ int align_call::plan()
     if (ps && !on_device)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
                              "vga_align_batch: path support is not scored under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
+    if (pu && !on_device)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
+                             "vga_align_batch: the pileup is not counted under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
     align_select(m, align_best_n, prob_read, prob_chain, read_prob0);
     n = prob_read.size();
     proxy.resize(n);
@@ -289,6 +295,17 @@ int align_call::count_winners()
     return VGA_OK;
 }
 
+// the pileup counts the same records, from lists of its own
+int align_call::pile_up_winners()
+{
+    std::vector<uint32_t> winners;
+    for (uint64_t r = 0; r < R; r++)
+        if (pick[r] >= 0) winners.push_back((uint32_t)pick[r]);
+    const int rc = pu_add_winners(ctx, pu, winners);
+    if (rc == VGA_OK) tr.mark("pileup");
+    return rc;
+}
+
 int align_call::fill_result()
 {
     uint64_t tp = 0, tc = 0, ts = 0;
@@ -373,6 +390,7 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     c.pick_winners();
     if (c.lists && (rc = c.count_winners()) != VGA_OK) return rc;
+    if (c.pu && (rc = c.pile_up_winners()) != VGA_OK) return rc;
     if ((rc = c.fill_result()) != VGA_OK) return rc;
     *out = c.res.release();
     return VGA_OK;

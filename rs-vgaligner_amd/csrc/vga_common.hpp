@@ -62,6 +62,9 @@ struct vga_dev_index {
     // path support of this index while it is on (vga_path_support.hip): the path bitsets and the accumulators, released with the index
     void *ps = nullptr;
     void (*ps_free)(void *) = nullptr;
+    // the pileup table of this index while it is counted (vga_pileup.hip), with event lists of its own: released with the index
+    void *pu = nullptr;
+    void (*pu_free)(void *) = nullptr;
 };
 
 struct vga_timer_entry {

@@ -157,6 +157,7 @@ void vga_index_release(vga_dev_index &ix)
     if (ix.d_edges) (void)hipFree(ix.d_edges);
     if (ix.cov && ix.cov_free) ix.cov_free(ix.cov);  // (counting stops with the index it counted on)
     if (ix.ps && ix.ps_free) ix.ps_free(ix.ps);      // (and so does path support)
+    if (ix.pu && ix.pu_free) ix.pu_free(ix.pu);      // (and the pileup)
     ix = vga_dev_index();
 }
 

@@ -4,6 +4,7 @@
 // from vga_poa_shape.hpp, the traceback pool is vga_poa_pool.hip.  The engine itself is described at the top of vga_poa.hip.
 #include "vga_common.hpp"
 #include "vga_coverage.hpp"
+#include "vga_pileup.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_poa_pool.hpp"
 
@@ -270,6 +271,7 @@ struct poa_call {
     poa_ws &W;
     poa_pool pool;
     cov_state *const cov;  // coverage or path support is on (cov_lists_active) and the graphs are in the device store: k_cov_runs beside k_poa_text
+    pu_state *const pu;    // the pileup is counted (pu_active) and the graphs are in the device store: k_pu_events behind k_cov_runs
     uint32_t max_q = 0;
     // ---- plan: node tables, estimates, launch order
     std::vector<poa_prep> G;
@@ -309,7 +311,8 @@ struct poa_call {
 
     poa_call(vga_ctx *c, poa_feed &f, const vga_poa_params *p, std::vector<poa_item> &o, poa_timing &t)
         : ctx(c), feed(f), params(p), out(o), tm(t), n(f.views.size()), views(f.views), sw(poa_read_switches()),
-          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_lists_active(c) : nullptr) {}
+          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_lists_active(c) : nullptr),
+          pu(f.dev ? pu_active(c) : nullptr) {}
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
     void chk(hipError_t e) { if (e != hipSuccess && launch_err == hipSuccess) launch_err = e; }
@@ -337,6 +340,7 @@ struct poa_call {
     void launch_dp(launch_t &L);
     void enqueue_results(const launch_t &L);
     void collect_coverage(const sub_t &cur, const poa_slot::out_set &S);
+    void collect_pileup(const sub_t &cur, const poa_slot::out_set &S);
     void fill();
     // fetch its text, requeue, post-process, account
     void collect();
@@ -748,6 +752,8 @@ void poa_call::enqueue_results(const launch_t &L)
     }
     // coverage: the run list of every problem, while its operations are in the slot (the refill recycles them)
     if (cov && launch_err == hipSuccess) chk(cov_enqueue_runs(ctx, cov, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
+    // pileup: likewise, the list of its matched runs and sparse operations
+    if (pu && launch_err == hipSuccess) chk(pu_enqueue_events(ctx, pu, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
 }
 
 // stage, upload and enqueue DP + traceback + result copies of a sub-batch that starts at launch position i0 and ends
@@ -833,6 +839,8 @@ bool poa_call::fetch_text(const sub_t &cur, poa_slot::out_set &S)
     // (coverage: a problem whose run list found no room is served from the operations too)
     if (cov)
         for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || cov_launch_recs(cov, cur.slot, cur.oset)[i - cur.i0].flags == 2u;
+    if (pu)
+        for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || (pu_launch_recs(pu, cur.slot, cur.oset)[i - cur.i0].flags & 3u) == 2u;
     hipError_t ce = hipSuccess;
     if (feed.keep_text) {
         // a buffer of the context's that holds the text: the smallest free one that fits, else the largest free one grows
@@ -932,6 +940,24 @@ void poa_call::collect_coverage(const sub_t &cur, const poa_slot::out_set &S)
     }
 }
 
+// pileup: the same for its lists; the host route needs the bases of both sides as well (the gathered node sequences came back with
+// the operations, the query is the problem's view of the read)
+void poa_call::collect_pileup(const sub_t &cur, const poa_slot::out_set &S)
+{
+    const pu_rec *recs = pu_launch_recs(pu, cur.slot, cur.oset);
+    for (uint64_t i = cur.i0; i < cur.i1; i++) {
+        const uint32_t p = order[i];
+        const poa_out &ho = S.h_outs.p[i - cur.i0];
+        if (ho.status != POA_ST_OK) continue;
+        const pu_rec &r = recs[i - cur.i0];
+        if ((r.flags & 3u) != 2u) { pu_keep(pu, p, r); continue; }
+        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its pileup list, built from the operations\n", p);
+        pu_keep_from_ops(pu, p, S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1,
+                         feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start, S.h_seq.p + probs[p].seq0, probs[p].N,
+                         views[p].query);
+    }
+}
+
 // CIGAR / cs strings / node paths of a finished sub-batch on the host threads, and its share of the call's totals
 void poa_call::post_process(const sub_t &cur, const poa_slot::out_set &S)
 {
@@ -978,6 +1004,7 @@ void poa_call::collect()
         if (launch_err != hipSuccess) break;
         if (!fetch_text(cur, S)) break;
         if (cov) collect_coverage(cur, S);
+        if (pu) collect_pileup(cur, S);
         bool pool_fail = false;
         for (uint64_t i = cur.i0; i < cur.i1; i++)
             if (S.h_outs.p[i - cur.i0].status == POA_ST_POOL) {
@@ -1124,6 +1151,11 @@ int poa_run(vga_ctx *ctx, poa_feed &feed, const vga_poa_params *params, std::vec
         uint64_t total_q = 0;
         for (const poa_view &v : c.views) total_q += v.qlen;
         if ((rc = cov_call_begin(ctx, c.cov, c.n, total_q)) != VGA_OK) return rc;
+    }
+    if (c.pu) {
+        uint64_t total_q = 0;
+        for (const poa_view &v : c.views) total_q += v.qlen;
+        if ((rc = pu_call_begin(ctx, c.pu, c.n, total_q, c.sw.has_pileup_words, c.sw.pileup_words)) != VGA_OK) return rc;
     }
     if ((rc = c.order_problems()) != VGA_OK) return rc;
     if ((rc = c.size_pool()) != VGA_OK) return rc;

@@ -43,7 +43,9 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // --coverage-only leaves the alignments GAF unwritten
                           {"", "--coverage", false, "coverage"}, {"", "--coverage-only", false, "coverage-only"},
                           // not in the reference: every reported alignment scored against the P lines of --graph on the GPU (two TSV files)
-                          {"", "--path-support", false, "path-support"}};
+                          {"", "--path-support", false, "path-support"},
+                          // not in the reference: read alleles, deletions and insertions per graph base, counted on the GPU (one TSV file)
+                          {"", "--pileup", false, "pileup"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -136,6 +138,8 @@ int map_main(int argc, char **argv)
     if (o.coverage && !o.also_align) throw Error(std::string(o.coverage_only ? "--coverage-only" : "--coverage") + " counts alignments: it needs --also-align");
     o.path_support = m.count("path-support") > 0;
     if (o.path_support && !o.also_align) throw Error("--path-support scores alignments: it needs --also-align");
+    o.pileup = m.count("pileup") > 0;
+    if (o.pileup && !o.also_align) throw Error("--pileup counts alignments: it needs --also-align");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -188,6 +192,9 @@ int map_main(int argc, char **argv)
     if (o.path_support)
         fprintf(stderr, "[vgaligner] Path support: %llu alignments scored, %llu unplaced\n", (unsigned long long)out.n_path_scored,
                 (unsigned long long)out.n_path_unplaced);
+    if (o.pileup)
+        fprintf(stderr, "[vgaligner] Pileup: %llu alignments piled up, %llu leading insertions\n", (unsigned long long)out.n_pileup,
+                (unsigned long long)out.n_leading_ins);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -228,7 +235,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
-                        "                [--both-strands] [--coverage | --coverage-only] [--path-support]\n");
+                        "                [--both-strands] [--coverage | --coverage-only] [--path-support] [--pileup]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -165,6 +165,10 @@ struct MapOptions {
     // <out>-path-support.tsv and <out>-path-support-reads.tsv next to the GAF files.  Needs also_align.  Every context scores its own
     // reads; the per-path totals are added in 64 bits at the end.
     bool path_support = false;
+    // --pileup (not in the reference): count, on the GPU, what the reported alignments say at every graph base -- read alleles
+    // A C G T N, deletions, insertions (vga_pileup_begin / vga_pileup_read) -- and write <out>-pileup.tsv next to the GAF files
+    // (needs also_align)
+    bool pileup = false;
     PathTable paths;
 };
 
@@ -177,6 +181,7 @@ struct MapOutput {
     uint64_t n_reverse = 0;              // reads mapped on their reverse complement (both_strands)
     double ms_map = 0, ms_align = 0;     // summed over chunks (per device: the maximum over devices)
     uint64_t n_chunks = 0, n_devices = 0;
+    uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)
 };

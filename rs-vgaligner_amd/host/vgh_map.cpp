@@ -730,6 +730,45 @@ void coverage_write(const Index &ix, CoverageSum s, const std::string &out_prefi
     write_file(out_prefix + "-coverage-edges.tsv", edges);
 }
 
+// ---- pileup (MapOptions::pileup): the tables of the contexts, added in 64 bits, and the TSV file
+struct PileupSum {
+    std::vector<uint64_t> counts;  // seq_length x 7
+    uint64_t n = 0, leading = 0;
+    void add(const PileupSum &o)
+    {
+        if (counts.size() < o.counts.size()) counts.resize(o.counts.size(), 0);
+        for (size_t i = 0; i < o.counts.size(); i++) counts[i] += o.counts[i];
+        n += o.n;
+        leading += o.leading;
+    }
+};
+
+// what the context has counted so far joins `s`
+void pileup_take(vga_ctx *ctx, const Index &ix, PileupSum &s)
+{
+    std::vector<uint32_t> c(ix.seq_length * 7 + 1);
+    PileupSum t;
+    if (vga_pileup_read(ctx, c.data(), &t.n, &t.leading) != VGA_OK) throw Error(vga_last_error(ctx));
+    t.counts.assign(c.begin(), c.begin() + (long)(ix.seq_length * 7));
+    s.add(t);
+}
+
+void pileup_write(const Index &ix, PileupSum s, const std::string &out_prefix)
+{
+    if (out_prefix.empty()) return;
+    s.counts.resize(ix.seq_length * 7, 0);
+    std::string t = "node\toffset\tref\tA\tC\tG\tT\tN\tdel\tins\n";
+    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
+        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
+        for (uint64_t p = p0; p < p1; p++) {
+            put_u64(t, id); t += '\t'; put_u64(t, p - p0); t += '\t'; t += ix.seq_fwd[p];
+            for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, s.counts[p * 7 + (uint64_t)c]); }
+            t += '\n';
+        }
+    }
+    write_file(out_prefix + "-pileup.tsv", t);
+}
+
 // ---- path support (MapOptions::path_support): the per-path totals of the contexts, added in 64 bits, and the two TSV files
 struct PathSum {
     std::vector<uint64_t> v[4];  // sum_bases, sum_edges, top, top_alone
@@ -777,6 +816,7 @@ void check_aligner(const MapOptions &opt)
 {
     if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
     if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
+    if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -815,6 +855,7 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     out.n_devices = 1;
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     if (opt.path_support) path_support_begin(ctx, opt);
+    if (opt.pileup && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     std::string path_rows;
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
@@ -841,6 +882,13 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         (void)vga_path_support_end(ctx);
         out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
         path_support_write(opt, s, path_rows, out_prefix);
+    }
+    if (opt.pileup) {
+        PileupSum s;
+        pileup_take(ctx, ix, s);
+        (void)vga_pileup_end(ctx);
+        out.n_pileup = s.n; out.n_leading_ins = s.leading;
+        pileup_write(ix, s, out_prefix);
     }
     finish(out, ix, inputs, opt, out_prefix);
     return out;
@@ -937,14 +985,19 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (vga_ctx *c : ctxs) {
             try { path_support_begin(c, opt); } catch (const Error &) { release(); throw; }
         }
+    if (opt.pileup)
+        for (vga_ctx *c : ctxs)
+            if (vga_pileup_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
+    std::vector<PileupSum> slot_pileup(n_slots);
     std::vector<CoverageSum> slot_cov(n_slots);
     std::vector<PathSum> slot_paths(n_slots);
     // what the slot's context has counted and scored, read once its last chunk is off the GPU
     auto take_tables = [&](uint32_t slot) {
         if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
         if (opt.path_support) path_support_take(ctxs[slot], opt, slot_paths[slot]);
+        if (opt.pileup) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
     };
-    const bool tables = coverage || opt.path_support;
+    const bool tables = coverage || opt.path_support || opt.pileup;
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -1096,6 +1149,13 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (size_t i = 0; i < plan.size(); i++) rows += parts[i].path_rows;  // read order
         path_support_write(opt, sum, rows, out_prefix);
         trace_mark("path support tables written");
+    }
+    if (opt.pileup) {
+        PileupSum sum;
+        for (const PileupSum &c : slot_pileup) sum.add(c);
+        out.n_pileup = sum.n; out.n_leading_ins = sum.leading;
+        pileup_write(ix, sum, out_prefix);
+        trace_mark("pileup table written");
     }
     if (stream) return out;
     finish(out, ix, inputs, opt, out_prefix);
