@@ -834,8 +834,9 @@ bool poa_call::fetch_text(const sub_t &cur, poa_slot::out_set &S)
     hipStream_t st = sarr[cur.slot];
     poa_slot &SL = W.slot[cur.slot];
     const uint64_t used = std::min<uint64_t>(S.h_tcur.p[0], SL.d_text.cap);
-    bool overflow = false;
-    for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || S.h_touts.p[i - cur.i0].flags == 2u;
+    uint64_t no_text = 0;  // problems that found the arena full
+    for (uint64_t i = cur.i0; i < cur.i1; i++) no_text += S.h_touts.p[i - cur.i0].flags == 2u ? 1u : 0u;
+    bool overflow = no_text != 0;
     // (coverage: a problem whose run list found no room is served from the operations too)
     if (cov)
         for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || cov_launch_recs(cov, cur.slot, cur.oset)[i - cur.i0].flags == 2u;
@@ -871,7 +872,9 @@ bool poa_call::fetch_text(const sub_t &cur, poa_slot::out_set &S)
         }
     }
     if (ce == hipSuccess && overflow) {
-        if (tr.on) fprintf(stderr, "[vga-trace] poa:   the text arena was too small for some problems: their operations come back\n");
+        if (tr.on && no_text) fprintf(stderr, "[vga-trace] poa:   the text arena was too small for %llu of %llu problems: their operations come back\n",
+                                      (unsigned long long)no_text, (unsigned long long)(cur.i1 - cur.i0));
+        if (tr.on && !no_text) fprintf(stderr, "[vga-trace] poa:   some run or pileup lists found no room: the operations come back\n");
         ce = S.h_ops.reserve(S.tot_ops);
         if (ce == hipSuccess) ce = S.h_orow.reserve(S.tot_ops);
         if (ce == hipSuccess) ce = S.h_seq.reserve(S.tot_seq + 4);

@@ -65,6 +65,22 @@ def compare_map(o, ix, mo, seqs, bandwidth=50, max_gap=1000, min_anchors=3, only
         assert mo.chains_of(r) == want, f"read {r}: chains differ"
 
 
+def assert_record_equals(al, r, gaf_line):
+    """record r of a GPU align result against a line of the oracle's alignments GAF: aligned or not, node path, cs and CIGAR,
+    path length / start / end and block length"""
+    f = gaf_line.split("\t")
+    if f[5] == "*":
+        assert not al.aligned[r], f"read {r}: aligned on the GPU, a placeholder in the oracle"
+        return
+    assert al.aligned[r], f"read {r}: not aligned on the GPU"
+    path = "".join((">" if not (h & 1) else "<") + str(h >> 1)
+                   for h in al.path_handles[int(al.path_off[r]):int(al.path_off[r + 1])].tolist())
+    assert path == f[5], f"read {r}: node path differs"
+    assert f[12] == "as:i:-30 " + al.cs[r] + ",cg:Z:" + al.cigar[r], f"read {r}: cs/CIGAR differ"
+    assert (int(f[6]), int(f[7]), int(f[8]), int(f[10])) == (
+        int(al.path_length[r]), int(al.path_start[r]), int(al.path_end[r]), int(al.block_length[r])), f"read {r}: path length / start / end / block length differ"
+
+
 def run_smoke():
     from oracle import oracle_py as o
 
@@ -82,16 +98,7 @@ def run_smoke():
     al = b.align(mo)
     _, ag, _ = o.map_reads(ix, [r.name for r in reads], seqs)
     lines = ag.splitlines()
-    for r in range(len(seqs)):
-        f = lines[r].split("\t")
-        if f[5] == "*":
-            assert not al.aligned[r]
-            continue
-        assert al.aligned[r]
-        path = "".join((">" if not (h & 1) else "<") + str(h >> 1)
-                       for h in al.path_handles[int(al.path_off[r]):int(al.path_off[r + 1])].tolist())
-        assert path == f[5], f"read {r}: node path differs"
-        assert f[12] == "as:i:-30 " + al.cs[r] + ",cg:Z:" + al.cigar[r], f"read {r}: cs/CIGAR differ"
-        assert (int(f[6]), int(f[7]), int(f[8]), int(f[10])) == (
-            int(al.path_length[r]), int(al.path_start[r]), int(al.path_end[r]), int(al.block_length[r]))
+    assert len(lines) == len(seqs)
+    for r, line in enumerate(lines):
+        assert_record_equals(al, r, line)
     print("smoke ok:", len(seqs), "reads,", mo.n_anchors, "anchors,", al.poa_cells, "POA cells")
