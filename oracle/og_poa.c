@@ -467,6 +467,15 @@ int og_poa_align(const char *const *nodes, const size_t *node_lens, size_t n_nod
 cleanup:
     free(first_row); free(last_row); free(row_base); free(row_node);
     free(in_off); free(out_off); free(in_adj); free(out_adj);
+    /* diagnostics (OG_POA_ROWS=<file>): the band of every row of this problem, "r beg end" per line; rewritten per problem */
+    {
+        const char *rows_file = getenv("OG_POA_ROWS");
+        FILE *rf = rows_file ? fopen(rows_file, "w") : NULL;
+        if (rf) {
+            for (size_t r = 0; r <= N; r++) fprintf(rf, "%zu %lld %lld\n", r, (long long)beg[r], (long long)end[r]);
+            fclose(rf);
+        }
+    }
     if (width_stat) {
         FILE *wf = fopen(width_stat, "a");
         if (wf) { fprintf(wf, "rows %zu qlen %lld max %zu mean %.1f over512 %zu over1024 %zu\n", N, (long long)qlen, ws_max, (double)ws_sum / (double)(N + 1), ws_over512, ws_over1024); fclose(wf); }

@@ -585,6 +585,29 @@ def poa_align(nodes: Sequence[str], edges: Sequence[Tuple[int, int]], query: str
     return out
 
 
+def poa_align_rows(nodes: Sequence[str], edges: Sequence[Tuple[int, int]], query: str,
+                   params: Optional[PoaParams] = None) -> Tuple[PoaT, List[Tuple[int, int]]]:
+    """poa_align and the band (beg, end) of every row 0..N of that call, through the OG_POA_ROWS diagnostic of og_poa.c"""
+    import tempfile
+
+    fd, path = tempfile.mkstemp(suffix=".rows")
+    os.close(fd)
+    old = os.environ.get("OG_POA_ROWS")
+    os.environ["OG_POA_ROWS"] = path
+    try:
+        res = poa_align(nodes, edges, query, params)
+        with open(path) as f:
+            rows = [tuple(int(x) for x in ln.split()) for ln in f]
+    finally:
+        if old is None:
+            del os.environ["OG_POA_ROWS"]
+        else:
+            os.environ["OG_POA_ROWS"] = old
+        os.unlink(path)
+    assert [r for r, _, _ in rows] == list(range(res.n_rows + 1))
+    return res, [(b, e) for _, b, e in rows]
+
+
 def gaf_placeholder(name: str, qlen: int) -> str:
     return _take_str(lib().og_gaf_from_placeholder(name.encode(), qlen))
 
