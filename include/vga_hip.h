@@ -393,6 +393,44 @@ int vga_pileup_read(vga_ctx *ctx, uint32_t *counts /* seq_length * 7 */, uint64_
 int vga_pileup_reset(vga_ctx *ctx);
 int vga_pileup_end(vga_ctx *ctx);
 
+/* ---- genotype: which pair of haplotype paths explains the reported alignments best ----------
+ * Stands in for nothing in the reference.  It is the diploid reading of path support: a read from a region two alleles share
+ * votes for both, so the second allele of a heterozygous sample is not the second line of the per-path totals; the pair of
+ * paths that together explains the reads best is.  Defined on the two n_reads x n_paths matrices of one vga_align_batch (what
+ * vga_path_support_last returns) and on nothing else (tests/genotype_ref.py recomputes it).  With key[r][p] = (bases[r][p],
+ * edges[r][p]) compared lexicographically, for every pair p <= q and every row r:
+ *   take_q = key[r][q] > key[r][p]                (a full tie takes p)
+ *   sum_bases[p,q] += bases[r][take_q ? q : p]    sum_edges[p,q] += edges[r][take_q ? q : p]
+ *                                                 (the maximum is taken on the tuple, the components are summed apart: it is
+ *                                                 not a sum of packed keys)
+ *   prefer_a[p,q] += 1 if key[r][p] > key[r][q]   prefer_b[p,q] += 1 if key[r][q] > key[r][p]     (both stay 0 for p == q)
+ * Every row takes part: a placeholder or unplaced row is all zeros, adds 0 to the sums and ties everywhere.  The four
+ * accumulators are 64-bit, exact and independent of the order of the additions, and accumulate over calls until reset.
+ * The pair (p, q) sits at  p * n_paths - p * (p - 1) / 2 + (q - p)  of each array: the upper triangle, row-major,
+ * n_pairs = n_paths * (n_paths + 1) / 2 entries.  Ranking the pairs (by sum_bases, then sum_edges, both descending, then the
+ * homozygous pair first, then p, then q; pairs whose sums are (0, 0) are not ranked) is the caller's: sum[p,q] >= sum[p,p]
+ * always, so a homozygous sample ties its own heterozygous pairs and prefer_a / prefer_b tell them apart.
+ * The state belongs to path support's, which belongs to the context's index: vga_path_support_end, a second
+ * vga_path_support_begin, uploading or building another index drop it and turn genotyping off.
+ *   vga_genotype_begin  needs path support on (VGA_ERR_ARG otherwise).  Allocates and zeroes the n_pairs x 4 64-bit table --
+ *                       32 n_pairs bytes of device memory: 2.5 KB at 12 paths, 268 MB at 4096 -- VGA_ERR_NOMEM when that fails.
+ *                       Every later vga_align_batch on ctx adds the pairs of its matrices, right after it has scored them.
+ *   vga_genotype_read   n_pairs values each; any pointer may be NULL; VGA_ERR_ARG if n_pairs is not the table's; does not reset.
+ *   vga_genotype_reset  zero the table, stay on.               vga_genotype_end  free, turn off (no error when it is off).
+ *   vga_genotype_pairs  the kernel seam, as vga_path_support_lists is for the scoring: explicit n_reads x n_paths host matrices
+ *                       (row-major, n_paths 1..4096, VGA_ERR_ARG otherwise or for a NULL matrix with n_reads > 0) through the
+ *                       same kernel into a table of its own.  Needs a context only: no index, no path support, and it touches
+ *                       no accumulator.  n_reads = 0 gives zeros.
+ * read and reset return VGA_ERR_ARG while genotyping is off.  With it off vga_align_batch tests one pointer and does what it
+ * did before these calls existed: no extra launch, no extra allocation, no entry in vga_last_kernel_times. */
+int vga_genotype_begin(vga_ctx *ctx);
+int vga_genotype_read(vga_ctx *ctx, uint64_t n_pairs, uint64_t *sum_bases, uint64_t *sum_edges, uint64_t *prefer_a,
+                      uint64_t *prefer_b);
+int vga_genotype_reset(vga_ctx *ctx);
+int vga_genotype_end(vga_ctx *ctx);
+int vga_genotype_pairs(vga_ctx *ctx, uint64_t n_reads, uint32_t n_paths, const uint32_t *bases, const uint32_t *edges,
+                       uint64_t *sum_bases, uint64_t *sum_edges, uint64_t *prefer_a, uint64_t *prefer_b);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

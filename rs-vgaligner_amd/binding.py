@@ -38,7 +38,15 @@ ABI_SYMBOLS = [
     "vga_path_support_begin", "vga_path_support_read", "vga_path_support_last", "vga_path_support_reset", "vga_path_support_end",
     "vga_path_support_lists",
     "vga_pileup_begin", "vga_pileup_read", "vga_pileup_reset", "vga_pileup_end",
+    "vga_genotype_begin", "vga_genotype_read", "vga_genotype_reset", "vga_genotype_end", "vga_genotype_pairs",
 ]
+
+# k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
+# (GT_READS), and the chunks of GT_READS reads a workgroup takes before the reads are split over more workgroups (GT_MIN_CHUNKS)
+GENOTYPE_TILE = 64
+GENOTYPE_READS = 32
+GENOTYPE_MIN_CHUNKS = 4
+GENOTYPE_MAX_PATHS = 4096
 
 
 class VgaError(RuntimeError):
@@ -188,6 +196,15 @@ def load_library():
             getattr(L, name).restype = C.c_int
         L.vga_pileup_read.argtypes = [vp, _P(C.c_uint32), _P(C.c_uint64), _P(C.c_uint64)]
         L.vga_pileup_read.restype = C.c_int
+    if hasattr(L, "vga_genotype_begin"):  # (absent from an older build named by VGA_LIB; the Context.genotype* calls then fail)
+        u64p, u32p = _P(C.c_uint64), _P(C.c_uint32)
+        for name in ("vga_genotype_begin", "vga_genotype_reset", "vga_genotype_end"):
+            getattr(L, name).argtypes = [vp]
+            getattr(L, name).restype = C.c_int
+        L.vga_genotype_read.argtypes = [vp, C.c_uint64, u64p, u64p, u64p, u64p]
+        L.vga_genotype_read.restype = C.c_int
+        L.vga_genotype_pairs.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p, u64p, u64p]
+        L.vga_genotype_pairs.restype = C.c_int
     _lib = L
     return L
 
@@ -220,6 +237,37 @@ def kmer_arrays(d: IndexDesc) -> dict:
 def index_kmers_free(d: IndexDesc) -> None:
     """vga_index_kmers_free: releases the k-mer half vga_index_build_kmers filled and zeroes it"""
     load_library().vga_index_kmers_free(C.byref(d))
+
+
+GENOTYPE_FIELDS = ("sum_bases", "sum_edges", "prefer_a", "prefer_b")
+
+
+def pair_count(n_paths):
+    """P (P + 1) / 2: the pairs p <= q of a genotype table over n_paths paths"""
+    return n_paths * (n_paths + 1) // 2
+
+
+def pair_index(n_paths, p, q):
+    """where the pair (p, q), p <= q < n_paths, sits in a genotype table: p P - p (p - 1) / 2 + (q - p), the upper triangle
+    row-major (csrc/vga_pair_index.hpp).  Python integers, or numpy integer arrays (computed in 64 bits)."""
+    if isinstance(p, np.ndarray) or isinstance(q, np.ndarray):
+        p, q = np.asarray(p, dtype=np.int64), np.asarray(q, dtype=np.int64)
+    return p * n_paths - p * (p - 1) // 2 + (q - p)
+
+
+def genotype_rank(table: dict, top: Optional[int] = None):
+    """the pairs (p, q) of a genotype table (Context.genotype / genotype_pairs) from the best down: by sum_bases, then sum_edges,
+    both descending, then the homozygous pair before a heterozygous one, then p, then q.  Pairs whose sums are (0, 0) are not
+    ranked; an empty list is no call.  top: at most that many (None or 0: all)."""
+    n = int(table["n_paths"])
+    p, q = np.triu_indices(n)  # (row-major upper triangle: the table's own order)
+    sb, se = np.asarray(table["sum_bases"], dtype=np.uint64), np.asarray(table["sum_edges"], dtype=np.uint64)
+    keep = np.flatnonzero((sb != 0) | (se != 0))
+    # np.lexsort: the last key is the primary one; descending through the complement, which keeps the 64 bits
+    order = keep[np.lexsort((q[keep], p[keep], (p[keep] != q[keep]), ~se[keep], ~sb[keep]))]
+    if top:
+        order = order[:top]
+    return [(int(p[i]), int(q[i])) for i in order]
 
 
 def _np(ptr, n, dtype):
@@ -650,6 +698,43 @@ class Context:
         self._check(self.L.vga_path_support_lists(self.h, n, _u64p(off), _u32p(ids), _u32p(nb), _u32p(b), _u32p(e)))
         shape = (n, self._n_paths)
         return b[:n * self._n_paths].reshape(shape), e[:n * self._n_paths].reshape(shape)
+
+    def genotype_begin(self) -> None:
+        """vga_genotype_begin: needs path_support_begin; from now on every align() of this context adds the pairs of paths of its
+        two reads x paths matrices to the pair table"""
+        self._check(self.L.vga_genotype_begin(self.h))
+
+    def genotype(self) -> dict:
+        """vga_genotype_read -> {sum_bases, sum_edges, prefer_a, prefer_b: uint64[n_paths (n_paths + 1) / 2] at pair_index, n_paths};
+        does not reset"""
+        n = pair_count(self._n_paths)
+        a = [np.zeros(max(1, n), dtype=np.uint64) for _ in range(4)]
+        self._check(self.L.vga_genotype_read(self.h, n, _u64p(a[0]), _u64p(a[1]), _u64p(a[2]), _u64p(a[3])))
+        out = {k: v[:n] for k, v in zip(GENOTYPE_FIELDS, a)}
+        out["n_paths"] = self._n_paths
+        return out
+
+    def genotype_reset(self) -> None:
+        """vga_genotype_reset: zero the pair table, keep adding"""
+        self._check(self.L.vga_genotype_reset(self.h))
+
+    def genotype_end(self) -> None:
+        """vga_genotype_end: free the pair table, stop adding"""
+        self._check(self.L.vga_genotype_end(self.h))
+
+    def genotype_pairs(self, bases, edges) -> dict:
+        """vga_genotype_pairs, the kernel seam: two uint32[n_reads, n_paths] matrices -> the table genotype() returns, from a table
+        of its own; needs no index and touches no accumulator"""
+        b, e = (np.ascontiguousarray(x, dtype=np.uint32) for x in (bases, edges))
+        assert b.ndim == 2 and b.shape == e.shape
+        n_reads, n_paths = b.shape
+        n = pair_count(n_paths)
+        a = [np.zeros(max(1, n), dtype=np.uint64) for _ in range(4)]
+        self._check(self.L.vga_genotype_pairs(self.h, n_reads, n_paths, _u32p(b) if b.size else None, _u32p(e) if e.size else None,
+                                              _u64p(a[0]), _u64p(a[1]), _u64p(a[2]), _u64p(a[3])))
+        out = {k: v[:n] for k, v in zip(GENOTYPE_FIELDS, a)}
+        out["n_paths"] = n_paths
+        return out
 
     def chain_paths_text(self, chains: "MapOut") -> List[bytes]:
         """the path column of every chain's GAF record (vga_chain_paths_text), one bytes object per chain"""

@@ -5,6 +5,7 @@
 // path p visits forward, edges[r][p] the number of consecutive node pairs of r's path that p steps over forward to forward.  All
 // values are integers; sums and ORs do not depend on order, so the tables are exact and repeatable.
 #include "vga_path_support.hpp"
+#include "vga_genotype.hpp"
 
 #include <algorithm>
 
@@ -177,19 +178,6 @@ __global__ __launch_bounds__(64) void k_ps_score(uint32_t n, const cov_rec *__re
 
 }  // namespace
 
-// The bitsets and accumulators of a context's index while path support is on (vga_dev_index::ps: released with the index), and
-// the matrices of the most recent vga_align_batch.
-struct ps_state {
-    uint32_t n_paths = 0, PW = 0;
-    vga_dbuf<uint32_t> d_node_paths, d_edge_paths;  // n_nodes x PW, n_edges x PW
-    vga_dbuf<unsigned long long> d_acc;              // sum_bases, sum_edges, top, top_alone (n_paths each), n_alignments, n_unplaced
-    // ---- the last call
-    vga_dbuf<uint32_t> d_bases, d_edges, d_rows;
-    vga_hbuf<uint32_t> h_rows;
-    uint64_t last_reads = 0;
-    bool have_last = false;
-};
-
 ps_state *ps_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (ps_state *)ctx->index.ps : nullptr; }
 
 static void ps_launch_score(vga_ctx *ctx, const ps_state *ps, uint32_t n, const cov_win_view &v, const uint32_t *d_rows, uint32_t *d_bases,
@@ -219,6 +207,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(ps->d_rows.p, ps->h_rows.p, nw * 4, hipMemcpyHostToDevice, st));
         ps_launch_score(ctx, ps, (uint32_t)nw, v, ps->d_rows.p, ps->d_bases.p, ps->d_edges.p, ps->d_acc.p);
         VGA_HIP_CHECK(ctx, hipGetLastError());
+        if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
+            const int rc = gt_add_call(ctx, ps->gt, n_reads, ps->d_bases.p, ps->d_edges.p);
+            if (rc != VGA_OK) return rc;
+        }
     }
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     ps->last_reads = n_reads;

@@ -24,7 +24,26 @@
 // LDS of k_ps_score: two 32-bit sums per path
 #define PS_MAX_PATHS 4096u
 
-struct ps_state;
+struct gt_state;
+// The bitsets and accumulators of a context's index while path support is on (vga_dev_index::ps: released with the index), and
+// the matrices of the most recent vga_align_batch.
+struct ps_state {
+    uint32_t n_paths = 0, PW = 0;
+    vga_dbuf<uint32_t> d_node_paths, d_edge_paths;  // n_nodes x PW, n_edges x PW
+    vga_dbuf<unsigned long long> d_acc;              // sum_bases, sum_edges, top, top_alone (n_paths each), n_alignments, n_unplaced
+    // ---- the last call
+    vga_dbuf<uint32_t> d_bases, d_edges, d_rows;
+    vga_hbuf<uint32_t> h_rows;
+    uint64_t last_reads = 0;
+    bool have_last = false;
+    // ---- the pair table while genotyping is on (vga_genotype.hip), released with this state
+    gt_state *gt = nullptr;
+    void (*gt_free)(gt_state *) = nullptr;
+    ps_state() = default;
+    ps_state(const ps_state &) = delete;
+    ps_state &operator=(const ps_state &) = delete;
+    ~ps_state() { if (gt && gt_free) gt_free(gt); }
+};
 // the context's path support state while it is on (vga_path_support_begin), else null
 ps_state *ps_active(vga_ctx *ctx);
 // k_ps_score over the staged winners of the call that just ended (reads[i]: the read winner i is reported for), on the context's

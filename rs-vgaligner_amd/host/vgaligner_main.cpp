@@ -45,7 +45,10 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: every reported alignment scored against the P lines of --graph on the GPU (two TSV files)
                           {"", "--path-support", false, "path-support"},
                           // not in the reference: read alleles, deletions and insertions per graph base, counted on the GPU (one TSV file)
-                          {"", "--pileup", false, "pileup"}};
+                          {"", "--pileup", false, "pileup"},
+                          // not in the reference: the pairs of P lines of --graph ranked by how well they explain the alignments, added up
+                          // on the GPU (one TSV file); --genotype-top N: the best N pairs (20), 0 = all
+                          {"", "--genotype", false, "genotype"}, {"", "--genotype-top", true, "genotype-top"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -140,6 +143,15 @@ int map_main(int argc, char **argv)
     if (o.path_support && !o.also_align) throw Error("--path-support scores alignments: it needs --also-align");
     o.pileup = m.count("pileup") > 0;
     if (o.pileup && !o.also_align) throw Error("--pileup counts alignments: it needs --also-align");
+    o.genotype = m.count("genotype") > 0;
+    if (o.genotype && !o.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
+    if (m.count("genotype-top")) {
+        const std::string v = m["genotype-top"];
+        if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos)
+            throw Error("--genotype-top takes a number of pairs, 0 for all: not " + v);
+        if (!o.genotype) throw Error("--genotype-top has no meaning without --genotype");
+        o.genotype_top = std::stoull(v);
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -161,16 +173,17 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    // --path-support: the P lines of --graph, and the graph checked against the index, before any device is opened
+    // --path-support, --genotype: the P lines of --graph, and the graph checked against the index, before any device is opened
     std::unique_ptr<HashGraph> graph;
-    if (o.path_support) {
+    const bool scoring = o.path_support || o.genotype;
+    if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);
-        if (o.paths.n_paths() == 0) throw Error("--path-support: " + m["graph"] + " has no P line");
+        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : "--genotype: ") + m["graph"] + " has no P line");
     } else
         prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
-    if (o.path_support) {
+    if (scoring) {
         check_graph_matches_index(*graph, ix);
         graph.reset();
         prewarm_contexts(o);
@@ -192,6 +205,13 @@ int map_main(int argc, char **argv)
     if (o.path_support)
         fprintf(stderr, "[vgaligner] Path support: %llu alignments scored, %llu unplaced\n", (unsigned long long)out.n_path_scored,
                 (unsigned long long)out.n_path_unplaced);
+    if (o.genotype) {
+        if (out.n_genotype_pairs)
+            fprintf(stderr, "[vgaligner] genotype: %s / %s (sum_bases %llu, sum_edges %llu)\n", out.genotype_a.c_str(), out.genotype_b.c_str(),
+                    (unsigned long long)out.genotype_sum_bases, (unsigned long long)out.genotype_sum_edges);
+        else
+            fprintf(stderr, "[vgaligner] genotype: no call\n");
+    }
     if (o.pileup)
         fprintf(stderr, "[vgaligner] Pileup: %llu alignments piled up, %llu leading insertions\n", (unsigned long long)out.n_pileup,
                 (unsigned long long)out.n_leading_ins);
@@ -235,7 +255,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "vgaligner 0.7 (MI355X build)\nUSAGE:\n  vgaligner index -i <graph.gfa> -k <K> [-o prefix] [-e 100] [-m 100] [--device N]\n"
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
-                        "                [--both-strands] [--coverage | --coverage-only] [--path-support] [--pileup]\n");
+                        "                [--both-strands] [--coverage | --coverage-only] [--path-support] [--pileup]\n"
+                        "                [--genotype [--genotype-top 20]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

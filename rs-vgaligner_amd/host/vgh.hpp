@@ -169,6 +169,12 @@ struct MapOptions {
     // A C G T N, deletions, insertions (vga_pileup_begin / vga_pileup_read) -- and write <out>-pileup.tsv next to the GAF files
     // (needs also_align)
     bool pileup = false;
+    // --genotype (not in the reference): add up, on the GPU, how well every pair of P lines explains the reported alignments
+    // (vga_genotype_begin / vga_genotype_read over path support's matrices; `paths` as for path_support, which it turns on inside
+    // the library without its two files) and write the ranked pairs to <out>-genotype.tsv: at most genotype_top of them, 0 = all.
+    // Needs also_align.  Every context adds up its own reads; the pair tables are added in 64 bits at the end.
+    bool genotype = false;
+    uint64_t genotype_top = 20;
     PathTable paths;
 };
 
@@ -184,6 +190,9 @@ struct MapOutput {
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)
+    // MapOptions::genotype: the pairs ranked, and the first of them (names of its P lines, its sums); no pair ranked: no call
+    uint64_t n_genotype_pairs = 0, genotype_sum_bases = 0, genotype_sum_edges = 0;
+    std::string genotype_a, genotype_b;
 };
 
 // One [begin, end) range of the read list, the device slot (index into MapOptions::devices) that maps it.

@@ -7,6 +7,7 @@
 //   map_reads .................. src/map.rs:27-216, write_gaf_to_file 219-226
 // The reference's debug printing inside the hot loops is not part of the contract and is not reproduced.
 #include "vgh.hpp"
+#include "../csrc/vga_pair_index.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -812,8 +813,63 @@ void path_support_write(const MapOptions &opt, PathSum s, const std::string &row
     write_file(out_prefix + "-path-support-reads.tsv", "read\tpath\tbases\tedges\n" + rows);
 }
 
+// ---- genotype (MapOptions::genotype): the pair tables of the contexts, added in 64 bits, the ranking and the TSV file
+struct PairSum {
+    std::vector<uint64_t> v[4];  // sum_bases, sum_edges, prefer_a, prefer_b at vga_pair_index
+};
+
+// what the context has accumulated so far joins `s`
+void genotype_take(vga_ctx *ctx, const MapOptions &opt, PairSum &s)
+{
+    const size_t n = vga_pair_count(opt.paths.n_paths());
+    std::vector<uint64_t> t[4];
+    for (auto &x : t) x.assign(n + 1, 0);
+    if (vga_genotype_read(ctx, n, t[0].data(), t[1].data(), t[2].data(), t[3].data()) != VGA_OK) throw Error(vga_last_error(ctx));
+    for (int k = 0; k < 4; k++) {
+        s.v[k].resize(n, 0);
+        for (size_t i = 0; i < n; i++) s.v[k][i] += t[k][i];
+    }
+}
+
+// The pairs whose sums are not (0, 0), from the best down: by sum_bases, then sum_edges, both descending, then the homozygous
+// pair before a heterozygous one, then p, then q.
+void genotype_write(const MapOptions &opt, PairSum s, MapOutput &out, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths(), n = vga_pair_count(np);
+    for (auto &x : s.v) x.resize(n, 0);
+    struct Pair { uint32_t p, q; uint64_t at; };
+    std::vector<Pair> ranked;
+    for (uint32_t p = 0; p < np; p++)
+        for (uint32_t q = p; q < np; q++) {
+            const uint64_t at = vga_pair_index(np, p, q);
+            if (s.v[0][at] || s.v[1][at]) ranked.push_back({p, q, at});
+        }
+    std::sort(ranked.begin(), ranked.end(), [&](const Pair &a, const Pair &b) {
+        if (s.v[0][a.at] != s.v[0][b.at]) return s.v[0][a.at] > s.v[0][b.at];
+        if (s.v[1][a.at] != s.v[1][b.at]) return s.v[1][a.at] > s.v[1][b.at];
+        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
+        return a.p != b.p ? a.p < b.p : a.q < b.q;
+    });
+    out.n_genotype_pairs = ranked.size();
+    if (!ranked.empty()) {
+        out.genotype_a = opt.paths.names[ranked[0].p]; out.genotype_b = opt.paths.names[ranked[0].q];
+        out.genotype_sum_bases = s.v[0][ranked[0].at]; out.genotype_sum_edges = s.v[1][ranked[0].at];
+    }
+    if (out_prefix.empty()) return;
+    std::string t = "rank\tpath_a\tpath_b\tsum_bases\tsum_edges\tprefer_a\tprefer_b\n";
+    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
+    for (size_t i = 0; i < rows; i++) {
+        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q];
+        for (const auto &x : s.v) { t += '\t'; put_u64(t, x[ranked[i].at]); }
+        t += '\n';
+    }
+    write_file(out_prefix + "-genotype.tsv", t);
+}
+
 void check_aligner(const MapOptions &opt)
 {
+    if (opt.genotype && !opt.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
+    if (opt.genotype && opt.paths.n_paths() == 0) throw Error("--genotype: the graph has no P line");
     if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
     if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
     if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
@@ -854,7 +910,9 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     out.n_reads = inputs.size();
     out.n_devices = 1;
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    if (opt.path_support) path_support_begin(ctx, opt);
+    const bool scoring = opt.path_support || opt.genotype;  // (--genotype turns the scoring on, not its files)
+    if (scoring) path_support_begin(ctx, opt);
+    if (opt.genotype && vga_genotype_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     if (opt.pileup && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     std::string path_rows;
     std::vector<uint64_t> len(inputs.size());
@@ -876,12 +934,17 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         out.n_coverage = s.n;
         coverage_write(ix, s, out_prefix);
     }
-    if (opt.path_support) {
+    if (opt.genotype) {
+        PairSum s;
+        genotype_take(ctx, opt, s);
+        genotype_write(opt, std::move(s), out, out_prefix);
+    }
+    if (scoring) {
         PathSum s;
         path_support_take(ctx, opt, s);
-        (void)vga_path_support_end(ctx);
+        (void)vga_path_support_end(ctx);  // (and genotyping with it)
         out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
-        path_support_write(opt, s, path_rows, out_prefix);
+        if (opt.path_support) path_support_write(opt, s, path_rows, out_prefix);
     }
     if (opt.pileup) {
         PileupSum s;
@@ -981,9 +1044,11 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     if (coverage)
         for (vga_ctx *c : ctxs)
             if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-    if (opt.path_support)
+    const bool scoring = opt.path_support || opt.genotype;  // (--genotype turns the scoring on, not its files)
+    if (scoring)
         for (vga_ctx *c : ctxs) {
             try { path_support_begin(c, opt); } catch (const Error &) { release(); throw; }
+            if (opt.genotype && vga_genotype_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
         }
     if (opt.pileup)
         for (vga_ctx *c : ctxs)
@@ -991,13 +1056,15 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     std::vector<PileupSum> slot_pileup(n_slots);
     std::vector<CoverageSum> slot_cov(n_slots);
     std::vector<PathSum> slot_paths(n_slots);
+    std::vector<PairSum> slot_pairs(n_slots);
     // what the slot's context has counted and scored, read once its last chunk is off the GPU
     auto take_tables = [&](uint32_t slot) {
         if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
-        if (opt.path_support) path_support_take(ctxs[slot], opt, slot_paths[slot]);
+        if (scoring) path_support_take(ctxs[slot], opt, slot_paths[slot]);
+        if (opt.genotype) genotype_take(ctxs[slot], opt, slot_pairs[slot]);
         if (opt.pileup) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
     };
-    const bool tables = coverage || opt.path_support || opt.pileup;
+    const bool tables = coverage || scoring || opt.pileup;
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -1134,7 +1201,18 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         coverage_write(ix, sum, out_prefix);
         trace_mark("coverage tables written");
     }
-    if (opt.path_support) {
+    if (opt.genotype) {
+        PairSum sum;
+        const size_t n = vga_pair_count(opt.paths.n_paths());
+        for (const PairSum &c : slot_pairs)
+            for (int k = 0; k < 4; k++) {
+                sum.v[k].resize(n, 0);
+                for (size_t i = 0; i < c.v[k].size(); i++) sum.v[k][i] += c.v[k][i];
+            }
+        genotype_write(opt, std::move(sum), out, out_prefix);
+        trace_mark("genotype table written");
+    }
+    if (scoring) {
         PathSum sum;
         sum.v[0].assign(opt.paths.n_paths(), 0);
         for (const PathSum &c : slot_paths) {
@@ -1145,10 +1223,12 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
             sum.n += c.n; sum.unplaced += c.unplaced;
         }
         out.n_path_scored = sum.n; out.n_path_unplaced = sum.unplaced;
-        std::string rows;
-        for (size_t i = 0; i < plan.size(); i++) rows += parts[i].path_rows;  // read order
-        path_support_write(opt, sum, rows, out_prefix);
-        trace_mark("path support tables written");
+        if (opt.path_support) {
+            std::string rows;
+            for (size_t i = 0; i < plan.size(); i++) rows += parts[i].path_rows;  // read order
+            path_support_write(opt, sum, rows, out_prefix);
+            trace_mark("path support tables written");
+        }
     }
     if (opt.pileup) {
         PileupSum sum;
