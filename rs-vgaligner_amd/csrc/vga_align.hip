@@ -169,7 +169,7 @@ int align_call::device_store()
     if (sw.trace)
         fprintf(stderr, "[vga-trace] align: mean width term of the launch-order proxy %.0f: the subgraph store is built in %s\n", mean_west,
                 split == n ? "one part" : "two parts");
-    const int rc = sg_prepare(ctx, descs.data(), q_src.data(), n, split, b->d_reads, params->remain_rule, store);
+    const int rc = sg_prepare(ctx, descs.data(), q_src.data(), prob_read.data(), n, split, b->d_reads, params->remain_rule, store);
     if (rc != VGA_OK) return rc;
     sub_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
     feed.dev = &store;

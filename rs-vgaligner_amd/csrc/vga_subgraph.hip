@@ -23,6 +23,7 @@
 #include "vga_subgraph.hpp"
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 namespace {
@@ -449,6 +450,8 @@ struct sg_ws {
     vga_hbuf<sg_off> h_off;
     sg_part_bufs part[2];
     std::vector<uint64_t> q_src;
+    std::string dump;               // VGA_SG_DUMP: file for the tables of every problem of the call (empty: off)
+    std::vector<uint64_t> read_no;  // ... and the read of every problem, for its records
     hipStream_t side = nullptr;
     uint64_t waves = 0;
     uint32_t nh = 0, words = 0;
@@ -457,6 +460,54 @@ struct sg_ws {
         if (side) (void)hipStreamDestroy(side);
     }
 };
+
+// VGA_SG_DUMP: what the kernels wrote for problems [p0, p1) -- the part is ready -- as one text record per problem, in launch
+// order, appended to the file (sg_prepare truncated it).  A record is the lines
+//   P <problem> read <read> pmin pmax q_first t_first q_last te_last qlen     (sg_desc)
+//   S n_nodes N n_preds n_sinks wlo whi longest life flags                    (sg_sum)
+//   T <entry> row len deg sink far remain pred    entry 0 is the virtual source, entry 1 + i node i: the four table words, split
+//   H handles / F first rows / L predecessor list / K sinks / Q the N sequence bytes in hex / E
+// and stops after S for a problem the kernels flagged (it has no tables).
+int sg_dump_part(vga_ctx *ctx, sg_ws &W, const sg_part_bufs &B, uint64_t p0, uint64_t p1, uint64_t tn, uint64_t tp, uint64_t ts, uint64_t tq, hipStream_t st)
+{
+    const uint64_t n = p1 - p0;
+    std::vector<uint4> ntab(tn + n);
+    std::vector<uint32_t> preds(tp + 1), sinks(ts + 1);
+    std::vector<char> seq(tq + 4);
+    VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(ntab.data(), B.d_ntab.p, (tn + n) * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    if (tp) VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(preds.data(), B.d_preds.p, tp * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (ts) VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(sinks.data(), B.d_sinks.p, ts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (tq) VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(seq.data(), B.d_seq.p, tq, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
+    FILE *f = fopen(W.dump.c_str(), "a");
+    if (!f) return vga_set_error(ctx, VGA_ERR_ARG, "VGA_SG_DUMP: cannot append to %s", W.dump.c_str());
+    auto list = [&](const char *tag, const uint32_t *v, uint64_t cnt) {
+        fputs(tag, f);
+        for (uint64_t i = 0; i < cnt; i++) fprintf(f, " %u", v[i]);
+        fputc('\n', f);
+    };
+    for (uint64_t p = p0; p < p1; p++) {
+        const sg_desc &d = W.h_desc.p[p];
+        const sg_sum &s = W.h_sum.p[p];
+        const sg_off &o = W.h_off.p[p];
+        fprintf(f, "P %llu read %llu %u %u %u %u %u %u %u\n", (unsigned long long)p, (unsigned long long)W.read_no[p], d.pmin, d.pmax, d.q_first, d.t_first,
+                d.q_last, d.te_last, d.qlen);
+        fprintf(f, "S %u %u %u %u %u %u %u %u %u\n", s.n_nodes, s.N, s.n_preds, s.n_sinks, s.wlo, s.whi, s.longest, s.life, s.flags);
+        if (s.flags & 1u) continue;
+        const uint4 *nt = ntab.data() + o.node0 + (p - p0);
+        for (uint32_t i = 0; i <= s.n_nodes; i++)
+            fprintf(f, "T %u %u %u %u %u %u %u %u\n", i, nt[i].x, nt[i].y & 0xFFFFFFu, nt[i].y >> 24, nt[i].z >> 31, (nt[i].z >> 30) & 1u, nt[i].z & 0x3FFFFFFFu, nt[i].w);
+        list("H", B.h_handles.p + o.node0, s.n_nodes);
+        list("F", B.h_first_row.p + o.node0, s.n_nodes);
+        list("L", preds.data() + o.pred0, s.n_preds);
+        list("K", sinks.data() + o.sink0, s.n_sinks);
+        fputs("Q ", f);
+        for (uint32_t i = 0; i < s.N; i++) fprintf(f, "%02x", (unsigned)(unsigned char)seq[o.seq0 + i]);
+        fputs("\nE\n", f);
+    }
+    fclose(f);
+    return VGA_OK;
+}
 
 // mark + counts, offsets, emit and the copies back for problems [p0, p1) on stream st; waits for them
 int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uint64_t p1, hipStream_t st)
@@ -508,6 +559,10 @@ int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uin
         VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(B.h_first_row.p, B.d_first_row.p, tn * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     VGA_HIP_CHECK_OOM(ctx, hipStreamSynchronize(st));
+    if (!W.dump.empty()) {
+        const int rc = sg_dump_part(ctx, W, B, p0, p1, tn, tp, ts, tq, st);
+        if (rc != VGA_OK) return rc;
+    }
     P.d_ntab = B.d_ntab.p; P.d_preds = B.d_preds.p; P.d_sinks = B.d_sinks.p; P.d_seq = B.d_seq.p;
     P.d_handles = B.d_handles.p;
     P.h_handles = B.h_handles.p; P.h_first_row = B.h_first_row.p;
@@ -517,8 +572,8 @@ int sg_run_part(vga_ctx *ctx, sg_ws &W, sg_store &store, int k, uint64_t p0, uin
 
 }  // namespace
 
-int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, uint64_t n, uint64_t split, const char *d_reads, int remain_rule,
-               sg_store &store)
+int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, const uint64_t *read_no, uint64_t n, uint64_t split, const char *d_reads,
+               int remain_rule, sg_store &store)
 {
     store = sg_store();
     store.remain_rule = remain_rule;
@@ -551,6 +606,14 @@ int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, uint64
     VGA_HIP_CHECK_OOM(ctx, W.d_scratch.reserve(W.waves * 5ull * W.nh));
     memcpy(W.h_desc.p, descs, n * sizeof(sg_desc));
     W.q_src.assign(q_src, q_src + n);
+    const char *dump = getenv("VGA_SG_DUMP");
+    W.dump = dump ? dump : "";
+    if (!W.dump.empty()) {  // (the first part of the call starts the file; both parts append)
+        W.read_no.assign(read_no, read_no + n);
+        FILE *f = fopen(W.dump.c_str(), "w");
+        if (!f) return vga_set_error(ctx, VGA_ERR_ARG, "VGA_SG_DUMP: cannot write %s", W.dump.c_str());
+        fclose(f);
+    }
     VGA_HIP_CHECK_OOM(ctx, hipMemcpyAsync(W.d_desc.p, W.h_desc.p, n * sizeof(sg_desc), hipMemcpyHostToDevice, st));
     store.n = n;
     store.split = split;

@@ -33,8 +33,9 @@ struct sg_store {
 };
 
 // Runs the extraction for chains [0, split) of n on ctx->stream and waits for it.  `store` points into the context's
-// workspace and stays valid until the next call.  Returns VGA_OK or a negative VGA_ERR_*.
-int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, uint64_t n, uint64_t split, const char *d_reads, int remain_rule,
-               sg_store &store);
+// workspace and stays valid until the next call.  read_no[p] is the read of chain p in the batch: it only labels the records of
+// the VGA_SG_DUMP diagnostic.  Returns VGA_OK or a negative VGA_ERR_*.
+int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, const uint64_t *read_no, uint64_t n, uint64_t split, const char *d_reads,
+               int remain_rule, sg_store &store);
 // ... and for chains [split, n), on the workspace's side stream (it may run beside DP launches); waits for it.
 int sg_prepare_rest(vga_ctx *ctx, sg_store &store);
