@@ -431,6 +431,43 @@ int vga_genotype_end(vga_ctx *ctx);
 int vga_genotype_pairs(vga_ctx *ctx, uint64_t n_reads, uint32_t n_paths, const uint32_t *bases, const uint32_t *edges,
                        uint64_t *sum_bases, uint64_t *sum_edges, uint64_t *prefer_a, uint64_t *prefer_b);
 
+/* ---- genotype likelihood: the diploid read likelihood of every pair of haplotype paths ----------
+ * Stands in for nothing in the reference.  The standard model of HLA typers: each read is explained by one of the two alleles
+ * with probability 1/2 each.  Defined, in integers only, on the two n_reads x n_paths matrices of one vga_align_batch (what
+ * vga_path_support_last returns) and on nothing else (tests/genotype_lik_ref.py recomputes it).  With lambda in 1..4096, the cost
+ * of one unit of deficit in 1/256 bit, and cap in 1..255, for every row r:
+ *   s[r][p] = bases[r][p] + edges[r][p]                      (64 bits)
+ *   d[r][p] = min(max over p' of s[r][p'] - s[r][p], cap)    (the capped deficit, a byte; an all-zero row has d = 0 everywhere)
+ *   cost[p,q] += lambda min(d[r][p], d[r][q]) + T[|d[r][p] - d[r][q]|]     for every pair p <= q, in uint64
+ *   n_scored  += 1 if some s[r][p] > 0
+ * with T[x] = round(256 (1 - log2(1 + 2^(-lambda x / 256)))), x = 0..cap: T[0] = 0, T never decreases, T <= 256.  This is
+ * -log2(1/2 2^(-lambda d_p) + 1/2 2^(-lambda d_q)) in 1/256 bit.  The cost is additive over reads, calls and contexts (the row
+ * maximum lies within the row) and independent of their order.  cost sits at p P - p (p - 1) / 2 + (q - p), as the genotype
+ * table does.  Ranking is the caller's: cost ascending, then the homozygous pair first, then p, then q; n_scored = 0 is no call.
+ * It does not need vga_genotype_begin and does not change it: either, both or neither may be on.  The state belongs to path
+ * support's, like the genotype table: vga_path_support_end, a second vga_path_support_begin, uploading or building another index
+ * drop it.
+ *   vga_genotype_lik_table  no context: out[0..cap] = T.  VGA_ERR_ARG for lambda or cap out of range or a NULL out.  The one
+ *                           definition of T: the kernels receive this table and never evaluate a logarithm.
+ *   vga_genotype_lik_begin  needs path support on (VGA_ERR_ARG otherwise, and for lambda or cap out of range).  Allocates and
+ *                           zeroes the table, 8 n_pairs bytes of device memory (and 8 for n_scored) -- VGA_ERR_NOMEM when that
+ *                           fails.  Every later vga_align_batch on ctx adds the cost of its matrices, right after scoring them.
+ *   vga_genotype_lik_read   n_pairs values; either pointer may be NULL; VGA_ERR_ARG if n_pairs is not the table's; does not reset.
+ *   vga_genotype_lik_reset  zero the table, stay on.           vga_genotype_lik_end  free, turn off (no error when it is off).
+ *   vga_genotype_lik_pairs  the kernel seam: explicit n_reads x n_paths host matrices (row-major, n_paths 1..4096; VGA_ERR_ARG
+ *                           otherwise, for lambda or cap out of range, or for a NULL matrix with n_reads > 0) through the same
+ *                           two kernels into a table of its own.  deficit_out (n_reads x n_paths bytes), cost_out and n_scored
+ *                           may each be NULL.  Needs a context only.  n_reads = 0 gives zeros.
+ * read and reset return VGA_ERR_ARG while it is off.  With it off vga_align_batch tests one pointer and does what it did before
+ * these calls existed: no extra launch, no extra allocation, no entry in vga_last_kernel_times. */
+int vga_genotype_lik_table(uint32_t lambda, uint32_t cap, uint32_t *out /* cap + 1 */);
+int vga_genotype_lik_begin(vga_ctx *ctx, uint32_t lambda, uint32_t cap);
+int vga_genotype_lik_read(vga_ctx *ctx, uint64_t n_pairs, uint64_t *cost, uint64_t *n_scored);
+int vga_genotype_lik_reset(vga_ctx *ctx);
+int vga_genotype_lik_end(vga_ctx *ctx);
+int vga_genotype_lik_pairs(vga_ctx *ctx, uint64_t n_reads, uint32_t n_paths, const uint32_t *bases, const uint32_t *edges,
+                           uint32_t lambda, uint32_t cap, uint8_t *deficit_out, uint64_t *cost_out, uint64_t *n_scored);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

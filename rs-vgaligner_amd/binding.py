@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "vga_path_support_lists",
     "vga_pileup_begin", "vga_pileup_read", "vga_pileup_reset", "vga_pileup_end",
     "vga_genotype_begin", "vga_genotype_read", "vga_genotype_reset", "vga_genotype_end", "vga_genotype_pairs",
+    "vga_genotype_lik_table", "vga_genotype_lik_begin", "vga_genotype_lik_read", "vga_genotype_lik_reset", "vga_genotype_lik_end",
+    "vga_genotype_lik_pairs",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -47,6 +49,19 @@ GENOTYPE_TILE = 64
 GENOTYPE_READS = 32
 GENOTYPE_MIN_CHUNKS = 4
 GENOTYPE_MAX_PATHS = 4096
+
+# k_gl_pairs (csrc/vga_genotype_lik.hpp): the paths on a side of a workgroup's tile (GL_TILE), the reads it stages at a time
+# (GL_READS), the chunks of GL_READS reads a workgroup takes before the reads are split over more workgroups (GL_MIN_CHUNKS), the
+# reads whose cost its 32-bit accumulators hold (GL_MAX_GROUP_READS), and the ranges of the two parameters
+GENOTYPE_LIK_TILE = 128
+GENOTYPE_LIK_READS = 32
+GENOTYPE_LIK_MIN_CHUNKS = 4
+GENOTYPE_LIK_MAX_GROUP_READS = 2048
+GENOTYPE_LIK_MAX_PATHS = 4096
+GENOTYPE_LIK_MAX_LAMBDA = 4096
+GENOTYPE_LIK_MAX_CAP = 255
+GENOTYPE_LIK_LAMBDA = 512  # the defaults of Context.genotype_likelihood_begin and of `vgaligner map --genotype-likelihood`
+GENOTYPE_LIK_CAP = 64
 
 
 class VgaError(RuntimeError):
@@ -205,6 +220,17 @@ def load_library():
         L.vga_genotype_read.restype = C.c_int
         L.vga_genotype_pairs.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p, u64p, u64p]
         L.vga_genotype_pairs.restype = C.c_int
+    if hasattr(L, "vga_genotype_lik_begin"):  # (absent from an older build named by VGA_LIB; the Context.genotype_likelihood* calls then fail)
+        u64p, u32p = _P(C.c_uint64), _P(C.c_uint32)
+        L.vga_genotype_lik_table.argtypes = [C.c_uint32, C.c_uint32, u32p]
+        L.vga_genotype_lik_begin.argtypes = [vp, C.c_uint32, C.c_uint32]
+        L.vga_genotype_lik_read.argtypes = [vp, C.c_uint64, u64p, u64p]
+        L.vga_genotype_lik_reset.argtypes = [vp]
+        L.vga_genotype_lik_end.argtypes = [vp]
+        L.vga_genotype_lik_pairs.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, _P(C.c_uint8), u64p, u64p]
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_genotype_lik_"):
+                getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -268,6 +294,34 @@ def genotype_rank(table: dict, top: Optional[int] = None):
     if top:
         order = order[:top]
     return [(int(p[i]), int(q[i])) for i in order]
+
+
+def genotype_likelihood_table(lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYPE_LIK_CAP) -> np.ndarray:
+    """vga_genotype_lik_table -> T, uint32[cap + 1]: T[x] = round(256 (1 - log2(1 + 2^(-lam x / 256)))), the library's one
+    definition (csrc/vga_genotype_lik.hpp); needs no context and no device"""
+    if not (0 <= int(lam) < 1 << 32 and 0 <= int(cap) < 1 << 32):
+        raise VgaError(-1, "genotype_likelihood_table: lam %r, cap %r" % (lam, cap))
+    t = np.zeros(int(cap) + 1 if 0 < int(cap) <= GENOTYPE_LIK_MAX_CAP else 1, dtype=np.uint32)
+    rc = load_library().vga_genotype_lik_table(int(lam), int(cap), _u32p(t))
+    if rc != VGA_OK:
+        raise VgaError(rc, "genotype_likelihood_table: lam %r is 1 to %d and cap %r 1 to %d" % (lam, GENOTYPE_LIK_MAX_LAMBDA, cap, GENOTYPE_LIK_MAX_CAP))
+    return t
+
+
+def genotype_likelihood_rank(cost, n_paths: int, top: Optional[int] = None):
+    """the pairs of a cost table (Context.genotype_likelihood / genotype_likelihood_pairs) from the best down, as
+    [(p, q, cost, margin)]: by cost ascending, then the homozygous pair before a heterozygous one, then p, then q; margin is the
+    cost above the first pair's.  Whether there is a call at all is n_scored's to say (0: no call).  top: at most that many
+    (None or 0: all)."""
+    n = int(n_paths)
+    c = np.asarray(cost, dtype=np.uint64)
+    assert c.shape == (pair_count(n),)
+    p, q = np.triu_indices(n)  # (row-major upper triangle: the table's own order)
+    order = np.lexsort((q, p, p != q, c))  # np.lexsort: the last key is the primary one
+    if top:
+        order = order[:top]
+    first = int(c[order[0]]) if len(order) else 0
+    return [(int(p[i]), int(q[i]), int(c[i]), int(c[i]) - first) for i in order]
 
 
 def _np(ptr, n, dtype):
@@ -735,6 +789,47 @@ class Context:
         out = {k: v[:n] for k, v in zip(GENOTYPE_FIELDS, a)}
         out["n_paths"] = n_paths
         return out
+
+    def genotype_likelihood_begin(self, lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYPE_LIK_CAP) -> None:
+        """vga_genotype_lik_begin: needs path_support_begin; from now on every align() of this context adds the diploid read
+        likelihood cost of every pair of paths, from its two reads x paths matrices, to the cost table.  lam: the cost of one unit
+        of deficit in 1/256 bit (1..4096); cap: the largest deficit told apart (1..255)"""
+        if not (0 <= int(lam) < 1 << 32 and 0 <= int(cap) < 1 << 32):
+            raise VgaError(-1, "genotype_likelihood_begin: lam %r, cap %r" % (lam, cap))
+        self._check(self.L.vga_genotype_lik_begin(self.h, int(lam), int(cap)))
+
+    def genotype_likelihood(self) -> dict:
+        """vga_genotype_lik_read -> {cost: uint64[n_paths (n_paths + 1) / 2] at pair_index, in 1/256 bit; n_scored; n_paths};
+        does not reset"""
+        n = pair_count(self._n_paths)
+        c = np.zeros(max(1, n), dtype=np.uint64)
+        scored = C.c_uint64(0)
+        self._check(self.L.vga_genotype_lik_read(self.h, n, _u64p(c), C.byref(scored)))
+        return {"cost": c[:n], "n_scored": int(scored.value), "n_paths": self._n_paths}
+
+    def genotype_likelihood_reset(self) -> None:
+        """vga_genotype_lik_reset: zero the cost table, keep adding"""
+        self._check(self.L.vga_genotype_lik_reset(self.h))
+
+    def genotype_likelihood_end(self) -> None:
+        """vga_genotype_lik_end: free the cost table, stop adding"""
+        self._check(self.L.vga_genotype_lik_end(self.h))
+
+    def genotype_likelihood_pairs(self, bases, edges, lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYPE_LIK_CAP) -> dict:
+        """vga_genotype_lik_pairs, the kernel seam: two uint32[n_reads, n_paths] matrices -> {cost: uint64[pairs], deficit:
+        uint8[n_reads, n_paths], n_scored, n_paths}, from a table of its own; needs no index and touches no accumulator"""
+        b, e = (np.ascontiguousarray(x, dtype=np.uint32) for x in (bases, edges))
+        assert b.ndim == 2 and b.shape == e.shape
+        if not (0 <= int(lam) < 1 << 32 and 0 <= int(cap) < 1 << 32):
+            raise VgaError(-1, "genotype_likelihood_pairs: lam %r, cap %r" % (lam, cap))
+        n_reads, n_paths = b.shape
+        n = pair_count(n_paths)
+        c = np.zeros(max(1, n), dtype=np.uint64)
+        d = np.zeros(max(1, b.size), dtype=np.uint8)
+        scored = C.c_uint64(0)
+        self._check(self.L.vga_genotype_lik_pairs(self.h, n_reads, n_paths, _u32p(b) if b.size else None, _u32p(e) if e.size else None,
+                                                  int(lam), int(cap), d.ctypes.data_as(_P(C.c_uint8)), _u64p(c), C.byref(scored)))
+        return {"cost": c[:n], "deficit": d[:b.size].reshape(b.shape), "n_scored": int(scored.value), "n_paths": n_paths}
 
     def chain_paths_text(self, chains: "MapOut") -> List[bytes]:
         """the path column of every chain's GAF record (vga_chain_paths_text), one bytes object per chain"""

@@ -6,6 +6,7 @@
 // values are integers; sums and ORs do not depend on order, so the tables are exact and repeatable.
 #include "vga_path_support.hpp"
 #include "vga_genotype.hpp"
+#include "vga_genotype_lik.hpp"
 
 #include <algorithm>
 
@@ -209,6 +210,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         VGA_HIP_CHECK(ctx, hipGetLastError());
         if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
             const int rc = gt_add_call(ctx, ps->gt, n_reads, ps->d_bases.p, ps->d_edges.p);
+            if (rc != VGA_OK) return rc;
+        }
+        if (ps->gl) {  // the read likelihood is on: the byte deficits of the two matrices and the cost of every pair, on the same stream
+            const int rc = gl_add_call(ctx, ps->gl, n_reads, ps->d_bases.p, ps->d_edges.p);
             if (rc != VGA_OK) return rc;
         }
     }

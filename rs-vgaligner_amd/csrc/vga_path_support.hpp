@@ -25,6 +25,7 @@
 #define PS_MAX_PATHS 4096u
 
 struct gt_state;
+struct gl_state;
 // The bitsets and accumulators of a context's index while path support is on (vga_dev_index::ps: released with the index), and
 // the matrices of the most recent vga_align_batch.
 struct ps_state {
@@ -39,10 +40,17 @@ struct ps_state {
     // ---- the pair table while genotyping is on (vga_genotype.hip), released with this state
     gt_state *gt = nullptr;
     void (*gt_free)(gt_state *) = nullptr;
+    // ---- the cost table while the read likelihood is on (vga_genotype_lik.hip), released with this state
+    gl_state *gl = nullptr;
+    void (*gl_free)(gl_state *) = nullptr;
     ps_state() = default;
     ps_state(const ps_state &) = delete;
     ps_state &operator=(const ps_state &) = delete;
-    ~ps_state() { if (gt && gt_free) gt_free(gt); }
+    ~ps_state()
+    {
+        if (gt && gt_free) gt_free(gt);
+        if (gl && gl_free) gl_free(gl);
+    }
 };
 // the context's path support state while it is on (vga_path_support_begin), else null
 ps_state *ps_active(vga_ctx *ctx);

@@ -48,7 +48,12 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"", "--pileup", false, "pileup"},
                           // not in the reference: the pairs of P lines of --graph ranked by how well they explain the alignments, added up
                           // on the GPU (one TSV file); --genotype-top N: the best N pairs (20), 0 = all
-                          {"", "--genotype", false, "genotype"}, {"", "--genotype-top", true, "genotype-top"}};
+                          {"", "--genotype", false, "genotype"}, {"", "--genotype-top", true, "genotype-top"},
+                          // not in the reference: the pairs of P lines of --graph ranked by the diploid read likelihood, added up on the
+                          // GPU (one TSV file); --genotype-lambda N: the cost of one unit of deficit in 1/256 bit (512, 1..4096);
+                          // --genotype-cap N: the largest deficit told apart (64, 1..255); --genotype-top applies to it too
+                          {"", "--genotype-likelihood", false, "genotype-likelihood"}, {"", "--genotype-lambda", true, "genotype-lambda"},
+                          {"", "--genotype-cap", true, "genotype-cap"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -145,13 +150,26 @@ int map_main(int argc, char **argv)
     if (o.pileup && !o.also_align) throw Error("--pileup counts alignments: it needs --also-align");
     o.genotype = m.count("genotype") > 0;
     if (o.genotype && !o.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
+    o.genotype_likelihood = m.count("genotype-likelihood") > 0;
+    if (o.genotype_likelihood && !o.also_align) throw Error("--genotype-likelihood calls from alignments: it needs --also-align");
     if (m.count("genotype-top")) {
         const std::string v = m["genotype-top"];
         if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos)
             throw Error("--genotype-top takes a number of pairs, 0 for all: not " + v);
-        if (!o.genotype) throw Error("--genotype-top has no meaning without --genotype");
+        if (!o.genotype && !o.genotype_likelihood) throw Error("--genotype-top has no meaning without --genotype or --genotype-likelihood");
         o.genotype_top = std::stoull(v);
     }
+    // --genotype-lambda, --genotype-cap: a number inside the range of vga_genotype_lik_begin, and only beside --genotype-likelihood
+    auto likelihood_value = [&](const char *key, uint32_t lo, uint32_t hi, uint32_t &into) {
+        if (!m.count(key)) return;
+        const std::string v = m[key], flag = std::string("--") + key;
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoul(v) < lo || std::stoul(v) > hi)
+            throw Error(flag + " takes a number from " + std::to_string(lo) + " to " + std::to_string(hi) + ": not " + v);
+        if (!o.genotype_likelihood) throw Error(flag + " has no meaning without --genotype-likelihood");
+        into = (uint32_t)std::stoul(v);
+    };
+    likelihood_value("genotype-lambda", 1, 4096, o.genotype_lambda);
+    likelihood_value("genotype-cap", 1, 255, o.genotype_cap);
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -173,13 +191,14 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    // --path-support, --genotype: the P lines of --graph, and the graph checked against the index, before any device is opened
+    // --path-support, --genotype, --genotype-likelihood: the P lines of --graph, and the graph checked against the index, before any
+    // device is opened
     std::unique_ptr<HashGraph> graph;
-    const bool scoring = o.path_support || o.genotype;
+    const bool scoring = o.path_support || o.genotype || o.genotype_likelihood;
     if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);
-        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : "--genotype: ") + m["graph"] + " has no P line");
+        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : "--genotype-likelihood: ") + m["graph"] + " has no P line");
     } else
         prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
@@ -211,6 +230,13 @@ int map_main(int argc, char **argv)
                     (unsigned long long)out.genotype_sum_bases, (unsigned long long)out.genotype_sum_edges);
         else
             fprintf(stderr, "[vgaligner] genotype: no call\n");
+    }
+    if (o.genotype_likelihood) {
+        if (out.n_likelihood_scored)
+            fprintf(stderr, "[vgaligner] genotype-likelihood: %s / %s cost %llu, next +%llu over %llu reads\n", out.likelihood_a.c_str(), out.likelihood_b.c_str(),
+                    (unsigned long long)out.likelihood_cost, (unsigned long long)out.likelihood_next, (unsigned long long)out.n_likelihood_scored);
+        else
+            fprintf(stderr, "[vgaligner] genotype-likelihood: no call\n");
     }
     if (o.pileup)
         fprintf(stderr, "[vgaligner] Pileup: %llu alignments piled up, %llu leading insertions\n", (unsigned long long)out.n_pileup,
@@ -256,7 +282,8 @@ int main(int argc, char **argv)
                         "  vgaligner map -i <index> -f <reads.fa|fq> -p abpoa [-o prefix] [-g 1000] [-a 3] [-b 1] [-D -G <graph.gfa>] [-C]\n"
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
                         "                [--both-strands] [--coverage | --coverage-only] [--path-support] [--pileup]\n"
-                        "                [--genotype [--genotype-top 20]]\n");
+                        "                [--genotype [--genotype-top 20]]\n"
+                        "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -175,6 +175,13 @@ struct MapOptions {
     // Needs also_align.  Every context adds up its own reads; the pair tables are added in 64 bits at the end.
     bool genotype = false;
     uint64_t genotype_top = 20;
+    // --genotype-likelihood (not in the reference): add up, on the GPU, the diploid read likelihood cost of every pair of P lines
+    // (vga_genotype_lik_begin / vga_genotype_lik_read over path support's matrices, which it turns on like genotype) and write the
+    // pairs from the cheapest up to <out>-genotype-likelihood.tsv: at most genotype_top of them, 0 = all.  genotype_lambda: the
+    // cost of one unit of deficit in 1/256 bit (1..4096); genotype_cap: the largest deficit told apart (1..255).  Needs
+    // also_align.  Every context adds up its own reads; the cost tables are added in 64 bits at the end.
+    bool genotype_likelihood = false;
+    uint32_t genotype_lambda = 512, genotype_cap = 64;
     PathTable paths;
 };
 
@@ -193,6 +200,10 @@ struct MapOutput {
     // MapOptions::genotype: the pairs ranked, and the first of them (names of its P lines, its sums); no pair ranked: no call
     uint64_t n_genotype_pairs = 0, genotype_sum_bases = 0, genotype_sum_edges = 0;
     std::string genotype_a, genotype_b;
+    // MapOptions::genotype_likelihood: the rows scored (0: no call), the cheapest pair (names of its P lines, its cost in 1/256
+    // bit) and how much more the next pair costs
+    uint64_t n_likelihood_scored = 0, likelihood_cost = 0, likelihood_next = 0;
+    std::string likelihood_a, likelihood_b;
 };
 
 // One [begin, end) range of the read list, the device slot (index into MapOptions::devices) that maps it.

@@ -866,8 +866,67 @@ void genotype_write(const MapOptions &opt, PairSum s, MapOutput &out, const std:
     write_file(out_prefix + "-genotype.tsv", t);
 }
 
+// ---- genotype likelihood (MapOptions::genotype_likelihood): the cost tables of the contexts, added in 64 bits, the ranking and
+// the TSV file
+struct CostSum {
+    std::vector<uint64_t> cost;  // at vga_pair_index, in 1/256 bit
+    uint64_t n_scored = 0;
+    void add(const CostSum &o)
+    {
+        if (cost.size() < o.cost.size()) cost.resize(o.cost.size(), 0);
+        for (size_t i = 0; i < o.cost.size(); i++) cost[i] += o.cost[i];
+        n_scored += o.n_scored;
+    }
+};
+
+// what the context has accumulated so far joins `s`
+void likelihood_take(vga_ctx *ctx, const MapOptions &opt, CostSum &s)
+{
+    CostSum t;
+    t.cost.assign(vga_pair_count(opt.paths.n_paths()), 0);
+    if (vga_genotype_lik_read(ctx, t.cost.size(), t.cost.data(), &t.n_scored) != VGA_OK) throw Error(vga_last_error(ctx));
+    s.add(t);
+}
+
+// Every pair from the cheapest up: by cost, then the homozygous pair before a heterozygous one, then p, then q.  No row scored:
+// no call, and a table with its header only.
+void likelihood_write(const MapOptions &opt, CostSum s, MapOutput &out, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    s.cost.resize(vga_pair_count(np), 0);
+    struct Pair { uint32_t p, q; uint64_t cost; };
+    std::vector<Pair> ranked;
+    if (s.n_scored)
+        for (uint32_t p = 0; p < np; p++)
+            for (uint32_t q = p; q < np; q++) ranked.push_back({p, q, s.cost[vga_pair_index(np, p, q)]});
+    std::sort(ranked.begin(), ranked.end(), [](const Pair &a, const Pair &b) {
+        if (a.cost != b.cost) return a.cost < b.cost;
+        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
+        return a.p != b.p ? a.p < b.p : a.q < b.q;
+    });
+    out.n_likelihood_scored = s.n_scored;
+    if (!ranked.empty()) {
+        out.likelihood_a = opt.paths.names[ranked[0].p]; out.likelihood_b = opt.paths.names[ranked[0].q];
+        out.likelihood_cost = ranked[0].cost;
+        out.likelihood_next = ranked.size() > 1 ? ranked[1].cost - ranked[0].cost : 0;
+    }
+    if (out_prefix.empty()) return;
+    std::string t = "rank\tpath_a\tpath_b\tcost\tmargin\n";
+    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
+    for (size_t i = 0; i < rows; i++) {
+        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q]; t += '\t';
+        put_u64(t, ranked[i].cost); t += '\t'; put_u64(t, ranked[i].cost - ranked[0].cost); t += '\n';
+    }
+    write_file(out_prefix + "-genotype-likelihood.tsv", t);
+}
+
+bool likelihood_params_ok(const MapOptions &opt) { return opt.genotype_lambda >= 1 && opt.genotype_lambda <= 4096 && opt.genotype_cap >= 1 && opt.genotype_cap <= 255; }
+
 void check_aligner(const MapOptions &opt)
 {
+    if (opt.genotype_likelihood && !opt.also_align) throw Error("--genotype-likelihood calls from alignments: it needs --also-align");
+    if (opt.genotype_likelihood && opt.paths.n_paths() == 0) throw Error("--genotype-likelihood: the graph has no P line");
+    if (opt.genotype_likelihood && !likelihood_params_ok(opt)) throw Error("--genotype-likelihood: --genotype-lambda is 1 to 4096 and --genotype-cap 1 to 255");
     if (opt.genotype && !opt.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
     if (opt.genotype && opt.paths.n_paths() == 0) throw Error("--genotype: the graph has no P line");
     if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
@@ -910,9 +969,10 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     out.n_reads = inputs.size();
     out.n_devices = 1;
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    const bool scoring = opt.path_support || opt.genotype;  // (--genotype turns the scoring on, not its files)
+    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood;  // (either genotype switch turns the scoring on, not its files)
     if (scoring) path_support_begin(ctx, opt);
     if (opt.genotype && vga_genotype_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
+    if (opt.genotype_likelihood && vga_genotype_lik_begin(ctx, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) throw Error(vga_last_error(ctx));
     if (opt.pileup && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     std::string path_rows;
     std::vector<uint64_t> len(inputs.size());
@@ -938,6 +998,11 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         PairSum s;
         genotype_take(ctx, opt, s);
         genotype_write(opt, std::move(s), out, out_prefix);
+    }
+    if (opt.genotype_likelihood) {
+        CostSum s;
+        likelihood_take(ctx, opt, s);
+        likelihood_write(opt, std::move(s), out, out_prefix);
     }
     if (scoring) {
         PathSum s;
@@ -1044,11 +1109,14 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     if (coverage)
         for (vga_ctx *c : ctxs)
             if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-    const bool scoring = opt.path_support || opt.genotype;  // (--genotype turns the scoring on, not its files)
+    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood;  // (either genotype switch turns the scoring on, not its files)
     if (scoring)
         for (vga_ctx *c : ctxs) {
             try { path_support_begin(c, opt); } catch (const Error &) { release(); throw; }
             if (opt.genotype && vga_genotype_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
+            if (opt.genotype_likelihood && vga_genotype_lik_begin(c, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) {
+                const std::string e = vga_last_error(c); release(); throw Error(e);
+            }
         }
     if (opt.pileup)
         for (vga_ctx *c : ctxs)
@@ -1057,11 +1125,13 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     std::vector<CoverageSum> slot_cov(n_slots);
     std::vector<PathSum> slot_paths(n_slots);
     std::vector<PairSum> slot_pairs(n_slots);
+    std::vector<CostSum> slot_costs(n_slots);
     // what the slot's context has counted and scored, read once its last chunk is off the GPU
     auto take_tables = [&](uint32_t slot) {
         if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
         if (scoring) path_support_take(ctxs[slot], opt, slot_paths[slot]);
         if (opt.genotype) genotype_take(ctxs[slot], opt, slot_pairs[slot]);
+        if (opt.genotype_likelihood) likelihood_take(ctxs[slot], opt, slot_costs[slot]);
         if (opt.pileup) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
     };
     const bool tables = coverage || scoring || opt.pileup;
@@ -1211,6 +1281,12 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
             }
         genotype_write(opt, std::move(sum), out, out_prefix);
         trace_mark("genotype table written");
+    }
+    if (opt.genotype_likelihood) {
+        CostSum sum;
+        for (const CostSum &c : slot_costs) sum.add(c);
+        likelihood_write(opt, std::move(sum), out, out_prefix);
+        trace_mark("genotype likelihood table written");
     }
     if (scoring) {
         PathSum sum;
