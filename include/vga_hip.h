@@ -468,6 +468,58 @@ int vga_genotype_lik_end(vga_ctx *ctx);
 int vga_genotype_lik_pairs(vga_ctx *ctx, uint64_t n_reads, uint32_t n_paths, const uint32_t *bases, const uint32_t *edges,
                            uint32_t lambda, uint32_t cap, uint8_t *deficit_out, uint64_t *cost_out, uint64_t *n_scored);
 
+/* ---- path edit: the edit distance of every reported alignment's read to every haplotype path ----------
+ * Stands in for nothing in the reference.  Path support counts what the alignment happened to walk over; this is what allele
+ * typers use: the unit-cost edit distance of the read to the allele's sequence.  Defined on the alignments GAF, the GFA's S and P
+ * lines and the read sequences and on nothing else (tests/path_edit_ref.py recomputes it from them).  For the record reported for
+ * read r, with query Q of m letters (the read; its reverse complement for a '-' record under VGA_STRANDS_BOTH) and node path
+ * w0..wn, and path p with sequence seq_p (its steps' node sequences in order, an "id-" step reverse-complemented, N stays N;
+ * pos_p(i) the offset of step i):
+ *   letters  compared upper-cased; A, C, G and T equal themselves, any other letter on either side matches nothing;
+ *   anchor   a = the first node of w that p visits as "id+", i = the FIRST such step of p;
+ *            b = the last node of w that p visits as "id+",  j = the LAST such step of p;
+ *            no such node, or j < i: e[r][p] = NONE (0xFFFFFFFF);
+ *   window   lo = max(0, pos_p(i) - m), hi = min(|seq_p|, pos_p(j) + len(b) + m): every placement of Q that overlaps the anchor span;
+ *   e[r][p]  the minimum of edit(Q, seq_p[s:t]) over lo <= s <= t <= hi (Sellers' infix distance: the top row is 0, the answer the
+ *            minimum of the bottom row, column 0 included), so e <= m.
+ * A read with a placeholder record has a NONE row; so has a read of more than 16 384 letters, which the kernel does not serve:
+ * it is counted in n_too_long.  Per path, accumulated over calls like path support (64-bit, exact, order-independent):
+ *   n_scored[p]: alignments with e[r][p] != NONE; sum_edit[p]: the sum of those e; best[p]: alignments for which p attains the
+ *   minimum of the row over its scored paths; best_alone[p]: those where no other path does; and the scalars n_alignments
+ *   (aligned records seen) and n_too_long.
+ * The state belongs to path support's, like the genotype tables: vga_path_support_end, a second vga_path_support_begin, uploading
+ * or building another index drop it.
+ *   vga_path_edit_begin  needs path support on (VGA_ERR_ARG otherwise).  Builds the path sequences (one byte per base) and each
+ *                        path's sorted (node, step) array on the device.  VGA_ERR_UNSUPPORTED when the paths hold 2^32 bases or
+ *                        more, VGA_ERR_NOMEM when an allocation fails.  Every later vga_align_batch on ctx scores its reported
+ *                        alignments.  A second begin starts over.
+ *   vga_path_edit_read   the accumulators, n_paths values each; any pointer may be NULL; does not reset.
+ *   vga_path_edit_last   the n_reads x n_paths matrix (row-major) of the most recent vga_align_batch on ctx.  VGA_ERR_ARG if
+ *                        n_reads is not that batch's or there has been none since begin.
+ *   vga_path_edit_reset  zero the accumulators, stay on.        vga_path_edit_end  free, turn off (no error when it is off).
+ *   vga_path_edit_pairs  the kernel seam: n explicit pairs -- query i is q[q_off[i] .. q_off[i+1]), text i is
+ *                        t[t_off[i] .. t_off[i+1]) -- through the same distance kernel with lo = 0, hi = |text|, into out[i].
+ *                        A query of more than 16 384 letters gives NONE, an empty query 0, an empty text m.  Needs a context
+ *                        only: no index, no path support, and it touches no accumulator.
+ *   vga_genotype_lik_source  which matrices the likelihood reads from now on: VGA_GL_FROM_SUPPORT (the default: path support's
+ *                        bases and edges) or VGA_GL_FROM_EDIT, which needs vga_path_edit_begin as well (VGA_ERR_ARG otherwise, for
+ *                        any other value, and while the likelihood is off): after every batch the same two kernels get
+ *                        bases' = m_r - e[r][p] (0 for NONE) and edges' = 0, so d = min(e - min e, cap), a NONE pair gets the
+ *                        deficit of e = m, and an all-NONE row costs nothing.  A deficit is then a count of edits.
+ * read, last and reset return VGA_ERR_ARG while it is off.  With it off vga_align_batch tests one pointer and does what it did
+ * before these calls existed: no extra launch, no extra allocation, no entry in vga_last_kernel_times. */
+#define VGA_GL_FROM_SUPPORT 0u
+#define VGA_GL_FROM_EDIT 1u
+int vga_path_edit_begin(vga_ctx *ctx);
+int vga_path_edit_read(vga_ctx *ctx, uint64_t *n_scored, uint64_t *sum_edit, uint64_t *best, uint64_t *best_alone,
+                       uint64_t *n_alignments, uint64_t *n_too_long);
+int vga_path_edit_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *edit);
+int vga_path_edit_reset(vga_ctx *ctx);
+int vga_path_edit_end(vga_ctx *ctx);
+int vga_path_edit_pairs(vga_ctx *ctx, uint64_t n, const uint64_t *q_off /* n + 1 */, const char *q, const uint64_t *t_off /* n + 1 */,
+                        const char *t, uint32_t *out /* n */);
+int vga_genotype_lik_source(vga_ctx *ctx, uint32_t source);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

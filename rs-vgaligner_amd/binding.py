@@ -40,7 +40,8 @@ ABI_SYMBOLS = [
     "vga_pileup_begin", "vga_pileup_read", "vga_pileup_reset", "vga_pileup_end",
     "vga_genotype_begin", "vga_genotype_read", "vga_genotype_reset", "vga_genotype_end", "vga_genotype_pairs",
     "vga_genotype_lik_table", "vga_genotype_lik_begin", "vga_genotype_lik_read", "vga_genotype_lik_reset", "vga_genotype_lik_end",
-    "vga_genotype_lik_pairs",
+    "vga_genotype_lik_pairs", "vga_genotype_lik_source",
+    "vga_path_edit_begin", "vga_path_edit_read", "vga_path_edit_last", "vga_path_edit_reset", "vga_path_edit_end", "vga_path_edit_pairs",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -62,6 +63,17 @@ GENOTYPE_LIK_MAX_LAMBDA = 4096
 GENOTYPE_LIK_MAX_CAP = 255
 GENOTYPE_LIK_LAMBDA = 512  # the defaults of Context.genotype_likelihood_begin and of `vgaligner map --genotype-likelihood`
 GENOTYPE_LIK_CAP = 64
+# vga_genotype_lik_source: the matrices the likelihood reads
+VGA_GL_FROM_SUPPORT = 0
+VGA_GL_FROM_EDIT = 1
+GENOTYPE_LIK_SOURCES = {"support": VGA_GL_FROM_SUPPORT, "edit": VGA_GL_FROM_EDIT}
+
+# k_pe_dist (csrc/vga_path_edit.hpp): e of a pair that is not scored, the most 64-row blocks a lane owns (PE_MAX_R; the kernel is
+# instantiated for 1, 2 and 4) and the longest query 64 such lanes hold (PE_MAX_QUERY)
+PATH_EDIT_NONE = 0xFFFFFFFF
+PATH_EDIT_MAX_R = 4
+PATH_EDIT_MAX_QUERY = 64 * 64 * PATH_EDIT_MAX_R
+PATH_EDIT_FIELDS = ("n_scored", "sum_edit", "best", "best_alone")
 
 
 class VgaError(RuntimeError):
@@ -229,7 +241,19 @@ def load_library():
         L.vga_genotype_lik_end.argtypes = [vp]
         L.vga_genotype_lik_pairs.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, _P(C.c_uint8), u64p, u64p]
         for name in ABI_SYMBOLS:
-            if name.startswith("vga_genotype_lik_"):
+            if name.startswith("vga_genotype_lik_") and name != "vga_genotype_lik_source":  # (declared with path edit below)
+                getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_path_edit_begin"):  # (absent from an older build named by VGA_LIB; the Context.path_edit* calls then fail)
+        u64p, u32p = _P(C.c_uint64), _P(C.c_uint32)
+        for name in ("vga_path_edit_begin", "vga_path_edit_reset", "vga_path_edit_end"):
+            getattr(L, name).argtypes = [vp]
+        L.vga_path_edit_read.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, u64p]
+        L.vga_path_edit_last.argtypes = [vp, C.c_uint64, u32p]
+        L.vga_path_edit_pairs.argtypes = [vp, C.c_uint64, u64p, C.c_char_p, u64p, C.c_char_p, u32p]
+        L.vga_genotype_lik_source.argtypes = [vp, C.c_uint32]
+        L.vga_genotype_lik_source.restype = C.c_int
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_path_edit_"):
                 getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -790,13 +814,23 @@ class Context:
         out["n_paths"] = n_paths
         return out
 
-    def genotype_likelihood_begin(self, lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYPE_LIK_CAP) -> None:
+    def genotype_likelihood_begin(self, lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYPE_LIK_CAP, source: str = "support") -> None:
         """vga_genotype_lik_begin: needs path_support_begin; from now on every align() of this context adds the diploid read
         likelihood cost of every pair of paths, from its two reads x paths matrices, to the cost table.  lam: the cost of one unit
-        of deficit in 1/256 bit (1..4096); cap: the largest deficit told apart (1..255)"""
+        of deficit in 1/256 bit (1..4096); cap: the largest deficit told apart (1..255); source: "support" (path support's bases and
+        edges) or "edit" (vga_genotype_lik_source: m - e of path_edit, which needs path_edit_begin first; a deficit is then a
+        count of edits)"""
         if not (0 <= int(lam) < 1 << 32 and 0 <= int(cap) < 1 << 32):
             raise VgaError(-1, "genotype_likelihood_begin: lam %r, cap %r" % (lam, cap))
+        if source not in GENOTYPE_LIK_SOURCES:
+            raise VgaError(-1, "genotype_likelihood_begin: source %r is neither 'support' nor 'edit'" % (source,))
         self._check(self.L.vga_genotype_lik_begin(self.h, int(lam), int(cap)))
+        if source != "support":
+            rc = self.L.vga_genotype_lik_source(self.h, GENOTYPE_LIK_SOURCES[source])
+            if rc != VGA_OK:
+                msg = (self.L.vga_last_error(self.h) or b"").decode()
+                self.L.vga_genotype_lik_end(self.h)
+                raise VgaError(rc, msg)
 
     def genotype_likelihood(self) -> dict:
         """vga_genotype_lik_read -> {cost: uint64[n_paths (n_paths + 1) / 2] at pair_index, in 1/256 bit; n_scored; n_paths};
@@ -830,6 +864,50 @@ class Context:
         self._check(self.L.vga_genotype_lik_pairs(self.h, n_reads, n_paths, _u32p(b) if b.size else None, _u32p(e) if e.size else None,
                                                   int(lam), int(cap), d.ctypes.data_as(_P(C.c_uint8)), _u64p(c), C.byref(scored)))
         return {"cost": c[:n], "deficit": d[:b.size].reshape(b.shape), "n_scored": int(scored.value), "n_paths": n_paths}
+
+    def path_edit_begin(self) -> None:
+        """vga_path_edit_begin: needs path_support_begin; from now on every align() of this context scores the read of every
+        reported alignment against every path by edit distance"""
+        self._check(self.L.vga_path_edit_begin(self.h))
+
+    def path_edit(self) -> dict:
+        """vga_path_edit_read -> {n_scored, sum_edit, best, best_alone: uint64[n_paths], n_alignments, n_too_long}; does not reset"""
+        a = [np.zeros(max(1, self._n_paths), dtype=np.uint64) for _ in range(4)]
+        n, long_ = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_path_edit_read(self.h, _u64p(a[0]), _u64p(a[1]), _u64p(a[2]), _u64p(a[3]), C.byref(n), C.byref(long_)))
+        out = {k: v[:self._n_paths] for k, v in zip(PATH_EDIT_FIELDS, a)}
+        out.update(n_alignments=int(n.value), n_too_long=int(long_.value))
+        return out
+
+    def path_edit_last(self, n_reads: Optional[int] = None):
+        """vga_path_edit_last -> uint32[n_reads, n_paths] of the most recent align() of this context; PATH_EDIT_NONE: not scored"""
+        n = self._last_reads if n_reads is None else int(n_reads)
+        e = np.zeros(max(1, n * self._n_paths), dtype=np.uint32)
+        self._check(self.L.vga_path_edit_last(self.h, n, _u32p(e)))
+        return e[:n * self._n_paths].reshape((n, self._n_paths))
+
+    def path_edit_reset(self) -> None:
+        """vga_path_edit_reset: zero the accumulators, keep scoring"""
+        self._check(self.L.vga_path_edit_reset(self.h))
+
+    def path_edit_end(self) -> None:
+        """vga_path_edit_end: free the state, stop scoring"""
+        self._check(self.L.vga_path_edit_end(self.h))
+
+    def path_edit_pairs(self, queries, texts) -> np.ndarray:
+        """vga_path_edit_pairs, the kernel seam: the infix edit distance of queries[i] in texts[i] (str or bytes) through the
+        distance kernel -> uint32[n]; PATH_EDIT_NONE for a query of more than PATH_EDIT_MAX_QUERY letters.  Needs no index and
+        touches no accumulator"""
+        assert len(queries) == len(texts)
+        n = len(queries)
+        enc = lambda x: x if isinstance(x, bytes) else x.encode()
+        qs, ts = [enc(x) for x in queries], [enc(x) for x in texts]
+        q_off, t_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(2))
+        q_off[1:] = np.cumsum([len(x) for x in qs], dtype=np.uint64)
+        t_off[1:] = np.cumsum([len(x) for x in ts], dtype=np.uint64)
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        self._check(self.L.vga_path_edit_pairs(self.h, n, _u64p(q_off), b"".join(qs), _u64p(t_off), b"".join(ts), _u32p(out)))
+        return out[:n]
 
     def chain_paths_text(self, chains: "MapOut") -> List[bytes]:
         """the path column of every chain's GAF record (vga_chain_paths_text), one bytes object per chain"""

@@ -14,6 +14,7 @@
 #include "vga_align_plan.hpp"
 #include "vga_common.hpp"
 #include "vga_coverage.hpp"
+#include "vga_path_edit.hpp"
 #include "vga_path_support.hpp"
 #include "vga_pileup.hpp"
 #include "vga_poa_internal.hpp"
@@ -289,7 +290,12 @@ int align_call::count_winners()
         tr.mark("coverage");
     }
     if (ps) {
-        if ((rc = ps_score_winners(ctx, ps, v, reads, R)) != VGA_OK) return rc;
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> len;
+        if (ps->pe)  // the edit distance is on: where each winner's query sits in the batch on the device
+            for (uint32_t r : reads) { off.push_back(q_off(r)); len.push_back(qlen(r)); }
+        const pe_queries q = {b->d_reads, off.data(), len.data()};
+        if ((rc = ps_score_winners(ctx, ps, v, reads, R, &q)) != VGA_OK) return rc;
         tr.mark("path support");
     }
     return VGA_OK;

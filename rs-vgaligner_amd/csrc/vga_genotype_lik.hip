@@ -11,6 +11,7 @@
 #include "vga_genotype_lik.hpp"
 #include "vga_common.hpp"
 #include "vga_pair_index.hpp"
+#include "vga_path_edit.hpp"
 #include "vga_path_support.hpp"
 
 #include <algorithm>
@@ -195,6 +196,7 @@ int gl_table_upload(vga_ctx *ctx, uint32_t lambda, uint32_t cap, uint16_t *h2, v
 
 struct gl_state {
     uint32_t n_paths = 0, lambda = 0, cap = 0;
+    uint32_t source = VGA_GL_FROM_SUPPORT;
     uint64_t n_pairs = 0;
     uint16_t h_table2[256] = {};
     vga_dbuf<uint16_t> d_table2;
@@ -207,6 +209,8 @@ gl_state *gl_active(vga_ctx *ctx)
     ps_state *ps = ps_active(ctx);
     return ps ? ps->gl : nullptr;
 }
+
+uint32_t gl_source(const gl_state *gl) { return gl->source; }
 
 int gl_add_call(vga_ctx *ctx, gl_state *gl, uint64_t n_reads, const uint32_t *d_bases, const uint32_t *d_edges)
 {
@@ -264,6 +268,19 @@ extern "C" int vga_genotype_lik_begin(vga_ctx *ctx, uint32_t lambda, uint32_t ca
     if (rc == VGA_OK) rc = gl_zero(ctx, gl);
     if (rc != VGA_OK) gl_release(ps);
     return rc;
+}
+
+extern "C" int vga_genotype_lik_source(vga_ctx *ctx, uint32_t source)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    gl_state *gl = gl_active(ctx);
+    if (!gl) return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_source: the likelihood is off (vga_genotype_lik_begin)");
+    if (source != VGA_GL_FROM_SUPPORT && source != VGA_GL_FROM_EDIT)
+        return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_source: %u is neither VGA_GL_FROM_SUPPORT nor VGA_GL_FROM_EDIT", source);
+    if (source == VGA_GL_FROM_EDIT && !pe_active(ctx))
+        return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_source: the edit distance is off (vga_path_edit_begin)");
+    gl->source = source;
+    return VGA_OK;
 }
 
 extern "C" int vga_genotype_lik_reset(vga_ctx *ctx)

@@ -56,3 +56,6 @@ gl_state *gl_active(vga_ctx *ctx);
 // k_gl_deficit and k_gl_pairs over the n_reads x n_paths matrices of the call that just ended, added into the context's cost table;
 // launched on the context's stream and not waited for
 int gl_add_call(vga_ctx *ctx, gl_state *gl, uint64_t n_reads, const uint32_t *d_bases, const uint32_t *d_edges);
+// which matrices vga_align_batch hands to gl_add_call: VGA_GL_FROM_SUPPORT (path support's) or VGA_GL_FROM_EDIT (m - e and zeros,
+// vga_path_edit.hpp); set by vga_genotype_lik_source
+uint32_t gl_source(const gl_state *gl);

@@ -7,6 +7,7 @@
 #include "vga_path_support.hpp"
 #include "vga_genotype.hpp"
 #include "vga_genotype_lik.hpp"
+#include "vga_path_edit.hpp"
 
 #include <algorithm>
 
@@ -192,7 +193,7 @@ static void ps_launch_score(vga_ctx *ctx, const ps_state *ps, uint32_t n, const 
     vga_timer_end(ctx, t);
 }
 
-int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const std::vector<uint32_t> &reads, uint64_t n_reads)
+int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const std::vector<uint32_t> &reads, uint64_t n_reads, const pe_queries *q)
 {
     const size_t nw = reads.size(), cells = (size_t)n_reads * ps->n_paths;
     hipStream_t st = ctx->stream;
@@ -208,14 +209,27 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(ps->d_rows.p, ps->h_rows.p, nw * 4, hipMemcpyHostToDevice, st));
         ps_launch_score(ctx, ps, (uint32_t)nw, v, ps->d_rows.p, ps->d_bases.p, ps->d_edges.p, ps->d_acc.p);
         VGA_HIP_CHECK(ctx, hipGetLastError());
+        const bool gl_from_edit = ps->gl && gl_source(ps->gl) == VGA_GL_FROM_EDIT;
+        if (gl_from_edit && !ps->pe)
+            return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the likelihood reads the edit distance (vga_genotype_lik_source), which is off (vga_path_edit_begin)");
+        if (ps->pe) {  // the edit distance is on: its three kernels over the same winners, on the same stream
+            if (!q) return vga_set_error(ctx, VGA_ERR_ARG, "path edit: no queries");
+            const int rc = pe_add_call(ctx, ps, v, ps->d_rows.p, nw, n_reads, *q, gl_from_edit);
+            if (rc != VGA_OK) return rc;
+        }
         if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
             const int rc = gt_add_call(ctx, ps->gt, n_reads, ps->d_bases.p, ps->d_edges.p);
             if (rc != VGA_OK) return rc;
         }
         if (ps->gl) {  // the read likelihood is on: the byte deficits of the two matrices and the cost of every pair, on the same stream
-            const int rc = gl_add_call(ctx, ps->gl, n_reads, ps->d_bases.p, ps->d_edges.p);
+            const int rc = gl_from_edit ? gl_add_call(ctx, ps->gl, n_reads, pe_gl_bases(ps->pe), pe_gl_edges(ps->pe))
+                                        : gl_add_call(ctx, ps->gl, n_reads, ps->d_bases.p, ps->d_edges.p);
             if (rc != VGA_OK) return rc;
         }
+    } else if (ps->pe) {  // (no winner: the call's matrix is all NONE)
+        const pe_queries none = {nullptr, nullptr, nullptr};
+        const int rc = pe_add_call(ctx, ps, v, nullptr, 0, n_reads, none, false);
+        if (rc != VGA_OK) return rc;
     }
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     ps->last_reads = n_reads;
@@ -255,6 +269,8 @@ static int ps_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, co
     ctx->index.ps_free = [](void *q) { delete (ps_state *)q; };
     ps->n_paths = n_paths;
     ps->PW = (n_paths + 31u) / 32u;
+    ps->h_off = off;
+    ps->h_steps.assign(h32.begin(), h32.begin() + (long)total);
     const size_t node_words = (size_t)ix.n_nodes * ps->PW, edge_words = (size_t)ix.n_edges * ps->PW;
     hipStream_t st = ctx->stream;
     vga_dbuf<uint32_t> d_steps;

@@ -26,12 +26,16 @@
 
 struct gt_state;
 struct gl_state;
+struct pe_state;
+struct pe_queries;
 // The bitsets and accumulators of a context's index while path support is on (vga_dev_index::ps: released with the index), and
 // the matrices of the most recent vga_align_batch.
 struct ps_state {
     uint32_t n_paths = 0, PW = 0;
     vga_dbuf<uint32_t> d_node_paths, d_edge_paths;  // n_nodes x PW, n_edges x PW
     vga_dbuf<unsigned long long> d_acc;              // sum_bases, sum_edges, top, top_alone (n_paths each), n_alignments, n_unplaced
+    std::vector<unsigned long long> h_off;           // the paths as vga_path_support_begin got them: steps [h_off[p], h_off[p + 1]) of
+    std::vector<uint32_t> h_steps;                   // h_steps, packed handles (vga_path_edit_begin builds the path sequences from them)
     // ---- the last call
     vga_dbuf<uint32_t> d_bases, d_edges, d_rows;
     vga_hbuf<uint32_t> h_rows;
@@ -43,6 +47,9 @@ struct ps_state {
     // ---- the cost table while the read likelihood is on (vga_genotype_lik.hip), released with this state
     gl_state *gl = nullptr;
     void (*gl_free)(gl_state *) = nullptr;
+    // ---- the path sequences and accumulators while the edit distance is on (vga_path_edit.hip), released with this state
+    pe_state *pe = nullptr;
+    void (*pe_free)(pe_state *) = nullptr;
     ps_state() = default;
     ps_state(const ps_state &) = delete;
     ps_state &operator=(const ps_state &) = delete;
@@ -50,10 +57,12 @@ struct ps_state {
     {
         if (gt && gt_free) gt_free(gt);
         if (gl && gl_free) gl_free(gl);
+        if (pe && pe_free) pe_free(pe);
     }
 };
 // the context's path support state while it is on (vga_path_support_begin), else null
 ps_state *ps_active(vga_ctx *ctx);
 // k_ps_score over the staged winners of the call that just ended (reads[i]: the read winner i is reported for), on the context's
-// stream; waits for it.  The call's two n_reads x n_paths matrices are kept on the device for vga_path_support_last.
-int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const std::vector<uint32_t> &reads, uint64_t n_reads);
+// stream; waits for it.  The call's two n_reads x n_paths matrices are kept on the device for vga_path_support_last.  q: the
+// winners' queries, read only while the edit distance is on (ps->pe).
+int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const std::vector<uint32_t> &reads, uint64_t n_reads, const pe_queries *q);

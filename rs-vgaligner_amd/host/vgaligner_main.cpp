@@ -53,7 +53,11 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // GPU (one TSV file); --genotype-lambda N: the cost of one unit of deficit in 1/256 bit (512, 1..4096);
                           // --genotype-cap N: the largest deficit told apart (64, 1..255); --genotype-top applies to it too
                           {"", "--genotype-likelihood", false, "genotype-likelihood"}, {"", "--genotype-lambda", true, "genotype-lambda"},
-                          {"", "--genotype-cap", true, "genotype-cap"}};
+                          {"", "--genotype-cap", true, "genotype-cap"},
+                          // not in the reference: the read of every reported alignment scored against the P lines of --graph by edit
+                          // distance on the GPU (two TSV files); --genotype-from edit|support: which of the two scorings the
+                          // likelihood reads (support)
+                          {"", "--path-edit", false, "path-edit"}, {"", "--genotype-from", true, "genotype-from"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -170,6 +174,14 @@ int map_main(int argc, char **argv)
     };
     likelihood_value("genotype-lambda", 1, 4096, o.genotype_lambda);
     likelihood_value("genotype-cap", 1, 255, o.genotype_cap);
+    o.path_edit = m.count("path-edit") > 0;
+    if (o.path_edit && !o.also_align) throw Error("--path-edit scores alignments: it needs --also-align");
+    if (m.count("genotype-from")) {
+        const std::string v = m["genotype-from"];
+        if (v != "edit" && v != "support") throw Error("--genotype-from takes edit or support: not " + v);
+        if (!o.genotype_likelihood) throw Error("--genotype-from has no meaning without --genotype-likelihood");
+        o.genotype_from_edit = v == "edit";
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -191,14 +203,14 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    // --path-support, --genotype, --genotype-likelihood: the P lines of --graph, and the graph checked against the index, before any
-    // device is opened
+    // --path-support, --genotype, --genotype-likelihood, --path-edit: the P lines of --graph, and the graph checked against the index,
+    // before any device is opened
     std::unique_ptr<HashGraph> graph;
-    const bool scoring = o.path_support || o.genotype || o.genotype_likelihood;
+    const bool scoring = o.path_support || o.genotype || o.genotype_likelihood || o.path_edit;
     if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);
-        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : "--genotype-likelihood: ") + m["graph"] + " has no P line");
+        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : o.genotype_likelihood ? "--genotype-likelihood: " : "--path-edit: ") + m["graph"] + " has no P line");
     } else
         prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
@@ -238,6 +250,9 @@ int map_main(int argc, char **argv)
         else
             fprintf(stderr, "[vgaligner] genotype-likelihood: no call\n");
     }
+    if (o.path_edit)
+        fprintf(stderr, "[vgaligner] path-edit: %llu alignments, %llu paths, %llu too long\n", (unsigned long long)out.n_edit_alignments,
+                (unsigned long long)o.paths.n_paths(), (unsigned long long)out.n_edit_too_long);
     if (o.pileup)
         fprintf(stderr, "[vgaligner] Pileup: %llu alignments piled up, %llu leading insertions\n", (unsigned long long)out.n_pileup,
                 (unsigned long long)out.n_leading_ins);
@@ -283,7 +298,9 @@ int main(int argc, char **argv)
                         "                [--device 0 | --devices 0,1,... | --devices all] [--chunk-reads 32768] [--poa-remain longest|first-edge]\n"
                         "                [--both-strands] [--coverage | --coverage-only] [--path-support] [--pileup]\n"
                         "                [--genotype [--genotype-top 20]]\n"
-                        "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]]\n");
+                        "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]\n"
+                        "                                       [--genotype-from support|edit]]\n"
+                        "                [--path-edit]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -182,6 +182,14 @@ struct MapOptions {
     // also_align.  Every context adds up its own reads; the cost tables are added in 64 bits at the end.
     bool genotype_likelihood = false;
     uint32_t genotype_lambda = 512, genotype_cap = 64;
+    // --path-edit (not in the reference): score, on the GPU, the read of every reported alignment against every P line by edit
+    // distance (vga_path_edit_begin / _read / _last, which needs path support and turns it on without its files) and write
+    // <out>-path-edit.tsv and <out>-path-edit-reads.tsv next to the GAF files.  Needs also_align.  Every context scores its own reads;
+    // the per-path totals are added in 64 bits at the end.
+    bool path_edit = false;
+    // --genotype-from edit: the likelihood reads m - e of the edit distance (vga_genotype_lik_source), which it turns on without its
+    // files; false: path support's matrices
+    bool genotype_from_edit = false;
     PathTable paths;
 };
 
@@ -196,6 +204,7 @@ struct MapOutput {
     uint64_t n_chunks = 0, n_devices = 0;
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
+    uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)
     uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)
     // MapOptions::genotype: the pairs ranked, and the first of them (names of its P lines, its sums); no pair ranked: no call
     uint64_t n_genotype_pairs = 0, genotype_sum_bases = 0, genotype_sum_edges = 0;

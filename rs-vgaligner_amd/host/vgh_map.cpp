@@ -446,6 +446,7 @@ private:
 struct ChunkOut {
     std::vector<std::string> chains, aligns;  // GAF text in read order, in pieces
     std::string path_rows;                    // MapOptions::path_support: the chunk's lines of <out>-path-support-reads.tsv
+    std::string edit_rows;                    // MapOptions::path_edit: the chunk's lines of <out>-path-edit-reads.tsv
     uint64_t n_aligned = 0, n_anchors = 0, poa_cells = 0, n_reverse = 0;
     double ms_map = 0, ms_align = 0;
 };
@@ -573,6 +574,22 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
                         put_u64(out.path_rows, pb[r * np + p]); out.path_rows += '\t'; put_u64(out.path_rows, pe[r * np + p]); out.path_rows += '\n';
                     }
             mark("path support rows");
+        }
+        if (opt.path_edit) {  // the chunk's scored pairs of the reads x paths edit distances, while the context still holds them
+            const size_t np = opt.paths.n_paths();
+            std::vector<uint32_t> ed(n * np + 1);
+            if (vga_path_edit_last(ctx, n, ed.data()) != VGA_OK) {
+                const std::string e = vga_last_error(ctx);
+                wait_k6();
+                throw Error(e);
+            }
+            for (uint64_t r = 0; r < n; r++)
+                for (size_t p = 0; a->aligned[r] && p < np; p++)
+                    if (ed[r * np + p] != 0xFFFFFFFFu) {
+                        put_u64(out.edit_rows, b0 + r); out.edit_rows += '\t'; put_u64(out.edit_rows, p); out.edit_rows += '\t';
+                        put_u64(out.edit_rows, ed[r * np + p]); out.edit_rows += '\n';
+                    }
+            mark("path edit rows");
         }
         // everything the text needs is in host memory now: the batch and, if the caller says so, the context can go
         wait_k6();
@@ -813,6 +830,64 @@ void path_support_write(const MapOptions &opt, PathSum s, const std::string &row
     write_file(out_prefix + "-path-support-reads.tsv", "read\tpath\tbases\tedges\n" + rows);
 }
 
+// ---- path edit (MapOptions::path_edit): the per-path totals of the contexts, added in 64 bits, and the two TSV files
+struct EditSum {
+    std::vector<uint64_t> v[4];  // n_scored, sum_edit, best, best_alone
+    uint64_t n = 0, too_long = 0;
+    void add(const EditSum &o)
+    {
+        for (int k = 0; k < 4; k++) {
+            if (v[k].size() < o.v[k].size()) v[k].resize(o.v[k].size(), 0);
+            for (size_t p = 0; p < o.v[k].size(); p++) v[k][p] += o.v[k][p];
+        }
+        n += o.n;
+        too_long += o.too_long;
+    }
+};
+
+// the edit distance is scored: for its own files, or for the likelihood
+bool edit_on(const MapOptions &opt) { return opt.path_edit || (opt.genotype_likelihood && opt.genotype_from_edit); }
+
+// what the context has accumulated so far joins `s`
+void path_edit_take(vga_ctx *ctx, const MapOptions &opt, EditSum &s)
+{
+    EditSum t;
+    for (auto &x : t.v) x.assign(opt.paths.n_paths(), 0);
+    if (vga_path_edit_read(ctx, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data(), &t.n, &t.too_long) != VGA_OK) throw Error(vga_last_error(ctx));
+    s.add(t);
+}
+
+// (length: |seq_p|, the bases of all the steps of the path, whichever way they are visited)
+void path_edit_write(const Index &ix, const MapOptions &opt, EditSum s, const std::string &rows, const std::string &out_prefix)
+{
+    if (out_prefix.empty()) return;
+    const size_t np = opt.paths.n_paths();
+    std::string paths = "path\tsteps\tlength\tscored\tsum_edit\tbest\tbest_alone\n";
+    for (size_t p = 0; p < np; p++) {
+        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
+        uint64_t len = 0;
+        for (uint64_t t = opt.paths.step_off[p]; t < opt.paths.step_off[p + 1]; t++) {
+            const uint64_t id = id_of(opt.paths.steps[t]);
+            len += ix.node_ref[id].seq_idx - ix.node_ref[id - 1].seq_idx;
+        }
+        put_u64(paths, len);
+        for (auto &x : s.v) { x.resize(np, 0); paths += '\t'; put_u64(paths, x[p]); }
+        paths += '\n';
+    }
+    write_file(out_prefix + "-path-edit.tsv", paths);
+    write_file(out_prefix + "-path-edit-reads.tsv", "read\tpath\tedit\n" + rows);
+}
+
+// path support and what is built on it, on one context
+void scoring_begin(vga_ctx *ctx, const MapOptions &opt)
+{
+    path_support_begin(ctx, opt);
+    if (edit_on(opt) && vga_path_edit_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
+    if (opt.genotype && vga_genotype_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
+    if (opt.genotype_likelihood && vga_genotype_lik_begin(ctx, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) throw Error(vga_last_error(ctx));
+    if (opt.genotype_likelihood && opt.genotype_from_edit && vga_genotype_lik_source(ctx, VGA_GL_FROM_EDIT) != VGA_OK) throw Error(vga_last_error(ctx));
+}
+
 // ---- genotype (MapOptions::genotype): the pair tables of the contexts, added in 64 bits, the ranking and the TSV file
 struct PairSum {
     std::vector<uint64_t> v[4];  // sum_bases, sum_edges, prefer_a, prefer_b at vga_pair_index
@@ -927,6 +1002,9 @@ void check_aligner(const MapOptions &opt)
     if (opt.genotype_likelihood && !opt.also_align) throw Error("--genotype-likelihood calls from alignments: it needs --also-align");
     if (opt.genotype_likelihood && opt.paths.n_paths() == 0) throw Error("--genotype-likelihood: the graph has no P line");
     if (opt.genotype_likelihood && !likelihood_params_ok(opt)) throw Error("--genotype-likelihood: --genotype-lambda is 1 to 4096 and --genotype-cap 1 to 255");
+    if (opt.genotype_from_edit && !opt.genotype_likelihood) throw Error("--genotype-from has no meaning without --genotype-likelihood");
+    if (opt.path_edit && !opt.also_align) throw Error("--path-edit scores alignments: it needs --also-align");
+    if (opt.path_edit && opt.paths.n_paths() == 0) throw Error("--path-edit: the graph has no P line");
     if (opt.genotype && !opt.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
     if (opt.genotype && opt.paths.n_paths() == 0) throw Error("--genotype: the graph has no P line");
     if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
@@ -969,12 +1047,10 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     out.n_reads = inputs.size();
     out.n_devices = 1;
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood;  // (either genotype switch turns the scoring on, not its files)
-    if (scoring) path_support_begin(ctx, opt);
-    if (opt.genotype && vga_genotype_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    if (opt.genotype_likelihood && vga_genotype_lik_begin(ctx, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) throw Error(vga_last_error(ctx));
+    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit;  // (each of the others turns the scoring on, not its files)
+    if (scoring) scoring_begin(ctx, opt);
     if (opt.pileup && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    std::string path_rows;
+    std::string path_rows, edit_rows;
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
     for (const Shard &s : plan_shards(len, 1, opt.chunk_reads)) {
@@ -983,6 +1059,7 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         append_pieces(out.chains_gaf, c.chains);
         append_pieces(out.alignments_gaf, c.aligns);
         path_rows += c.path_rows;
+        edit_rows += c.edit_rows;
         out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells; out.n_reverse += c.n_reverse;
         out.ms_map += c.ms_map; out.ms_align += c.ms_align;
         out.n_chunks++;
@@ -1004,10 +1081,16 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         likelihood_take(ctx, opt, s);
         likelihood_write(opt, std::move(s), out, out_prefix);
     }
+    if (edit_on(opt)) {
+        EditSum s;
+        path_edit_take(ctx, opt, s);
+        out.n_edit_alignments = s.n; out.n_edit_too_long = s.too_long;
+        if (opt.path_edit) path_edit_write(ix, opt, std::move(s), edit_rows, out_prefix);
+    }
     if (scoring) {
         PathSum s;
         path_support_take(ctx, opt, s);
-        (void)vga_path_support_end(ctx);  // (and genotyping with it)
+        (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
         out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
         if (opt.path_support) path_support_write(opt, s, path_rows, out_prefix);
     }
@@ -1109,14 +1192,10 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     if (coverage)
         for (vga_ctx *c : ctxs)
             if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood;  // (either genotype switch turns the scoring on, not its files)
+    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit;  // (each of the others turns the scoring on, not its files)
     if (scoring)
         for (vga_ctx *c : ctxs) {
-            try { path_support_begin(c, opt); } catch (const Error &) { release(); throw; }
-            if (opt.genotype && vga_genotype_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-            if (opt.genotype_likelihood && vga_genotype_lik_begin(c, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) {
-                const std::string e = vga_last_error(c); release(); throw Error(e);
-            }
+            try { scoring_begin(c, opt); } catch (const Error &) { release(); throw; }
         }
     if (opt.pileup)
         for (vga_ctx *c : ctxs)
@@ -1126,12 +1205,14 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     std::vector<PathSum> slot_paths(n_slots);
     std::vector<PairSum> slot_pairs(n_slots);
     std::vector<CostSum> slot_costs(n_slots);
+    std::vector<EditSum> slot_edit(n_slots);
     // what the slot's context has counted and scored, read once its last chunk is off the GPU
     auto take_tables = [&](uint32_t slot) {
         if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
         if (scoring) path_support_take(ctxs[slot], opt, slot_paths[slot]);
         if (opt.genotype) genotype_take(ctxs[slot], opt, slot_pairs[slot]);
         if (opt.genotype_likelihood) likelihood_take(ctxs[slot], opt, slot_costs[slot]);
+        if (edit_on(opt)) path_edit_take(ctxs[slot], opt, slot_edit[slot]);
         if (opt.pileup) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
     };
     const bool tables = coverage || scoring || opt.pileup;
@@ -1287,6 +1368,18 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (const CostSum &c : slot_costs) sum.add(c);
         likelihood_write(opt, std::move(sum), out, out_prefix);
         trace_mark("genotype likelihood table written");
+    }
+    if (edit_on(opt)) {
+        EditSum sum;
+        for (auto &x : sum.v) x.assign(opt.paths.n_paths(), 0);
+        for (const EditSum &c : slot_edit) sum.add(c);
+        out.n_edit_alignments = sum.n; out.n_edit_too_long = sum.too_long;
+        if (opt.path_edit) {
+            std::string rows;
+            for (size_t i = 0; i < plan.size(); i++) rows += parts[i].edit_rows;  // read order
+            path_edit_write(ix, opt, std::move(sum), rows, out_prefix);
+            trace_mark("path edit tables written");
+        }
     }
     if (scoring) {
         PathSum sum;
