@@ -520,6 +520,48 @@ int vga_path_edit_pairs(vga_ctx *ctx, uint64_t n, const uint64_t *q_off /* n + 1
                         const char *t, uint32_t *out /* n */);
 int vga_genotype_lik_source(vga_ctx *ctx, uint32_t source);
 
+/* ---- variant call: where the reads disagree with the graph, called from the pileup on the GPU ----------
+ * Stands in for nothing in the reference.  It is the first consumer of the pileup table that stays on the device: an
+ * integer-only diploid call at every graph base, the sites compacted there, so that only the calls cross PCIe.  Defined on the
+ * pileup table and the graph's letters and on nothing else (tests/variant_ref.py recomputes it, from the alignments GAF too).
+ * Costs are in 1/256 bit, like the genotype likelihood's.
+ *   inputs     for base i its pileup row A C G T N del ins, exactly as vga_pileup_read returns it, and its letter;
+ *              r = the column of the letter (A C G T in either case 0..3, anything else N);  depth = A + C + G + T + N + del.
+ *              The alleles are A < C < G < T < D, D a deleted base with n_D = del.  The N column counts towards depth only.
+ *   parameters E, the cost of an observation that neither allele of the genotype explains (257..8192; 1280 in the CLI),
+ *              min_depth (at least 1; 4) and min_qual (512).  The defaults are choices, not measurements.
+ *   tested     a base with r < 4 and depth >= min_depth.  A base whose own letter is not A C G T is never tested.
+ *   genotype   for every unordered pair x <= y of the five alleles (15 pairs) cost(x, y) = sum over a of n_a w(a; x, y) in 64 bits:
+ *              w = 0 for a == x under a homozygous pair, 256 for a == x or a == y under a heterozygous one, E for any other
+ *              observation.  The pairs are enumerated as (r, r), then the four pairs that hold r by their other allele ascending,
+ *              then the remaining ten by (x, y) ascending; the first minimum in that order is the genotype, so the reference
+ *              genotype wins every tie.  qual = the smallest cost among the other fourteen pairs minus the best, saturated at
+ *              2^32 - 1.
+ *   insertion  behind the base, with k = min(ins, depth): none costs ins E, het 256 depth, hom (depth - k) E; the first minimum
+ *              in that order wins, ins_qual = the second smallest cost minus the best (64 bits, not saturated).
+ *   reported   a tested base whose genotype is not (r, r) with qual >= min_qual, or whose insertion state is not none with
+ *              ins_qual >= min_qual.
+ * The calls come in base order as parallel arrays: pos (the base), gt (x | y << 3 | state << 6, alleles 0..4 = A C G T D, state
+ * 0 none, 1 het, 2 hom), qual, ins_qual, depth and -- what a caller needs to print a site without fetching the table -- counts,
+ * the base's seven counters widened to 64 bits (cap x 7, row-major; may be NULL).  The first min(n_calls, cap) are written,
+ * *n_calls is the total and *n_tested the tested bases (either may be NULL); the arrays may be NULL when cap is 0.  A counter of
+ * 2^32 - 1 is an ordinary value.  The inserted letters are not called, the sites are independent, and a base on one arm of a
+ * bubble sees only the reads that went through that arm.
+ *   vga_variant_call        from the context's own counters, after the prefix pass vga_pileup_read does too.  Needs
+ *                           vga_pileup_begin (VGA_ERR_ARG otherwise, and for E or min_depth out of range or a NULL array with
+ *                           cap > 0); VGA_ERR_UNSUPPORTED where vga_pileup_read refuses.  Does not reset the counters.
+ *   vga_variant_call_table  the kernel seam, and the route of several contexts whose tables were added in 64 bits: an explicit
+ *                           table of n rows (counts_in: n x 7, letters: n) through the same kernels.  Needs a context only: no
+ *                           index, no counters touched.  VGA_ERR_UNSUPPORTED for a counter of 2^40 or more (found on the
+ *                           device) and for n of 2^31 or more.  n = 0 gives no call.
+ * Neither is called by vga_align_batch: with no call made nothing is launched or allocated. */
+int vga_variant_call(vga_ctx *ctx, uint32_t E, uint64_t min_depth, uint64_t min_qual, uint64_t cap, uint32_t *pos, uint8_t *gt,
+                     uint32_t *qual, uint64_t *ins_qual, uint64_t *depth, uint64_t *counts /* cap * 7 */, uint64_t *n_tested,
+                     uint64_t *n_calls);
+int vga_variant_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *counts_in /* n * 7 */, const char *letters /* n */, uint32_t E,
+                           uint64_t min_depth, uint64_t min_qual, uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual,
+                           uint64_t *ins_qual, uint64_t *depth, uint64_t *counts /* cap * 7 */, uint64_t *n_tested, uint64_t *n_calls);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "vga_genotype_lik_table", "vga_genotype_lik_begin", "vga_genotype_lik_read", "vga_genotype_lik_reset", "vga_genotype_lik_end",
     "vga_genotype_lik_pairs", "vga_genotype_lik_source",
     "vga_path_edit_begin", "vga_path_edit_read", "vga_path_edit_last", "vga_path_edit_reset", "vga_path_edit_end", "vga_path_edit_pairs",
+    "vga_variant_call", "vga_variant_call_table",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -74,6 +75,19 @@ PATH_EDIT_NONE = 0xFFFFFFFF
 PATH_EDIT_MAX_R = 4
 PATH_EDIT_MAX_QUERY = 64 * 64 * PATH_EDIT_MAX_R
 PATH_EDIT_FIELDS = ("n_scored", "sum_edit", "best", "best_alone")
+
+# k_vc_count / k_vc_emit (csrc/vga_variant.hpp): the bases of a workgroup, the range of the error cost E, the counters and the
+# rows vga_variant_call_table serves, and the defaults of Context.variant_call and of `vgaligner map --call-variants`
+VARIANT_BLOCK = 256
+VARIANT_MIN_ERROR = 257
+VARIANT_MAX_ERROR = 8192
+VARIANT_MAX_COUNT = 1 << 40
+VARIANT_MAX_BASES = 1 << 31
+VARIANT_ERROR = 1280
+VARIANT_MIN_DEPTH = 4
+VARIANT_MIN_QUAL = 512
+VARIANT_ALLELES = "ACGT-"  # alleles 0..4 as <out>-variants.tsv writes them: D, the deleted base, is '-'
+VARIANT_INS_STATES = (".", "het", "hom")
 
 
 class VgaError(RuntimeError):
@@ -255,6 +269,12 @@ def load_library():
         for name in ABI_SYMBOLS:
             if name.startswith("vga_path_edit_"):
                 getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_variant_call"):  # (absent from an older build named by VGA_LIB; the Context.variant_call* calls then fail)
+        u64p, u32p, u64 = _P(C.c_uint64), _P(C.c_uint32), C.c_uint64
+        outs = [u64, u32p, _P(C.c_uint8), u32p, u64p, u64p, u64p, u64p, u64p]
+        L.vga_variant_call.argtypes = [vp, C.c_uint32, u64, u64] + outs
+        L.vga_variant_call_table.argtypes = [vp, u64, u64p, C.c_char_p, C.c_uint32, u64, u64] + outs
+        L.vga_variant_call.restype = L.vga_variant_call_table.restype = C.c_int
     _lib = L
     return L
 
@@ -721,6 +741,40 @@ class Context:
     def pileup_end(self) -> None:
         """vga_pileup_end: free the table, stop counting"""
         self._check(self.L.vga_pileup_end(self.h))
+
+    def _variant(self, call, cap) -> dict:
+        """`call(cap, *outs)` is one of the two C calls with everything before cap bound: asks again with a larger cap when the
+        first answer holds more calls than it had room for"""
+        cap = max(0, int(cap))
+        while True:
+            m = max(1, cap)
+            pos, gt, qual = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint32)
+            insq, depth, rows = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64), np.zeros((m, len(PILEUP_COLUMNS)), dtype=np.uint64)
+            nt, nc = C.c_uint64(0), C.c_uint64(0)
+            self._check(call(cap, _u32p(pos), gt.ctypes.data_as(_P(C.c_uint8)), _u32p(qual), _u64p(insq), _u64p(depth), _u64p(rows), C.byref(nt), C.byref(nc)))
+            n = int(nc.value)
+            if n <= cap:
+                break
+            cap = n
+        return {"pos": pos[:n], "x": gt[:n] & 7, "y": (gt[:n] >> 3) & 7, "ins": gt[:n] >> 6, "qual": qual[:n], "ins_qual": insq[:n],
+                "depth": depth[:n], "counts": rows[:n], "n_tested": int(nt.value), "n_calls": n}
+
+    def variant_call(self, error: int = VARIANT_ERROR, min_depth: int = VARIANT_MIN_DEPTH, min_qual: int = VARIANT_MIN_QUAL, cap: int = 1024) -> dict:
+        """vga_variant_call: the diploid call at every graph base from this context's pileup counters (needs pileup_begin; does
+        not reset) -> {pos, x, y (alleles 0..4 = A C G T D), ins (0 none, 1 het, 2 hom), qual, ins_qual, depth, counts[n, 7]:
+        arrays over the reported bases in base order, n_tested, n_calls}.  cap: the calls the first request has room for."""
+        return self._variant(lambda c, *outs: self.L.vga_variant_call(self.h, int(error), int(min_depth), int(min_qual), c, *outs), cap)
+
+    def variant_call_table(self, counts, letters, error: int = VARIANT_ERROR, min_depth: int = VARIANT_MIN_DEPTH, min_qual: int = VARIANT_MIN_QUAL,
+                           cap: int = 1024) -> dict:
+        """vga_variant_call_table, the kernel seam: the same call from an explicit table counts[n, 7] (uint64) and its n letters
+        (str or bytes).  Needs a context only."""
+        tab = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1, len(PILEUP_COLUMNS))
+        let = letters.encode() if isinstance(letters, str) else bytes(letters)
+        if len(let) != len(tab):
+            raise ValueError(f"{len(tab)} rows and {len(let)} letters")
+        return self._variant(lambda c, *outs: self.L.vga_variant_call_table(self.h, len(tab), _u64p(tab), let, int(error), int(min_depth), int(min_qual),
+                                                                           c, *outs), cap)
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

@@ -415,6 +415,20 @@ extern "C" int vga_pileup_end(vga_ctx *ctx)
     return VGA_OK;
 }
 
+int pu_finish_device(vga_ctx *ctx, pu_state *pu, const char *who, const uint32_t **table, uint32_t *seq_length)
+{
+    if (pu->n_alignments >= 0xFFFFFFFFull)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu alignments counted: a 32-bit counter may have wrapped", who,
+                             (unsigned long long)pu->n_alignments);
+    if (pu->seq_length) {
+        hipLaunchKernelGGL(k_pu_finish, dim3(1), dim3(1024), 0, ctx->stream, pu->d_mdiff.p, pu->d_counts.p, ctx->index.d_seq_fwd, pu->d_out.p, pu->seq_length);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+    }
+    *table = pu->d_out.p;
+    *seq_length = pu->seq_length;
+    return VGA_OK;
+}
+
 extern "C" int vga_pileup_read(vga_ctx *ctx, uint32_t *counts, uint64_t *n_alignments, uint64_t *leading_ins)
 {
     if (!ctx) return VGA_ERR_ARG;
@@ -426,9 +440,11 @@ extern "C" int vga_pileup_read(vga_ctx *ctx, uint32_t *counts, uint64_t *n_align
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     if (counts && pu->seq_length) {
-        hipLaunchKernelGGL(k_pu_finish, dim3(1), dim3(1024), 0, st, pu->d_mdiff.p, pu->d_counts.p, ctx->index.d_seq_fwd, pu->d_out.p, pu->seq_length);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(counts, pu->d_out.p, (size_t)pu->seq_length * PU_COLS * 4, hipMemcpyDeviceToHost, st));
+        const uint32_t *table = nullptr;
+        uint32_t n = 0;
+        const int rc = pu_finish_device(ctx, pu, "vga_pileup_read", &table, &n);
+        if (rc != VGA_OK) return rc;
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(counts, table, (size_t)n * PU_COLS * 4, hipMemcpyDeviceToHost, st));
         VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
     if (n_alignments) *n_alignments = pu->n_alignments;

@@ -52,3 +52,6 @@ void pu_keep_from_ops(pu_state *pu, uint32_t p, const uint8_t *ops, const uint32
                       const uint32_t *handles, const std::vector<uint32_t> &node_start, const char *bases, uint32_t n_rows, const char *query);
 // k_pu_add over the lists of the winners (problem indices of the call that just ended), on the context's stream; waits for it
 int pu_add_winners(vga_ctx *ctx, pu_state *pu, const std::vector<uint32_t> &winners);
+// k_pu_finish on the context's stream, not waited for: the table vga_pileup_read copies out (seq_length x PU_COLS), left on the
+// device for vga_variant.hip.  VGA_ERR_UNSUPPORTED once a 32-bit counter may have wrapped.
+int pu_finish_device(vga_ctx *ctx, pu_state *pu, const char *who, const uint32_t **table, uint32_t *seq_length);

@@ -57,7 +57,13 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: the read of every reported alignment scored against the P lines of --graph by edit
                           // distance on the GPU (two TSV files); --genotype-from edit|support: which of the two scorings the
                           // likelihood reads (support)
-                          {"", "--path-edit", false, "path-edit"}, {"", "--genotype-from", true, "genotype-from"}};
+                          {"", "--path-edit", false, "path-edit"}, {"", "--genotype-from", true, "genotype-from"},
+                          // not in the reference: a diploid call at every graph base from the pileup counters, made on the GPU (one TSV
+                          // file with the bases where the reads disagree with the graph); --call-error N: the cost of an observation
+                          // neither allele explains in 1/256 bit (1280, 257..8192); --call-min-depth N: the depth from which a base is
+                          // tested (4, at least 1); --call-min-qual N: the margin from which a call is reported (512)
+                          {"", "--call-variants", false, "call-variants"}, {"", "--call-error", true, "call-error"},
+                          {"", "--call-min-depth", true, "call-min-depth"}, {"", "--call-min-qual", true, "call-min-qual"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -182,6 +188,22 @@ int map_main(int argc, char **argv)
         if (!o.genotype_likelihood) throw Error("--genotype-from has no meaning without --genotype-likelihood");
         o.genotype_from_edit = v == "edit";
     }
+    o.call_variants = m.count("call-variants") > 0;
+    if (o.call_variants && !o.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
+    // --call-error, --call-min-depth, --call-min-qual: a number inside the range of vga_variant_call, and only beside --call-variants
+    auto call_value = [&](const char *key, uint64_t lo, uint64_t hi, uint64_t &into) {
+        if (!m.count(key)) return;
+        const std::string v = m[key], flag = std::string("--") + key;
+        if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos || std::stoull(v) < lo || std::stoull(v) > hi)
+            throw Error(flag + " takes a number " + (hi == UINT64_MAX ? "of at least " + std::to_string(lo) : "from " + std::to_string(lo) + " to " + std::to_string(hi)) + ": not " + v);
+        if (!o.call_variants) throw Error(flag + " has no meaning without --call-variants");
+        into = std::stoull(v);
+    };
+    uint64_t call_error = o.call_error;
+    call_value("call-error", 257, 8192, call_error);
+    o.call_error = (uint32_t)call_error;
+    call_value("call-min-depth", 1, UINT64_MAX, o.call_min_depth);
+    call_value("call-min-qual", 0, UINT64_MAX, o.call_min_qual);
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -256,6 +278,8 @@ int map_main(int argc, char **argv)
     if (o.pileup)
         fprintf(stderr, "[vgaligner] Pileup: %llu alignments piled up, %llu leading insertions\n", (unsigned long long)out.n_pileup,
                 (unsigned long long)out.n_leading_ins);
+    if (o.call_variants)
+        fprintf(stderr, "[vgaligner] call-variants: %llu bases tested, %llu calls\n", (unsigned long long)out.n_variant_tested, (unsigned long long)out.n_variant_calls);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -300,7 +324,8 @@ int main(int argc, char **argv)
                         "                [--genotype [--genotype-top 20]]\n"
                         "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]\n"
                         "                                       [--genotype-from support|edit]]\n"
-                        "                [--path-edit]\n");
+                        "                [--path-edit]\n"
+                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -190,6 +190,14 @@ struct MapOptions {
     // --genotype-from edit: the likelihood reads m - e of the edit distance (vga_genotype_lik_source), which it turns on without its
     // files; false: path support's matrices
     bool genotype_from_edit = false;
+    // --call-variants (not in the reference): an integer-only diploid call at every graph base, made on the GPU from the pileup
+    // counters (vga_variant_call; several contexts: their tables added in 64 bits, then vga_variant_call_table on the first), and
+    // <out>-variants.tsv with the bases where the reads disagree with the graph.  Turns the pileup counting on without its file.
+    // call_error: the cost of an observation that neither allele explains in 1/256 bit (257..8192); call_min_depth: the depth from
+    // which a base is tested (at least 1); call_min_qual: the margin from which a call is reported.  Needs also_align.
+    bool call_variants = false;
+    uint32_t call_error = 1280;
+    uint64_t call_min_depth = 4, call_min_qual = 512;
     PathTable paths;
 };
 
@@ -203,6 +211,7 @@ struct MapOutput {
     double ms_map = 0, ms_align = 0;     // summed over chunks (per device: the maximum over devices)
     uint64_t n_chunks = 0, n_devices = 0;
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
+    uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)
     uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)

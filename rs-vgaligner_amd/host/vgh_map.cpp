@@ -787,6 +787,70 @@ void pileup_write(const Index &ix, PileupSum s, const std::string &out_prefix)
     write_file(out_prefix + "-pileup.tsv", t);
 }
 
+// ---- variant calls (MapOptions::call_variants): the calls as the library returns them, and the TSV file
+struct VariantCalls {
+    std::vector<uint32_t> pos, qual;
+    std::vector<uint8_t> gt;
+    std::vector<uint64_t> ins_qual, depth, counts;  // counts: 7 per call
+    uint64_t n_tested = 0, n_calls = 0;
+};
+
+// `call(cap, arrays..)` is one of the two library calls with everything before cap bound: asked again when the first answer holds
+// more calls than it had room for
+template <typename F>
+void variant_fetch(vga_ctx *ctx, VariantCalls &v, F call)
+{
+    uint64_t cap = 4096;
+    for (;;) {
+        v.pos.resize(cap); v.qual.resize(cap); v.gt.resize(cap); v.ins_qual.resize(cap); v.depth.resize(cap); v.counts.resize(cap * 7);
+        if (call(cap, v.pos.data(), v.gt.data(), v.qual.data(), v.ins_qual.data(), v.depth.data(), v.counts.data(), &v.n_tested, &v.n_calls) != VGA_OK)
+            throw Error(vga_last_error(ctx));
+        if (v.n_calls <= cap) break;
+        cap = v.n_calls;
+    }
+}
+
+// from the context's own counters
+void variant_take(vga_ctx *ctx, const MapOptions &opt, VariantCalls &v)
+{
+    variant_fetch(ctx, v, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
+        return vga_variant_call(ctx, opt.call_error, opt.call_min_depth, opt.call_min_qual, cap, pos, gt, qual, iq, depth, counts, nt, nc);
+    });
+}
+
+// from the tables of several contexts, added in 64 bits
+void variant_take_table(vga_ctx *ctx, const Index &ix, const MapOptions &opt, PileupSum s, VariantCalls &v)
+{
+    s.counts.resize(ix.seq_length * 7, 0);
+    variant_fetch(ctx, v, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
+        return vga_variant_call_table(ctx, ix.seq_length, s.counts.data(), ix.seq_fwd.data(), opt.call_error, opt.call_min_depth, opt.call_min_qual, cap, pos, gt,
+                                      qual, iq, depth, counts, nt, nc);
+    });
+}
+
+void variant_write(const Index &ix, const VariantCalls &v, MapOutput &out, const std::string &out_prefix)
+{
+    out.n_variant_tested = v.n_tested; out.n_variant_calls = v.n_calls;
+    if (out_prefix.empty()) return;
+    static const char ALLELES[] = "ACGT-";
+    static const char *const STATES[] = {".", "het", "hom"};
+    std::string t = "node\toffset\tref\tgt\tqual\tins\tins_qual\tdepth\tA\tC\tG\tT\tN\tdel\tins_count\n";
+    uint64_t id = 1;  // the calls come in base order: the node moves forward only
+    for (uint64_t j = 0; j < v.n_calls; j++) {
+        const uint64_t p = v.pos[j];
+        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= p) id++;
+        const uint32_t g = v.gt[j];
+        put_u64(t, id); t += '\t'; put_u64(t, p - ix.node_ref[id - 1].seq_idx); t += '\t'; t += ix.seq_fwd[p]; t += '\t';
+        t += ALLELES[g & 7u]; t += '/'; t += ALLELES[(g >> 3) & 7u]; t += '\t'; put_u64(t, v.qual[j]); t += '\t';
+        t += STATES[(g >> 6) < 3u ? (g >> 6) : 0u]; t += '\t'; put_u64(t, v.ins_qual[j]); t += '\t'; put_u64(t, v.depth[j]);
+        for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, v.counts[j * 7 + (uint64_t)c]); }
+        t += '\n';
+    }
+    write_file(out_prefix + "-variants.tsv", t);
+}
+
+bool variant_params_ok(const MapOptions &opt) { return opt.call_error >= 257 && opt.call_error <= 8192 && opt.call_min_depth >= 1; }
+
 // ---- path support (MapOptions::path_support): the per-path totals of the contexts, added in 64 bits, and the two TSV files
 struct PathSum {
     std::vector<uint64_t> v[4];  // sum_bases, sum_edges, top, top_alone
@@ -1010,6 +1074,8 @@ void check_aligner(const MapOptions &opt)
     if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
     if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
     if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
+    if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
+    if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -1049,7 +1115,8 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
     if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit;  // (each of the others turns the scoring on, not its files)
     if (scoring) scoring_begin(ctx, opt);
-    if (opt.pileup && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
+    const bool piling = opt.pileup || opt.call_variants;  // (the call turns the counting on, not its file)
+    if (piling && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
     std::string path_rows, edit_rows;
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
@@ -1094,13 +1161,18 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
         out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
         if (opt.path_support) path_support_write(opt, s, path_rows, out_prefix);
     }
+    if (opt.call_variants) {
+        VariantCalls v;
+        variant_take(ctx, opt, v);
+        variant_write(ix, v, out, out_prefix);
+    }
     if (opt.pileup) {
         PileupSum s;
         pileup_take(ctx, ix, s);
-        (void)vga_pileup_end(ctx);
         out.n_pileup = s.n; out.n_leading_ins = s.leading;
         pileup_write(ix, s, out_prefix);
     }
+    if (piling) (void)vga_pileup_end(ctx);
     finish(out, ix, inputs, opt, out_prefix);
     return out;
 }
@@ -1197,9 +1269,14 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (vga_ctx *c : ctxs) {
             try { scoring_begin(c, opt); } catch (const Error &) { release(); throw; }
         }
-    if (opt.pileup)
+    const bool piling = opt.pileup || opt.call_variants;  // (the call turns the counting on, not its file)
+    if (piling)
         for (vga_ctx *c : ctxs)
             if (vga_pileup_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
+    // --call-variants: one context calls from its own counters as soon as its last chunk is counted; several hand their tables
+    // over, and the first context stays until it has called from their sum
+    const bool call_alone = opt.call_variants && n_slots == 1, call_summed = opt.call_variants && n_slots > 1;
+    VariantCalls variants;
     std::vector<PileupSum> slot_pileup(n_slots);
     std::vector<CoverageSum> slot_cov(n_slots);
     std::vector<PathSum> slot_paths(n_slots);
@@ -1213,9 +1290,17 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         if (opt.genotype) genotype_take(ctxs[slot], opt, slot_pairs[slot]);
         if (opt.genotype_likelihood) likelihood_take(ctxs[slot], opt, slot_costs[slot]);
         if (edit_on(opt)) path_edit_take(ctxs[slot], opt, slot_edit[slot]);
-        if (opt.pileup) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
+        // (VGA_TRACE: what each of the two routes to the sites costs at the device's end, tests/prof_variant.py)
+        const auto t0 = std::chrono::steady_clock::now();
+        if (opt.pileup || call_summed) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (call_alone) variant_take(ctxs[slot], opt, variants);
+        if (piling && getenv("VGA_TRACE"))
+            fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
+                    std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
     };
-    const bool tables = coverage || scoring || opt.pileup;
+    const bool tables = coverage || scoring || piling;
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -1291,6 +1376,7 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
                         if (opt.leave_contexts && i == last_of_slot[slot])
                             hooks.gpu_done = [&, slot]() {
                                 take_tables(slot);  // (the slot's last chunk has been counted)
+                                if (call_summed && slot == 0) return;  // (it still has the summed table to call from)
                                 vga_ctx *c = ctxs[slot];
                                 ctxs[slot] = nullptr;
                                 std::lock_guard<std::mutex> lk(destroyers_mu);
@@ -1314,6 +1400,22 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     bool any_error = false;
     for (const std::string &e : errors) any_error = any_error || !e.empty();
     for (const std::string &e : writer_err) any_error = any_error || !e.empty();
+    if (call_summed && !any_error) {
+        try {
+            PileupSum sum;
+            for (const PileupSum &c : slot_pileup) sum.add(c);
+            variant_take_table(ctxs[0], ix, opt, std::move(sum), variants);
+            trace_mark("variants called");
+        } catch (const std::exception &e) {
+            errors[0] = e.what();
+            any_error = true;
+        }
+        if (opt.leave_contexts && !any_error) {
+            vga_ctx *c = ctxs[0];
+            ctxs[0] = nullptr;
+            destroyers.emplace_back([c]() { vga_ctx_destroy(c); });
+        }
+    }
     if (opt.leave_contexts && !any_error) {
         // the caller leaves the process next (vgaligner: _exit once the files are closed): whatever the tear-down threads have not
         // finished, the exit finishes
@@ -1398,6 +1500,10 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
             path_support_write(opt, sum, rows, out_prefix);
             trace_mark("path support tables written");
         }
+    }
+    if (opt.call_variants) {
+        variant_write(ix, variants, out, out_prefix);
+        trace_mark("variants written");
     }
     if (opt.pileup) {
         PileupSum sum;
