@@ -228,7 +228,7 @@ int map_main(int argc, char **argv)
     // --path-support, --genotype, --genotype-likelihood, --path-edit: the P lines of --graph, and the graph checked against the index,
     // before any device is opened
     std::unique_ptr<HashGraph> graph;
-    const bool scoring = o.path_support || o.genotype || o.genotype_likelihood || o.path_edit;
+    const bool scoring = scoring_on(o);
     if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);

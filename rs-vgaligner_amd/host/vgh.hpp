@@ -200,6 +200,8 @@ struct MapOptions {
     uint64_t call_min_depth = 4, call_min_qual = 512;
     PathTable paths;
 };
+// the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
+bool scoring_on(const MapOptions &opt);
 
 // VGA_TRACE=1: wall-clock marks of the driver's phases on stderr (since the first call)
 void trace_mark(const char *what);

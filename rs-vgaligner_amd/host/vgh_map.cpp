@@ -7,7 +7,7 @@
 //   map_reads .................. src/map.rs:27-216, write_gaf_to_file 219-226
 // The reference's debug printing inside the hot loops is not part of the contract and is not reproduced.
 #include "vgh.hpp"
-#include "../csrc/vga_pair_index.hpp"
+#include "vgh_tables.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -83,13 +83,6 @@ std::string gaf_placeholder(const QuerySequence &q)
 }
 
 namespace {
-inline void put_u64(std::string &s, uint64_t v)
-{
-    char t[24];
-    int n = 0;
-    do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (n) s.push_back(t[--n]);
-}
 // columns 3-5 of a chain record: "qs\tqe\t+\t".  A read mapped on its reverse complement (strand 1: qb / qe count from the start of
 // the reverse complement) gets the read's own frame, qs = L - qe and qe = L - qs, and '-'.
 inline void put_chain_query(std::string &s, uint64_t L, const vga_map_result *m, uint64_t read, uint64_t qb, uint64_t qe)
@@ -280,14 +273,6 @@ std::string validation_record(const Index &ix, const std::string &gaf_line, cons
     return out + "]\n\n";
 }
 
-static void write_file(const std::string &name, const std::string &body)
-{
-    std::ofstream o(name, std::ios::binary);
-    if (!o) throw Error("Couldn't create file " + name);
-    o.write(body.data(), body.size());
-    if (!o) throw Error("Couldn't write to file " + name);
-}
-
 std::vector<Shard> plan_shards(const std::vector<uint64_t> &len, uint32_t n_slots, uint64_t chunk_reads)
 {
     std::vector<Shard> out;
@@ -445,8 +430,7 @@ private:
 
 struct ChunkOut {
     std::vector<std::string> chains, aligns;  // GAF text in read order, in pieces
-    std::string path_rows;                    // MapOptions::path_support: the chunk's lines of <out>-path-support-reads.tsv
-    std::string edit_rows;                    // MapOptions::path_edit: the chunk's lines of <out>-path-edit-reads.tsv
+    ReadRows rows;                            // the chunk's lines of the per-read tables
     uint64_t n_aligned = 0, n_anchors = 0, poa_cells = 0, n_reverse = 0;
     double ms_map = 0, ms_align = 0;
 };
@@ -458,8 +442,8 @@ struct ChunkHooks {
 };
 
 // anchors -> chains -> (alignments) of reads [b, e) on one context; the GAF text of exactly those reads
-void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &inputs, uint64_t b0, uint64_t e0, const MapOptions &opt, ChunkOut &out,
-               const ChunkHooks &hooks, unsigned T)
+void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &inputs, uint64_t b0, uint64_t e0, const MapOptions &opt, const Tables &tables,
+               ChunkOut &out, const ChunkHooks &hooks, unsigned T)
 {
     const uint64_t n = e0 - b0;
     const bool trace = getenv("VGA_TRACE") != nullptr;
@@ -550,46 +534,17 @@ void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &
         vga_poa_default_params(&pp);
         if (opt.poa_remain_rule >= 0) pp.remain_rule = opt.poa_remain_rule;
         vga_align_result *a = nullptr;
-        if (vga_align_batch(b, m, (uint32_t)opt.align_best_n, &pp, &a) != VGA_OK) {
-            const std::string e = vga_last_error(ctx);
+        std::unique_ptr<vga_align_result, void (*)(vga_align_result *)> a_owner(nullptr, vga_align_result_free);
+        try {
+            if (vga_align_batch(b, m, (uint32_t)opt.align_best_n, &pp, &a) != VGA_OK) throw Error(vga_last_error(ctx));
+            a_owner.reset(a);
+            out.ms_align = a->ms_total;
+            out.poa_cells = a->poa_cells;
+            mark("vga_align_batch");
+            tables.chunk_rows(ctx, b0, n, a->aligned, out.rows, mark);
+        } catch (const Error &) {  // (the error has its text: K6, beside this on the same context, may set another)
             wait_k6();
-            throw Error(e);
-        }
-        std::unique_ptr<vga_align_result, void (*)(vga_align_result *)> a_owner(a, vga_align_result_free);
-        out.ms_align = a->ms_total;
-        out.poa_cells = a->poa_cells;
-        mark("vga_align_batch");
-        if (opt.path_support) {  // the chunk's rows of the reads x paths table, while the context still holds them
-            const size_t np = opt.paths.n_paths();
-            std::vector<uint32_t> pb(n * np + 1), pe(n * np + 1);
-            if (vga_path_support_last(ctx, n, pb.data(), pe.data()) != VGA_OK) {
-                const std::string e = vga_last_error(ctx);
-                wait_k6();
-                throw Error(e);
-            }
-            for (uint64_t r = 0; r < n; r++)
-                for (size_t p = 0; a->aligned[r] && p < np; p++)
-                    if (pb[r * np + p] || pe[r * np + p]) {
-                        put_u64(out.path_rows, b0 + r); out.path_rows += '\t'; put_u64(out.path_rows, p); out.path_rows += '\t';
-                        put_u64(out.path_rows, pb[r * np + p]); out.path_rows += '\t'; put_u64(out.path_rows, pe[r * np + p]); out.path_rows += '\n';
-                    }
-            mark("path support rows");
-        }
-        if (opt.path_edit) {  // the chunk's scored pairs of the reads x paths edit distances, while the context still holds them
-            const size_t np = opt.paths.n_paths();
-            std::vector<uint32_t> ed(n * np + 1);
-            if (vga_path_edit_last(ctx, n, ed.data()) != VGA_OK) {
-                const std::string e = vga_last_error(ctx);
-                wait_k6();
-                throw Error(e);
-            }
-            for (uint64_t r = 0; r < n; r++)
-                for (size_t p = 0; a->aligned[r] && p < np; p++)
-                    if (ed[r * np + p] != 0xFFFFFFFFu) {
-                        put_u64(out.edit_rows, b0 + r); out.edit_rows += '\t'; put_u64(out.edit_rows, p); out.edit_rows += '\t';
-                        put_u64(out.edit_rows, ed[r * np + p]); out.edit_rows += '\n';
-                    }
-            mark("path edit rows");
+            throw;
         }
         // everything the text needs is in host memory now: the batch and, if the caller says so, the context can go
         wait_k6();
@@ -695,394 +650,6 @@ TextReplay textpath_replay(vga_ctx *ctx, const Index &ix, const std::vector<Quer
 
 namespace {
 
-// ---- coverage (MapOptions::coverage): the tables of the contexts, added in 64 bits, and the three TSV files
-struct CoverageSum {
-    std::vector<uint64_t> base, node, edge;
-    uint64_t n = 0;
-    void add(const CoverageSum &o)
-    {
-        if (base.size() < o.base.size()) base.resize(o.base.size(), 0);
-        if (node.size() < o.node.size()) node.resize(o.node.size(), 0);
-        if (edge.size() < o.edge.size()) edge.resize(o.edge.size(), 0);
-        for (size_t i = 0; i < o.base.size(); i++) base[i] += o.base[i];
-        for (size_t i = 0; i < o.node.size(); i++) node[i] += o.node[i];
-        for (size_t i = 0; i < o.edge.size(); i++) edge[i] += o.edge[i];
-        n += o.n;
-    }
-};
-
-// what the context has counted so far joins `s`
-void coverage_take(vga_ctx *ctx, const Index &ix, CoverageSum &s)
-{
-    std::vector<uint32_t> b(ix.seq_length + 1), nd(ix.n_nodes + 1), ed(ix.n_edges + 1);
-    uint64_t n = 0;
-    if (vga_coverage_read(ctx, b.data(), nd.data(), ed.data(), &n) != VGA_OK) throw Error(vga_last_error(ctx));
-    CoverageSum c;
-    c.base.assign(b.begin(), b.begin() + (long)ix.seq_length);
-    c.node.assign(nd.begin(), nd.begin() + (long)ix.n_nodes);
-    c.edge.assign(ed.begin(), ed.begin() + (long)ix.n_edges);
-    c.n = n;
-    s.add(c);
-}
-
-void coverage_write(const Index &ix, CoverageSum s, const std::string &out_prefix)
-{
-    if (out_prefix.empty()) return;
-    s.add(CoverageSum{std::vector<uint64_t>(ix.seq_length, 0), std::vector<uint64_t>(ix.n_nodes, 0), std::vector<uint64_t>(ix.n_edges, 0), 0});
-    std::string nodes = "node\tlength\treads\tbases\n", bases = "node\toffset\tdepth\n", edges = "from\tto\treads\n";
-    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
-        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
-        uint64_t sum = 0;
-        for (uint64_t p = p0; p < p1; p++) {
-            sum += s.base[p];
-            put_u64(bases, id); bases += '\t'; put_u64(bases, p - p0); bases += '\t'; put_u64(bases, s.base[p]); bases += '\n';
-        }
-        put_u64(nodes, id); nodes += '\t'; put_u64(nodes, p1 - p0); nodes += '\t'; put_u64(nodes, s.node[id - 1]); nodes += '\t';
-        put_u64(nodes, sum); nodes += '\n';
-        for (uint64_t e = ix.node_ref[id - 1].edge_idx + ix.node_ref[id - 1].edges_to_node; e < ix.node_ref[id].edge_idx; e++) {
-            put_u64(edges, id); edges += '\t'; put_u64(edges, id_of(ix.edges[e])); edges += '\t'; put_u64(edges, s.edge[e]); edges += '\n';
-        }
-    }
-    write_file(out_prefix + "-coverage-nodes.tsv", nodes);
-    write_file(out_prefix + "-coverage-bases.tsv", bases);
-    write_file(out_prefix + "-coverage-edges.tsv", edges);
-}
-
-// ---- pileup (MapOptions::pileup): the tables of the contexts, added in 64 bits, and the TSV file
-struct PileupSum {
-    std::vector<uint64_t> counts;  // seq_length x 7
-    uint64_t n = 0, leading = 0;
-    void add(const PileupSum &o)
-    {
-        if (counts.size() < o.counts.size()) counts.resize(o.counts.size(), 0);
-        for (size_t i = 0; i < o.counts.size(); i++) counts[i] += o.counts[i];
-        n += o.n;
-        leading += o.leading;
-    }
-};
-
-// what the context has counted so far joins `s`
-void pileup_take(vga_ctx *ctx, const Index &ix, PileupSum &s)
-{
-    std::vector<uint32_t> c(ix.seq_length * 7 + 1);
-    PileupSum t;
-    if (vga_pileup_read(ctx, c.data(), &t.n, &t.leading) != VGA_OK) throw Error(vga_last_error(ctx));
-    t.counts.assign(c.begin(), c.begin() + (long)(ix.seq_length * 7));
-    s.add(t);
-}
-
-void pileup_write(const Index &ix, PileupSum s, const std::string &out_prefix)
-{
-    if (out_prefix.empty()) return;
-    s.counts.resize(ix.seq_length * 7, 0);
-    std::string t = "node\toffset\tref\tA\tC\tG\tT\tN\tdel\tins\n";
-    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
-        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
-        for (uint64_t p = p0; p < p1; p++) {
-            put_u64(t, id); t += '\t'; put_u64(t, p - p0); t += '\t'; t += ix.seq_fwd[p];
-            for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, s.counts[p * 7 + (uint64_t)c]); }
-            t += '\n';
-        }
-    }
-    write_file(out_prefix + "-pileup.tsv", t);
-}
-
-// ---- variant calls (MapOptions::call_variants): the calls as the library returns them, and the TSV file
-struct VariantCalls {
-    std::vector<uint32_t> pos, qual;
-    std::vector<uint8_t> gt;
-    std::vector<uint64_t> ins_qual, depth, counts;  // counts: 7 per call
-    uint64_t n_tested = 0, n_calls = 0;
-};
-
-// `call(cap, arrays..)` is one of the two library calls with everything before cap bound: asked again when the first answer holds
-// more calls than it had room for
-template <typename F>
-void variant_fetch(vga_ctx *ctx, VariantCalls &v, F call)
-{
-    uint64_t cap = 4096;
-    for (;;) {
-        v.pos.resize(cap); v.qual.resize(cap); v.gt.resize(cap); v.ins_qual.resize(cap); v.depth.resize(cap); v.counts.resize(cap * 7);
-        if (call(cap, v.pos.data(), v.gt.data(), v.qual.data(), v.ins_qual.data(), v.depth.data(), v.counts.data(), &v.n_tested, &v.n_calls) != VGA_OK)
-            throw Error(vga_last_error(ctx));
-        if (v.n_calls <= cap) break;
-        cap = v.n_calls;
-    }
-}
-
-// from the context's own counters
-void variant_take(vga_ctx *ctx, const MapOptions &opt, VariantCalls &v)
-{
-    variant_fetch(ctx, v, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
-        return vga_variant_call(ctx, opt.call_error, opt.call_min_depth, opt.call_min_qual, cap, pos, gt, qual, iq, depth, counts, nt, nc);
-    });
-}
-
-// from the tables of several contexts, added in 64 bits
-void variant_take_table(vga_ctx *ctx, const Index &ix, const MapOptions &opt, PileupSum s, VariantCalls &v)
-{
-    s.counts.resize(ix.seq_length * 7, 0);
-    variant_fetch(ctx, v, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
-        return vga_variant_call_table(ctx, ix.seq_length, s.counts.data(), ix.seq_fwd.data(), opt.call_error, opt.call_min_depth, opt.call_min_qual, cap, pos, gt,
-                                      qual, iq, depth, counts, nt, nc);
-    });
-}
-
-void variant_write(const Index &ix, const VariantCalls &v, MapOutput &out, const std::string &out_prefix)
-{
-    out.n_variant_tested = v.n_tested; out.n_variant_calls = v.n_calls;
-    if (out_prefix.empty()) return;
-    static const char ALLELES[] = "ACGT-";
-    static const char *const STATES[] = {".", "het", "hom"};
-    std::string t = "node\toffset\tref\tgt\tqual\tins\tins_qual\tdepth\tA\tC\tG\tT\tN\tdel\tins_count\n";
-    uint64_t id = 1;  // the calls come in base order: the node moves forward only
-    for (uint64_t j = 0; j < v.n_calls; j++) {
-        const uint64_t p = v.pos[j];
-        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= p) id++;
-        const uint32_t g = v.gt[j];
-        put_u64(t, id); t += '\t'; put_u64(t, p - ix.node_ref[id - 1].seq_idx); t += '\t'; t += ix.seq_fwd[p]; t += '\t';
-        t += ALLELES[g & 7u]; t += '/'; t += ALLELES[(g >> 3) & 7u]; t += '\t'; put_u64(t, v.qual[j]); t += '\t';
-        t += STATES[(g >> 6) < 3u ? (g >> 6) : 0u]; t += '\t'; put_u64(t, v.ins_qual[j]); t += '\t'; put_u64(t, v.depth[j]);
-        for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, v.counts[j * 7 + (uint64_t)c]); }
-        t += '\n';
-    }
-    write_file(out_prefix + "-variants.tsv", t);
-}
-
-bool variant_params_ok(const MapOptions &opt) { return opt.call_error >= 257 && opt.call_error <= 8192 && opt.call_min_depth >= 1; }
-
-// ---- path support (MapOptions::path_support): the per-path totals of the contexts, added in 64 bits, and the two TSV files
-struct PathSum {
-    std::vector<uint64_t> v[4];  // sum_bases, sum_edges, top, top_alone
-    uint64_t n = 0, unplaced = 0;
-};
-
-void path_support_begin(vga_ctx *ctx, const MapOptions &opt)
-{
-    if (vga_path_support_begin(ctx, (uint32_t)opt.paths.n_paths(), opt.paths.step_off.data(), opt.paths.steps.data(), nullptr) != VGA_OK)
-        throw Error(vga_last_error(ctx));
-}
-
-// what the context has accumulated so far joins `s`
-void path_support_take(vga_ctx *ctx, const MapOptions &opt, PathSum &s)
-{
-    const size_t np = opt.paths.n_paths();
-    std::vector<uint64_t> t[4];
-    for (auto &x : t) x.assign(np + 1, 0);
-    uint64_t n = 0, un = 0;
-    if (vga_path_support_read(ctx, t[0].data(), t[1].data(), t[2].data(), t[3].data(), &n, &un) != VGA_OK) throw Error(vga_last_error(ctx));
-    for (int k = 0; k < 4; k++) {
-        s.v[k].resize(np, 0);
-        for (size_t p = 0; p < np; p++) s.v[k][p] += t[k][p];
-    }
-    s.n += n;
-    s.unplaced += un;
-}
-
-void path_support_write(const MapOptions &opt, PathSum s, const std::string &rows, const std::string &out_prefix)
-{
-    if (out_prefix.empty()) return;
-    const size_t np = opt.paths.n_paths();
-    std::string paths = "path\tsteps\tlength\tsum_bases\tsum_edges\ttop\ttop_alone\n";
-    for (size_t p = 0; p < np; p++) {
-        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
-        put_u64(paths, opt.paths.length[p]);
-        for (auto &x : s.v) { x.resize(np, 0); paths += '\t'; put_u64(paths, x[p]); }
-        paths += '\n';
-    }
-    write_file(out_prefix + "-path-support.tsv", paths);
-    write_file(out_prefix + "-path-support-reads.tsv", "read\tpath\tbases\tedges\n" + rows);
-}
-
-// ---- path edit (MapOptions::path_edit): the per-path totals of the contexts, added in 64 bits, and the two TSV files
-struct EditSum {
-    std::vector<uint64_t> v[4];  // n_scored, sum_edit, best, best_alone
-    uint64_t n = 0, too_long = 0;
-    void add(const EditSum &o)
-    {
-        for (int k = 0; k < 4; k++) {
-            if (v[k].size() < o.v[k].size()) v[k].resize(o.v[k].size(), 0);
-            for (size_t p = 0; p < o.v[k].size(); p++) v[k][p] += o.v[k][p];
-        }
-        n += o.n;
-        too_long += o.too_long;
-    }
-};
-
-// the edit distance is scored: for its own files, or for the likelihood
-bool edit_on(const MapOptions &opt) { return opt.path_edit || (opt.genotype_likelihood && opt.genotype_from_edit); }
-
-// what the context has accumulated so far joins `s`
-void path_edit_take(vga_ctx *ctx, const MapOptions &opt, EditSum &s)
-{
-    EditSum t;
-    for (auto &x : t.v) x.assign(opt.paths.n_paths(), 0);
-    if (vga_path_edit_read(ctx, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data(), &t.n, &t.too_long) != VGA_OK) throw Error(vga_last_error(ctx));
-    s.add(t);
-}
-
-// (length: |seq_p|, the bases of all the steps of the path, whichever way they are visited)
-void path_edit_write(const Index &ix, const MapOptions &opt, EditSum s, const std::string &rows, const std::string &out_prefix)
-{
-    if (out_prefix.empty()) return;
-    const size_t np = opt.paths.n_paths();
-    std::string paths = "path\tsteps\tlength\tscored\tsum_edit\tbest\tbest_alone\n";
-    for (size_t p = 0; p < np; p++) {
-        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
-        uint64_t len = 0;
-        for (uint64_t t = opt.paths.step_off[p]; t < opt.paths.step_off[p + 1]; t++) {
-            const uint64_t id = id_of(opt.paths.steps[t]);
-            len += ix.node_ref[id].seq_idx - ix.node_ref[id - 1].seq_idx;
-        }
-        put_u64(paths, len);
-        for (auto &x : s.v) { x.resize(np, 0); paths += '\t'; put_u64(paths, x[p]); }
-        paths += '\n';
-    }
-    write_file(out_prefix + "-path-edit.tsv", paths);
-    write_file(out_prefix + "-path-edit-reads.tsv", "read\tpath\tedit\n" + rows);
-}
-
-// path support and what is built on it, on one context
-void scoring_begin(vga_ctx *ctx, const MapOptions &opt)
-{
-    path_support_begin(ctx, opt);
-    if (edit_on(opt) && vga_path_edit_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    if (opt.genotype && vga_genotype_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    if (opt.genotype_likelihood && vga_genotype_lik_begin(ctx, opt.genotype_lambda, opt.genotype_cap) != VGA_OK) throw Error(vga_last_error(ctx));
-    if (opt.genotype_likelihood && opt.genotype_from_edit && vga_genotype_lik_source(ctx, VGA_GL_FROM_EDIT) != VGA_OK) throw Error(vga_last_error(ctx));
-}
-
-// ---- genotype (MapOptions::genotype): the pair tables of the contexts, added in 64 bits, the ranking and the TSV file
-struct PairSum {
-    std::vector<uint64_t> v[4];  // sum_bases, sum_edges, prefer_a, prefer_b at vga_pair_index
-};
-
-// what the context has accumulated so far joins `s`
-void genotype_take(vga_ctx *ctx, const MapOptions &opt, PairSum &s)
-{
-    const size_t n = vga_pair_count(opt.paths.n_paths());
-    std::vector<uint64_t> t[4];
-    for (auto &x : t) x.assign(n + 1, 0);
-    if (vga_genotype_read(ctx, n, t[0].data(), t[1].data(), t[2].data(), t[3].data()) != VGA_OK) throw Error(vga_last_error(ctx));
-    for (int k = 0; k < 4; k++) {
-        s.v[k].resize(n, 0);
-        for (size_t i = 0; i < n; i++) s.v[k][i] += t[k][i];
-    }
-}
-
-// The pairs whose sums are not (0, 0), from the best down: by sum_bases, then sum_edges, both descending, then the homozygous
-// pair before a heterozygous one, then p, then q.
-void genotype_write(const MapOptions &opt, PairSum s, MapOutput &out, const std::string &out_prefix)
-{
-    const size_t np = opt.paths.n_paths(), n = vga_pair_count(np);
-    for (auto &x : s.v) x.resize(n, 0);
-    struct Pair { uint32_t p, q; uint64_t at; };
-    std::vector<Pair> ranked;
-    for (uint32_t p = 0; p < np; p++)
-        for (uint32_t q = p; q < np; q++) {
-            const uint64_t at = vga_pair_index(np, p, q);
-            if (s.v[0][at] || s.v[1][at]) ranked.push_back({p, q, at});
-        }
-    std::sort(ranked.begin(), ranked.end(), [&](const Pair &a, const Pair &b) {
-        if (s.v[0][a.at] != s.v[0][b.at]) return s.v[0][a.at] > s.v[0][b.at];
-        if (s.v[1][a.at] != s.v[1][b.at]) return s.v[1][a.at] > s.v[1][b.at];
-        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
-        return a.p != b.p ? a.p < b.p : a.q < b.q;
-    });
-    out.n_genotype_pairs = ranked.size();
-    if (!ranked.empty()) {
-        out.genotype_a = opt.paths.names[ranked[0].p]; out.genotype_b = opt.paths.names[ranked[0].q];
-        out.genotype_sum_bases = s.v[0][ranked[0].at]; out.genotype_sum_edges = s.v[1][ranked[0].at];
-    }
-    if (out_prefix.empty()) return;
-    std::string t = "rank\tpath_a\tpath_b\tsum_bases\tsum_edges\tprefer_a\tprefer_b\n";
-    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
-    for (size_t i = 0; i < rows; i++) {
-        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q];
-        for (const auto &x : s.v) { t += '\t'; put_u64(t, x[ranked[i].at]); }
-        t += '\n';
-    }
-    write_file(out_prefix + "-genotype.tsv", t);
-}
-
-// ---- genotype likelihood (MapOptions::genotype_likelihood): the cost tables of the contexts, added in 64 bits, the ranking and
-// the TSV file
-struct CostSum {
-    std::vector<uint64_t> cost;  // at vga_pair_index, in 1/256 bit
-    uint64_t n_scored = 0;
-    void add(const CostSum &o)
-    {
-        if (cost.size() < o.cost.size()) cost.resize(o.cost.size(), 0);
-        for (size_t i = 0; i < o.cost.size(); i++) cost[i] += o.cost[i];
-        n_scored += o.n_scored;
-    }
-};
-
-// what the context has accumulated so far joins `s`
-void likelihood_take(vga_ctx *ctx, const MapOptions &opt, CostSum &s)
-{
-    CostSum t;
-    t.cost.assign(vga_pair_count(opt.paths.n_paths()), 0);
-    if (vga_genotype_lik_read(ctx, t.cost.size(), t.cost.data(), &t.n_scored) != VGA_OK) throw Error(vga_last_error(ctx));
-    s.add(t);
-}
-
-// Every pair from the cheapest up: by cost, then the homozygous pair before a heterozygous one, then p, then q.  No row scored:
-// no call, and a table with its header only.
-void likelihood_write(const MapOptions &opt, CostSum s, MapOutput &out, const std::string &out_prefix)
-{
-    const size_t np = opt.paths.n_paths();
-    s.cost.resize(vga_pair_count(np), 0);
-    struct Pair { uint32_t p, q; uint64_t cost; };
-    std::vector<Pair> ranked;
-    if (s.n_scored)
-        for (uint32_t p = 0; p < np; p++)
-            for (uint32_t q = p; q < np; q++) ranked.push_back({p, q, s.cost[vga_pair_index(np, p, q)]});
-    std::sort(ranked.begin(), ranked.end(), [](const Pair &a, const Pair &b) {
-        if (a.cost != b.cost) return a.cost < b.cost;
-        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
-        return a.p != b.p ? a.p < b.p : a.q < b.q;
-    });
-    out.n_likelihood_scored = s.n_scored;
-    if (!ranked.empty()) {
-        out.likelihood_a = opt.paths.names[ranked[0].p]; out.likelihood_b = opt.paths.names[ranked[0].q];
-        out.likelihood_cost = ranked[0].cost;
-        out.likelihood_next = ranked.size() > 1 ? ranked[1].cost - ranked[0].cost : 0;
-    }
-    if (out_prefix.empty()) return;
-    std::string t = "rank\tpath_a\tpath_b\tcost\tmargin\n";
-    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
-    for (size_t i = 0; i < rows; i++) {
-        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q]; t += '\t';
-        put_u64(t, ranked[i].cost); t += '\t'; put_u64(t, ranked[i].cost - ranked[0].cost); t += '\n';
-    }
-    write_file(out_prefix + "-genotype-likelihood.tsv", t);
-}
-
-bool likelihood_params_ok(const MapOptions &opt) { return opt.genotype_lambda >= 1 && opt.genotype_lambda <= 4096 && opt.genotype_cap >= 1 && opt.genotype_cap <= 255; }
-
-void check_aligner(const MapOptions &opt)
-{
-    if (opt.genotype_likelihood && !opt.also_align) throw Error("--genotype-likelihood calls from alignments: it needs --also-align");
-    if (opt.genotype_likelihood && opt.paths.n_paths() == 0) throw Error("--genotype-likelihood: the graph has no P line");
-    if (opt.genotype_likelihood && !likelihood_params_ok(opt)) throw Error("--genotype-likelihood: --genotype-lambda is 1 to 4096 and --genotype-cap 1 to 255");
-    if (opt.genotype_from_edit && !opt.genotype_likelihood) throw Error("--genotype-from has no meaning without --genotype-likelihood");
-    if (opt.path_edit && !opt.also_align) throw Error("--path-edit scores alignments: it needs --also-align");
-    if (opt.path_edit && opt.paths.n_paths() == 0) throw Error("--path-edit: the graph has no P line");
-    if (opt.genotype && !opt.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
-    if (opt.genotype && opt.paths.n_paths() == 0) throw Error("--genotype: the graph has no P line");
-    if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
-    if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
-    if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
-    if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
-    if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
-    if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
-    if (opt.poa_aligner != "abpoa") {
-        if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
-        throw Error("POA Aligner not recognized");  // map_main.rs:67
-    }
-}
-
 // file output and validation records of the assembled GAF texts (map.rs:135-139, 174-178, 186-208)
 void finish(MapOutput &out, const Index &ix, const std::vector<QuerySequence> &inputs, const MapOptions &opt, const std::string &out_prefix)
 {
@@ -1108,71 +675,27 @@ MapOutput map_reads(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequen
                     const std::string &out_prefix)
 {
     check_aligner(opt);
-    const bool coverage = opt.coverage || opt.coverage_only;
     MapOutput out;
     out.n_reads = inputs.size();
     out.n_devices = 1;
-    if (coverage && vga_coverage_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit;  // (each of the others turns the scoring on, not its files)
-    if (scoring) scoring_begin(ctx, opt);
-    const bool piling = opt.pileup || opt.call_variants;  // (the call turns the counting on, not its file)
-    if (piling && vga_pileup_begin(ctx) != VGA_OK) throw Error(vga_last_error(ctx));
-    std::string path_rows, edit_rows;
+    Tables tables(ix, opt);
+    tables.begin(ctx);
+    ReadRows rows;
     std::vector<uint64_t> len(inputs.size());
     for (size_t i = 0; i < inputs.size(); i++) len[i] = inputs[i].seq.size();
     for (const Shard &s : plan_shards(len, 1, opt.chunk_reads)) {
         ChunkOut c;
-        map_chunk(ctx, ix, inputs, s.begin, s.end, opt, c, ChunkHooks(), text_threads(1));
+        map_chunk(ctx, ix, inputs, s.begin, s.end, opt, tables, c, ChunkHooks(), text_threads(1));
         append_pieces(out.chains_gaf, c.chains);
         append_pieces(out.alignments_gaf, c.aligns);
-        path_rows += c.path_rows;
-        edit_rows += c.edit_rows;
+        rows += c.rows;
         out.n_aligned += c.n_aligned; out.n_anchors += c.n_anchors; out.poa_cells += c.poa_cells; out.n_reverse += c.n_reverse;
         out.ms_map += c.ms_map; out.ms_align += c.ms_align;
         out.n_chunks++;
     }
-    if (coverage) {
-        CoverageSum s;
-        coverage_take(ctx, ix, s);
-        (void)vga_coverage_end(ctx);
-        out.n_coverage = s.n;
-        coverage_write(ix, s, out_prefix);
-    }
-    if (opt.genotype) {
-        PairSum s;
-        genotype_take(ctx, opt, s);
-        genotype_write(opt, std::move(s), out, out_prefix);
-    }
-    if (opt.genotype_likelihood) {
-        CostSum s;
-        likelihood_take(ctx, opt, s);
-        likelihood_write(opt, std::move(s), out, out_prefix);
-    }
-    if (edit_on(opt)) {
-        EditSum s;
-        path_edit_take(ctx, opt, s);
-        out.n_edit_alignments = s.n; out.n_edit_too_long = s.too_long;
-        if (opt.path_edit) path_edit_write(ix, opt, std::move(s), edit_rows, out_prefix);
-    }
-    if (scoring) {
-        PathSum s;
-        path_support_take(ctx, opt, s);
-        (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
-        out.n_path_scored = s.n; out.n_path_unplaced = s.unplaced;
-        if (opt.path_support) path_support_write(opt, s, path_rows, out_prefix);
-    }
-    if (opt.call_variants) {
-        VariantCalls v;
-        variant_take(ctx, opt, v);
-        variant_write(ix, v, out, out_prefix);
-    }
-    if (opt.pileup) {
-        PileupSum s;
-        pileup_take(ctx, ix, s);
-        out.n_pileup = s.n; out.n_leading_ins = s.leading;
-        pileup_write(ix, s, out_prefix);
-    }
-    if (piling) (void)vga_pileup_end(ctx);
+    tables.take(ctx, 0, true);
+    tables.end(ctx);  // (the context is the caller's: it goes on without the tables)
+    tables.write(out, rows, out_prefix);
     finish(out, ix, inputs, opt, out_prefix);
     return out;
 }
@@ -1260,47 +783,15 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         for (vga_ctx *c : ctxs)
             if (vga_index_upload(c, &d) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
     }
-    const bool coverage = opt.coverage || opt.coverage_only;
-    if (coverage)
-        for (vga_ctx *c : ctxs)
-            if (vga_coverage_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-    const bool scoring = opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit;  // (each of the others turns the scoring on, not its files)
-    if (scoring)
-        for (vga_ctx *c : ctxs) {
-            try { scoring_begin(c, opt); } catch (const Error &) { release(); throw; }
-        }
-    const bool piling = opt.pileup || opt.call_variants;  // (the call turns the counting on, not its file)
-    if (piling)
-        for (vga_ctx *c : ctxs)
-            if (vga_pileup_begin(c) != VGA_OK) { const std::string e = vga_last_error(c); release(); throw Error(e); }
-    // --call-variants: one context calls from its own counters as soon as its last chunk is counted; several hand their tables
-    // over, and the first context stays until it has called from their sum
-    const bool call_alone = opt.call_variants && n_slots == 1, call_summed = opt.call_variants && n_slots > 1;
-    VariantCalls variants;
-    std::vector<PileupSum> slot_pileup(n_slots);
-    std::vector<CoverageSum> slot_cov(n_slots);
-    std::vector<PathSum> slot_paths(n_slots);
-    std::vector<PairSum> slot_pairs(n_slots);
-    std::vector<CostSum> slot_costs(n_slots);
-    std::vector<EditSum> slot_edit(n_slots);
-    // what the slot's context has counted and scored, read once its last chunk is off the GPU
-    auto take_tables = [&](uint32_t slot) {
-        if (coverage) coverage_take(ctxs[slot], ix, slot_cov[slot]);
-        if (scoring) path_support_take(ctxs[slot], opt, slot_paths[slot]);
-        if (opt.genotype) genotype_take(ctxs[slot], opt, slot_pairs[slot]);
-        if (opt.genotype_likelihood) likelihood_take(ctxs[slot], opt, slot_costs[slot]);
-        if (edit_on(opt)) path_edit_take(ctxs[slot], opt, slot_edit[slot]);
-        // (VGA_TRACE: what each of the two routes to the sites costs at the device's end, tests/prof_variant.py)
-        const auto t0 = std::chrono::steady_clock::now();
-        if (opt.pileup || call_summed) pileup_take(ctxs[slot], ix, slot_pileup[slot]);
-        const auto t1 = std::chrono::steady_clock::now();
-        if (call_alone) variant_take(ctxs[slot], opt, variants);
-        if (piling && getenv("VGA_TRACE"))
-            fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
-                    std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
-    };
-    const bool tables = coverage || scoring || piling;
+    // the tables of every slot's context; the first becomes their sum.  --call-variants: one context calls from its own counters as
+    // soon as its last chunk is counted; several hand their tables over, and the first context stays until it has called from
+    // their sum
+    std::vector<Tables> slot_tables(n_slots, Tables(ix, opt));
+    Tables &tables = slot_tables[0];
+    const bool call_summed = tables.call_summed(n_slots);
+    for (uint32_t slot = 0; slot < n_slots; slot++) {
+        try { slot_tables[slot].begin(ctxs[slot]); } catch (const Error &) { release(); throw; }
+    }
     trace_mark("index uploaded");
     // the library's worker threads (CIGAR strings, result copies) are per call: the slots share the cores
     if (n_slots > 1 && !getenv("VGA_HOST_THREADS")) {
@@ -1371,18 +862,17 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
                         { std::lock_guard<std::mutex> lk(mu); if (abort_workers) break; }
                         ChunkHooks hooks;
                         if (stream) hooks.chains_ready = [&, i]() { { std::lock_guard<std::mutex> lk(mu); chains_done[i] = 1; } cv.notify_all(); };
-                        if (tables && i == last_of_slot[slot] && !opt.leave_contexts)
-                            hooks.gpu_done = [&, slot]() { take_tables(slot); };
-                        if (opt.leave_contexts && i == last_of_slot[slot])
+                        if (i == last_of_slot[slot] && (tables.any() || opt.leave_contexts))
                             hooks.gpu_done = [&, slot]() {
-                                take_tables(slot);  // (the slot's last chunk has been counted)
+                                slot_tables[slot].take(ctxs[slot], slot, !call_summed);  // (the slot's last chunk has been counted)
+                                if (!opt.leave_contexts) return;
                                 if (call_summed && slot == 0) return;  // (it still has the summed table to call from)
                                 vga_ctx *c = ctxs[slot];
                                 ctxs[slot] = nullptr;
                                 std::lock_guard<std::mutex> lk(destroyers_mu);
                                 destroyers.emplace_back([c]() { vga_ctx_destroy(c); });
                             };
-                        map_chunk(ctxs[slot], ix, inputs, plan[i].begin, plan[i].end, opt, parts[i], hooks, T_text);
+                        map_chunk(ctxs[slot], ix, inputs, plan[i].begin, plan[i].end, opt, slot_tables[slot], parts[i], hooks, T_text);
                         { std::lock_guard<std::mutex> lk(mu); done[i] = 1; }
                         cv.notify_all();
                     }
@@ -1400,12 +890,11 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
     bool any_error = false;
     for (const std::string &e : errors) any_error = any_error || !e.empty();
     for (const std::string &e : writer_err) any_error = any_error || !e.empty();
+    if (!any_error)
+        for (uint32_t slot = 1; slot < n_slots; slot++) tables.add(slot_tables[slot]);
     if (call_summed && !any_error) {
         try {
-            PileupSum sum;
-            for (const PileupSum &c : slot_pileup) sum.add(c);
-            variant_take_table(ctxs[0], ix, opt, std::move(sum), variants);
-            trace_mark("variants called");
+            tables.call(ctxs[0]);
         } catch (const std::exception &e) {
             errors[0] = e.what();
             any_error = true;
@@ -1447,71 +936,9 @@ MapOutput map_reads_multi(const Index &ix, const std::vector<QuerySequence> &inp
         ms_map[plan[i].slot] += parts[i].ms_map; ms_align[plan[i].slot] += parts[i].ms_align;
     }
     for (uint32_t s = 0; s < n_slots; s++) { out.ms_map = std::max(out.ms_map, ms_map[s]); out.ms_align = std::max(out.ms_align, ms_align[s]); }
-    if (coverage) {
-        CoverageSum sum;
-        for (const CoverageSum &c : slot_cov) sum.add(c);
-        out.n_coverage = sum.n;
-        coverage_write(ix, sum, out_prefix);
-        trace_mark("coverage tables written");
-    }
-    if (opt.genotype) {
-        PairSum sum;
-        const size_t n = vga_pair_count(opt.paths.n_paths());
-        for (const PairSum &c : slot_pairs)
-            for (int k = 0; k < 4; k++) {
-                sum.v[k].resize(n, 0);
-                for (size_t i = 0; i < c.v[k].size(); i++) sum.v[k][i] += c.v[k][i];
-            }
-        genotype_write(opt, std::move(sum), out, out_prefix);
-        trace_mark("genotype table written");
-    }
-    if (opt.genotype_likelihood) {
-        CostSum sum;
-        for (const CostSum &c : slot_costs) sum.add(c);
-        likelihood_write(opt, std::move(sum), out, out_prefix);
-        trace_mark("genotype likelihood table written");
-    }
-    if (edit_on(opt)) {
-        EditSum sum;
-        for (auto &x : sum.v) x.assign(opt.paths.n_paths(), 0);
-        for (const EditSum &c : slot_edit) sum.add(c);
-        out.n_edit_alignments = sum.n; out.n_edit_too_long = sum.too_long;
-        if (opt.path_edit) {
-            std::string rows;
-            for (size_t i = 0; i < plan.size(); i++) rows += parts[i].edit_rows;  // read order
-            path_edit_write(ix, opt, std::move(sum), rows, out_prefix);
-            trace_mark("path edit tables written");
-        }
-    }
-    if (scoring) {
-        PathSum sum;
-        sum.v[0].assign(opt.paths.n_paths(), 0);
-        for (const PathSum &c : slot_paths) {
-            for (int k = 0; k < 4; k++) {
-                sum.v[k].resize(opt.paths.n_paths(), 0);
-                for (size_t p = 0; p < c.v[k].size(); p++) sum.v[k][p] += c.v[k][p];
-            }
-            sum.n += c.n; sum.unplaced += c.unplaced;
-        }
-        out.n_path_scored = sum.n; out.n_path_unplaced = sum.unplaced;
-        if (opt.path_support) {
-            std::string rows;
-            for (size_t i = 0; i < plan.size(); i++) rows += parts[i].path_rows;  // read order
-            path_support_write(opt, sum, rows, out_prefix);
-            trace_mark("path support tables written");
-        }
-    }
-    if (opt.call_variants) {
-        variant_write(ix, variants, out, out_prefix);
-        trace_mark("variants written");
-    }
-    if (opt.pileup) {
-        PileupSum sum;
-        for (const PileupSum &c : slot_pileup) sum.add(c);
-        out.n_pileup = sum.n; out.n_leading_ins = sum.leading;
-        pileup_write(ix, sum, out_prefix);
-        trace_mark("pileup table written");
-    }
+    ReadRows rows;
+    for (size_t i = 0; i < plan.size(); i++) rows += parts[i].rows;  // read order
+    tables.write(out, rows, out_prefix);
     if (stream) return out;
     finish(out, ix, inputs, opt, out_prefix);
     return out;

@@ -1,0 +1,421 @@
+// vgh_tables.cpp -- the analysis tables of map_reads / map_reads_multi (vgh_tables.hpp): reading them from a context, adding them
+// over the contexts, the two rankings and the TSV files.  Nothing of this is in the reference.
+#include "vgh_tables.hpp"
+#include "../csrc/vga_pair_index.hpp"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <fstream>
+
+namespace vgh {
+
+void write_file(const std::string &name, const std::string &body)
+{
+    std::ofstream o(name, std::ios::binary);
+    if (!o) throw Error("Couldn't create file " + name);
+    o.write(body.data(), body.size());
+    if (!o) throw Error("Couldn't write to file " + name);
+}
+
+void Counters::add(const Counters &o)
+{
+    if (v.size() < o.v.size()) v.resize(o.v.size());
+    for (size_t k = 0; k < o.v.size(); k++) {
+        if (v[k].size() < o.v[k].size()) v[k].resize(o.v[k].size(), 0);
+        for (size_t i = 0; i < o.v[k].size(); i++) v[k][i] += o.v[k][i];
+    }
+    n[0] += o.n[0];
+    n[1] += o.n[1];
+}
+
+void Counters::pad(const std::vector<size_t> &sizes)
+{
+    if (v.size() < sizes.size()) v.resize(sizes.size());
+    for (size_t k = 0; k < sizes.size(); k++)
+        if (v[k].size() < sizes[k]) v[k].resize(sizes[k], 0);
+}
+
+bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit; }
+
+namespace {
+
+bool variant_params_ok(const MapOptions &opt) { return opt.call_error >= 257 && opt.call_error <= 8192 && opt.call_min_depth >= 1; }
+bool likelihood_params_ok(const MapOptions &opt) { return opt.genotype_lambda >= 1 && opt.genotype_lambda <= 4096 && opt.genotype_cap >= 1 && opt.genotype_cap <= 255; }
+
+void check(vga_ctx *ctx, int rc)
+{
+    if (rc != VGA_OK) throw Error(vga_last_error(ctx));
+}
+
+// the first n of the library's 32-bit counters as one vector of a table
+std::vector<uint64_t> widen(const std::vector<uint32_t> &t, size_t n) { return std::vector<uint64_t>(t.begin(), t.begin() + (long)n); }
+
+// `call(cap, arrays..)` is one of the two library calls with everything before cap bound: asked again when the first answer holds
+// more calls than it had room for
+template <typename F>
+void variant_fetch(vga_ctx *ctx, VariantCalls &v, F call)
+{
+    uint64_t cap = 4096;
+    for (;;) {
+        v.pos.resize(cap); v.qual.resize(cap); v.gt.resize(cap); v.ins_qual.resize(cap); v.depth.resize(cap); v.counts.resize(cap * 7);
+        check(ctx, call(cap, v.pos.data(), v.gt.data(), v.qual.data(), v.ins_qual.data(), v.depth.data(), v.counts.data(), &v.n_tested, &v.n_calls));
+        if (v.n_calls <= cap) break;
+        cap = v.n_calls;
+    }
+}
+
+// ---- the writers.  Each gets its table padded to the sizes it indexes.
+
+void coverage_write(const Index &ix, const Counters &s, const std::string &out_prefix)
+{
+    const std::vector<uint64_t> &base = s.v[0], &node = s.v[1], &edge = s.v[2];
+    std::string nodes = "node\tlength\treads\tbases\n", bases = "node\toffset\tdepth\n", edges = "from\tto\treads\n";
+    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
+        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
+        uint64_t sum = 0;
+        for (uint64_t p = p0; p < p1; p++) {
+            sum += base[p];
+            put_u64(bases, id); bases += '\t'; put_u64(bases, p - p0); bases += '\t'; put_u64(bases, base[p]); bases += '\n';
+        }
+        put_u64(nodes, id); nodes += '\t'; put_u64(nodes, p1 - p0); nodes += '\t'; put_u64(nodes, node[id - 1]); nodes += '\t';
+        put_u64(nodes, sum); nodes += '\n';
+        for (uint64_t e = ix.node_ref[id - 1].edge_idx + ix.node_ref[id - 1].edges_to_node; e < ix.node_ref[id].edge_idx; e++) {
+            put_u64(edges, id); edges += '\t'; put_u64(edges, id_of(ix.edges[e])); edges += '\t'; put_u64(edges, edge[e]); edges += '\n';
+        }
+    }
+    write_file(out_prefix + "-coverage-nodes.tsv", nodes);
+    write_file(out_prefix + "-coverage-bases.tsv", bases);
+    write_file(out_prefix + "-coverage-edges.tsv", edges);
+}
+
+void pileup_write(const Index &ix, const Counters &s, const std::string &out_prefix)
+{
+    std::string t = "node\toffset\tref\tA\tC\tG\tT\tN\tdel\tins\n";
+    for (uint64_t id = 1; id <= ix.n_nodes; id++) {
+        const uint64_t p0 = ix.node_ref[id - 1].seq_idx, p1 = ix.node_ref[id].seq_idx;
+        for (uint64_t p = p0; p < p1; p++) {
+            put_u64(t, id); t += '\t'; put_u64(t, p - p0); t += '\t'; t += ix.seq_fwd[p];
+            for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, s.v[0][p * 7 + (uint64_t)c]); }
+            t += '\n';
+        }
+    }
+    write_file(out_prefix + "-pileup.tsv", t);
+}
+
+void variant_write(const Index &ix, const VariantCalls &v, const std::string &out_prefix)
+{
+    static const char ALLELES[] = "ACGT-";
+    static const char *const STATES[] = {".", "het", "hom"};
+    std::string t = "node\toffset\tref\tgt\tqual\tins\tins_qual\tdepth\tA\tC\tG\tT\tN\tdel\tins_count\n";
+    uint64_t id = 1;  // the calls come in base order: the node moves forward only
+    for (uint64_t j = 0; j < v.n_calls; j++) {
+        const uint64_t p = v.pos[j];
+        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= p) id++;
+        const uint32_t g = v.gt[j];
+        put_u64(t, id); t += '\t'; put_u64(t, p - ix.node_ref[id - 1].seq_idx); t += '\t'; t += ix.seq_fwd[p]; t += '\t';
+        t += ALLELES[g & 7u]; t += '/'; t += ALLELES[(g >> 3) & 7u]; t += '\t'; put_u64(t, v.qual[j]); t += '\t';
+        t += STATES[(g >> 6) < 3u ? (g >> 6) : 0u]; t += '\t'; put_u64(t, v.ins_qual[j]); t += '\t'; put_u64(t, v.depth[j]);
+        for (int c = 0; c < 7; c++) { t += '\t'; put_u64(t, v.counts[j * 7 + (uint64_t)c]); }
+        t += '\n';
+    }
+    write_file(out_prefix + "-variants.tsv", t);
+}
+
+void path_support_write(const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    std::string paths = "path\tsteps\tlength\tsum_bases\tsum_edges\ttop\ttop_alone\n";
+    for (size_t p = 0; p < np; p++) {
+        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
+        put_u64(paths, opt.paths.length[p]);
+        for (const auto &x : s.v) { paths += '\t'; put_u64(paths, x[p]); }
+        paths += '\n';
+    }
+    write_file(out_prefix + "-path-support.tsv", paths);
+    write_file(out_prefix + "-path-support-reads.tsv", "read\tpath\tbases\tedges\n" + rows);
+}
+
+// (length: |seq_p|, the bases of all the steps of the path, whichever way they are visited)
+void path_edit_write(const Index &ix, const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    std::string paths = "path\tsteps\tlength\tscored\tsum_edit\tbest\tbest_alone\n";
+    for (size_t p = 0; p < np; p++) {
+        paths += opt.paths.names[p]; paths += '\t'; put_u64(paths, opt.paths.step_off[p + 1] - opt.paths.step_off[p]); paths += '\t';
+        uint64_t len = 0;
+        for (uint64_t t = opt.paths.step_off[p]; t < opt.paths.step_off[p + 1]; t++) {
+            const uint64_t id = id_of(opt.paths.steps[t]);
+            len += ix.node_ref[id].seq_idx - ix.node_ref[id - 1].seq_idx;
+        }
+        put_u64(paths, len);
+        for (const auto &x : s.v) { paths += '\t'; put_u64(paths, x[p]); }
+        paths += '\n';
+    }
+    write_file(out_prefix + "-path-edit.tsv", paths);
+    write_file(out_prefix + "-path-edit-reads.tsv", "read\tpath\tedit\n" + rows);
+}
+
+// The pairs whose sums are not (0, 0), from the best down: by sum_bases, then sum_edges, both descending, then the homozygous
+// pair before a heterozygous one, then p, then q.
+void genotype_write(const MapOptions &opt, const Counters &s, MapOutput &out, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    struct Pair { uint32_t p, q; uint64_t at; };
+    std::vector<Pair> ranked;
+    for (uint32_t p = 0; p < np; p++)
+        for (uint32_t q = p; q < np; q++) {
+            const uint64_t at = vga_pair_index(np, p, q);
+            if (s.v[0][at] || s.v[1][at]) ranked.push_back({p, q, at});
+        }
+    std::sort(ranked.begin(), ranked.end(), [&](const Pair &a, const Pair &b) {
+        if (s.v[0][a.at] != s.v[0][b.at]) return s.v[0][a.at] > s.v[0][b.at];
+        if (s.v[1][a.at] != s.v[1][b.at]) return s.v[1][a.at] > s.v[1][b.at];
+        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
+        return a.p != b.p ? a.p < b.p : a.q < b.q;
+    });
+    out.n_genotype_pairs = ranked.size();
+    if (!ranked.empty()) {
+        out.genotype_a = opt.paths.names[ranked[0].p]; out.genotype_b = opt.paths.names[ranked[0].q];
+        out.genotype_sum_bases = s.v[0][ranked[0].at]; out.genotype_sum_edges = s.v[1][ranked[0].at];
+    }
+    if (out_prefix.empty()) return;
+    std::string t = "rank\tpath_a\tpath_b\tsum_bases\tsum_edges\tprefer_a\tprefer_b\n";
+    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
+    for (size_t i = 0; i < rows; i++) {
+        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q];
+        for (const auto &x : s.v) { t += '\t'; put_u64(t, x[ranked[i].at]); }
+        t += '\n';
+    }
+    write_file(out_prefix + "-genotype.tsv", t);
+}
+
+// Every pair from the cheapest up: by cost, then the homozygous pair before a heterozygous one, then p, then q.  No row scored:
+// no call, and a table with its header only.
+void likelihood_write(const MapOptions &opt, const Counters &s, MapOutput &out, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    const uint64_t n_scored = s.n[0];
+    struct Pair { uint32_t p, q; uint64_t cost; };
+    std::vector<Pair> ranked;
+    if (n_scored)
+        for (uint32_t p = 0; p < np; p++)
+            for (uint32_t q = p; q < np; q++) ranked.push_back({p, q, s.v[0][vga_pair_index(np, p, q)]});
+    std::sort(ranked.begin(), ranked.end(), [](const Pair &a, const Pair &b) {
+        if (a.cost != b.cost) return a.cost < b.cost;
+        if ((a.p == a.q) != (b.p == b.q)) return a.p == a.q;
+        return a.p != b.p ? a.p < b.p : a.q < b.q;
+    });
+    out.n_likelihood_scored = n_scored;
+    if (!ranked.empty()) {
+        out.likelihood_a = opt.paths.names[ranked[0].p]; out.likelihood_b = opt.paths.names[ranked[0].q];
+        out.likelihood_cost = ranked[0].cost;
+        out.likelihood_next = ranked.size() > 1 ? ranked[1].cost - ranked[0].cost : 0;
+    }
+    if (out_prefix.empty()) return;
+    std::string t = "rank\tpath_a\tpath_b\tcost\tmargin\n";
+    const size_t rows = opt.genotype_top ? std::min<size_t>(opt.genotype_top, ranked.size()) : ranked.size();
+    for (size_t i = 0; i < rows; i++) {
+        put_u64(t, i + 1); t += '\t'; t += opt.paths.names[ranked[i].p]; t += '\t'; t += opt.paths.names[ranked[i].q]; t += '\t';
+        put_u64(t, ranked[i].cost); t += '\t'; put_u64(t, ranked[i].cost - ranked[0].cost); t += '\n';
+    }
+    write_file(out_prefix + "-genotype-likelihood.tsv", t);
+}
+
+}  // namespace
+
+void check_aligner(const MapOptions &opt)
+{
+    if (opt.genotype_likelihood && !opt.also_align) throw Error("--genotype-likelihood calls from alignments: it needs --also-align");
+    if (opt.genotype_likelihood && opt.paths.n_paths() == 0) throw Error("--genotype-likelihood: the graph has no P line");
+    if (opt.genotype_likelihood && !likelihood_params_ok(opt)) throw Error("--genotype-likelihood: --genotype-lambda is 1 to 4096 and --genotype-cap 1 to 255");
+    if (opt.genotype_from_edit && !opt.genotype_likelihood) throw Error("--genotype-from has no meaning without --genotype-likelihood");
+    if (opt.path_edit && !opt.also_align) throw Error("--path-edit scores alignments: it needs --also-align");
+    if (opt.path_edit && opt.paths.n_paths() == 0) throw Error("--path-edit: the graph has no P line");
+    if (opt.genotype && !opt.also_align) throw Error("--genotype calls from alignments: it needs --also-align");
+    if (opt.genotype && opt.paths.n_paths() == 0) throw Error("--genotype: the graph has no P line");
+    if (opt.path_support && !opt.also_align) throw Error("--path-support scores alignments: it needs --also-align");
+    if (opt.path_support && opt.paths.n_paths() == 0) throw Error("--path-support: the graph has no P line");
+    if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
+    if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
+    if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
+    if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
+    if (opt.poa_aligner != "abpoa") {
+        if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
+        throw Error("POA Aligner not recognized");  // map_main.rs:67
+    }
+}
+
+Tables::Tables(const Index &ix, const MapOptions &opt) : ix_(ix), opt_(opt) {}
+
+void Tables::begin(vga_ctx *ctx) const
+{
+    if (coverage()) check(ctx, vga_coverage_begin(ctx));
+    if (scoring()) {  // path support and what is built on it
+        check(ctx, vga_path_support_begin(ctx, (uint32_t)opt_.paths.n_paths(), opt_.paths.step_off.data(), opt_.paths.steps.data(), nullptr));
+        if (edit()) check(ctx, vga_path_edit_begin(ctx));
+        if (opt_.genotype) check(ctx, vga_genotype_begin(ctx));
+        if (opt_.genotype_likelihood) check(ctx, vga_genotype_lik_begin(ctx, opt_.genotype_lambda, opt_.genotype_cap));
+        if (opt_.genotype_likelihood && opt_.genotype_from_edit) check(ctx, vga_genotype_lik_source(ctx, VGA_GL_FROM_EDIT));
+    }
+    if (piling()) check(ctx, vga_pileup_begin(ctx));
+}
+
+void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const
+{
+    const size_t np = opt_.paths.n_paths();
+    // one line per pair (aligned read, path) that keep(at) lets through: the read, the path, then the pair's value in each matrix
+    auto put_rows = [&](std::string &dst, std::initializer_list<const std::vector<uint32_t> *> matrices, auto keep) {
+        for (uint64_t r = 0; r < n; r++)
+            for (size_t p = 0; aligned[r] && p < np; p++)
+                if (keep(r * np + p)) {
+                    put_u64(dst, b0 + r); dst += '\t'; put_u64(dst, p);
+                    for (const std::vector<uint32_t> *m : matrices) { dst += '\t'; put_u64(dst, (*m)[r * np + p]); }
+                    dst += '\n';
+                }
+    };
+    if (opt_.path_support) {  // the reads x paths table
+        std::vector<uint32_t> pb(n * np + 1), pe(n * np + 1);
+        check(ctx, vga_path_support_last(ctx, n, pb.data(), pe.data()));
+        put_rows(rows.path, {&pb, &pe}, [&](size_t at) { return pb[at] || pe[at]; });
+        mark("path support rows");
+    }
+    if (opt_.path_edit) {  // the scored pairs of the reads x paths edit distances
+        std::vector<uint32_t> ed(n * np + 1);
+        check(ctx, vga_path_edit_last(ctx, n, ed.data()));
+        put_rows(rows.edit, {&ed}, [&](size_t at) { return ed[at] != 0xFFFFFFFFu; });
+        mark("path edit rows");
+    }
+}
+
+void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
+{
+    const size_t np = opt_.paths.n_paths(), n_pairs = vga_pair_count(np);
+    if (coverage()) {
+        Counters t;
+        std::vector<uint32_t> b(ix_.seq_length + 1), nd(ix_.n_nodes + 1), ed(ix_.n_edges + 1);
+        check(ctx, vga_coverage_read(ctx, b.data(), nd.data(), ed.data(), &t.n[0]));
+        t.v = {widen(b, ix_.seq_length), widen(nd, ix_.n_nodes), widen(ed, ix_.n_edges)};
+        coverage_.add(t);
+    }
+    if (scoring()) {
+        Counters t;
+        t.pad({np, np, np, np});
+        check(ctx, vga_path_support_read(ctx, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data(), &t.n[0], &t.n[1]));
+        paths_.add(t);
+    }
+    if (opt_.genotype) {
+        Counters t;
+        t.pad({n_pairs, n_pairs, n_pairs, n_pairs});
+        check(ctx, vga_genotype_read(ctx, n_pairs, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data()));
+        pairs_.add(t);
+    }
+    if (opt_.genotype_likelihood) {
+        Counters t;
+        t.pad({n_pairs});
+        check(ctx, vga_genotype_lik_read(ctx, n_pairs, t.v[0].data(), &t.n[0]));
+        costs_.add(t);
+    }
+    if (edit()) {
+        Counters t;
+        t.pad({np, np, np, np});
+        check(ctx, vga_path_edit_read(ctx, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data(), &t.n[0], &t.n[1]));
+        edit_.add(t);
+    }
+    // (VGA_TRACE: what each of the two routes to the sites costs at the device's end, tests/prof_variant.py)
+    const auto t0 = std::chrono::steady_clock::now();
+    if (opt_.pileup || (opt_.call_variants && !call_now)) {
+        Counters t;
+        std::vector<uint32_t> c(ix_.seq_length * 7 + 1);
+        check(ctx, vga_pileup_read(ctx, c.data(), &t.n[0], &t.n[1]));
+        t.v = {widen(c, ix_.seq_length * 7)};
+        pileup_.add(t);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    if (opt_.call_variants && call_now)
+        variant_fetch(ctx, variants_, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
+            return vga_variant_call(ctx, opt_.call_error, opt_.call_min_depth, opt_.call_min_qual, cap, pos, gt, qual, iq, depth, counts, nt, nc);
+        });
+    if (piling() && getenv("VGA_TRACE"))
+        fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
+                std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+}
+
+void Tables::end(vga_ctx *ctx) const
+{
+    if (coverage()) (void)vga_coverage_end(ctx);
+    if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
+    if (piling()) (void)vga_pileup_end(ctx);
+}
+
+void Tables::add(const Tables &o)
+{
+    coverage_.add(o.coverage_);
+    paths_.add(o.paths_);
+    pairs_.add(o.pairs_);
+    costs_.add(o.costs_);
+    edit_.add(o.edit_);
+    pileup_.add(o.pileup_);
+}
+
+void Tables::call(vga_ctx *ctx)
+{
+    pileup_.pad({ix_.seq_length * 7});
+    variant_fetch(ctx, variants_, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
+        return vga_variant_call_table(ctx, ix_.seq_length, pileup_.v[0].data(), ix_.seq_fwd.data(), opt_.call_error, opt_.call_min_depth, opt_.call_min_qual, cap,
+                                      pos, gt, qual, iq, depth, counts, nt, nc);
+    });
+    trace_mark("variants called");
+}
+
+void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix)
+{
+    const size_t np = opt_.paths.n_paths(), n_pairs = vga_pair_count(np);
+    const bool files = !out_prefix.empty();
+    if (coverage()) {
+        coverage_.pad({ix_.seq_length, ix_.n_nodes, ix_.n_edges});
+        out.n_coverage = coverage_.n[0];
+        if (files) coverage_write(ix_, coverage_, out_prefix);
+        trace_mark("coverage tables written");
+    }
+    if (opt_.genotype) {
+        pairs_.pad({n_pairs, n_pairs, n_pairs, n_pairs});
+        genotype_write(opt_, pairs_, out, out_prefix);
+        trace_mark("genotype table written");
+    }
+    if (opt_.genotype_likelihood) {
+        costs_.pad({n_pairs});
+        likelihood_write(opt_, costs_, out, out_prefix);
+        trace_mark("genotype likelihood table written");
+    }
+    if (edit()) {
+        out.n_edit_alignments = edit_.n[0]; out.n_edit_too_long = edit_.n[1];
+        if (opt_.path_edit) {
+            edit_.pad({np, np, np, np});
+            if (files) path_edit_write(ix_, opt_, edit_, rows.edit, out_prefix);
+            trace_mark("path edit tables written");
+        }
+    }
+    if (scoring()) {
+        out.n_path_scored = paths_.n[0]; out.n_path_unplaced = paths_.n[1];
+        if (opt_.path_support) {
+            paths_.pad({np, np, np, np});
+            if (files) path_support_write(opt_, paths_, rows.path, out_prefix);
+            trace_mark("path support tables written");
+        }
+    }
+    if (opt_.call_variants) {
+        out.n_variant_tested = variants_.n_tested; out.n_variant_calls = variants_.n_calls;
+        if (files) variant_write(ix_, variants_, out_prefix);
+        trace_mark("variants written");
+    }
+    if (opt_.pileup) {
+        pileup_.pad({ix_.seq_length * 7});
+        out.n_pileup = pileup_.n[0]; out.n_leading_ins = pileup_.n[1];
+        if (files) pileup_write(ix_, pileup_, out_prefix);
+        trace_mark("pileup table written");
+    }
+}
+
+}  // namespace vgh

@@ -1,0 +1,92 @@
+// vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
+// --genotype-likelihood, --path-edit, --call-variants): what a context has counted and scored, added over the contexts in 64 bits,
+// and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
+// context through begin .. write and know nothing of the single analyses.
+#pragma once
+
+#include "vgh.hpp"
+
+#include <functional>
+
+namespace vgh {
+
+inline void put_u64(std::string &s, uint64_t v)
+{
+    char t[24];
+    int n = 0;
+    do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (n) s.push_back(t[--n]);
+}
+
+void write_file(const std::string &name, const std::string &body);
+
+// A few vectors of 64-bit counters and two scalar counts.  A table nothing was read into (a device slot that got no read) has no
+// vectors at all: add() grows to the larger side and pad() fills up to the sizes a writer indexes.
+struct Counters {
+    std::vector<std::vector<uint64_t>> v;
+    uint64_t n[2] = {0, 0};
+    void add(const Counters &o);
+    void pad(const std::vector<size_t> &sizes);
+};
+
+// The variant calls as the library returns them (MapOptions::call_variants)
+struct VariantCalls {
+    std::vector<uint32_t> pos, qual;
+    std::vector<uint8_t> gt;
+    std::vector<uint64_t> ins_qual, depth, counts;  // counts: 7 per call
+    uint64_t n_tested = 0, n_calls = 0;
+};
+
+// The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
+struct ReadRows {
+    std::string path, edit;
+    void operator+=(const ReadRows &o) { path += o.path; edit += o.edit; }
+};
+
+// the options are refused here when they contradict each other (before any device is opened)
+void check_aligner(const MapOptions &opt);
+
+class Tables {
+public:
+    // `ix` and `opt` outlive the object
+    Tables(const Index &ix, const MapOptions &opt);
+
+    // Which analyses run.  Each of --genotype, --genotype-likelihood and --path-edit turns the scoring on, not its files; the
+    // likelihood from the edit distance turns that on; --call-variants turns the counting of the pileup on, not its file.
+    bool coverage() const { return opt_.coverage || opt_.coverage_only; }
+    bool scoring() const { return scoring_on(opt_); }
+    bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit); }
+    bool piling() const { return opt_.pileup || opt_.call_variants; }
+    bool any() const { return coverage() || scoring() || piling(); }
+    // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
+    bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
+
+    // turns the analyses on, on a context that holds the index
+    void begin(vga_ctx *ctx) const;
+    // the rows of reads [b0, b0 + n), the most recent vga_align_batch of ctx, while the context still holds them (`aligned`: of that
+    // call's result; mark(what): a trace mark after each of the two tables)
+    void chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const;
+    // What the context has counted and scored so far joins this object.  call_now: the variants are called from the context's own
+    // counters; otherwise its pileup table is kept for the sum.  (`slot` names the context in the trace.)
+    void take(vga_ctx *ctx, uint32_t slot, bool call_now);
+    // turns the analyses off on a context that stays with the caller
+    void end(vga_ctx *ctx) const;
+    void add(const Tables &o);
+    // the variants of the summed pileup table, called on `ctx` (any context: its own counters are not touched)
+    void call(vga_ctx *ctx);
+    // the TSV files beside the GAF files (out_prefix == "": none) and the fields of `out`
+    void write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix);
+
+private:
+    const Index &ix_;
+    const MapOptions &opt_;
+    Counters coverage_;  // base, node, edge; n: alignments
+    Counters paths_;     // sum_bases, sum_edges, top, top_alone; n: alignments, unplaced
+    Counters pairs_;     // sum_bases, sum_edges, prefer_a, prefer_b at vga_pair_index
+    Counters costs_;     // cost at vga_pair_index, in 1/256 bit; n: rows scored
+    Counters edit_;      // n_scored, sum_edit, best, best_alone; n: alignments, too long
+    Counters pileup_;    // seq_length x 7; n: alignments, leading insertions
+    VariantCalls variants_;
+};
+
+}  // namespace vgh
