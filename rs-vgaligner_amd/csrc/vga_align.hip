@@ -93,7 +93,6 @@ struct align_call {
     int begin_result();
     void pick_winners();
     int count_winners();
-    int pile_up_winners();
     int fill_result();
 };
 
@@ -118,15 +117,10 @@ int align_call::reverse_complements()
 // permuted into launch order here and poa_run's sort keeps them; the host route leaves the ordering to poa_run.
 int align_call::plan()
 {
-    if (cov && !on_device)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
-                             "vga_align_batch: read coverage is not counted under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
-    if (ps && !on_device)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
-                             "vga_align_batch: path support is not scored under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
-    if (pu && !on_device)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED,
-                             "vga_align_batch: the pileup is not counted under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)");
+    // the list makers read the subgraph store's handles on the device
+    const char *refused = on_device ? nullptr : cov ? "read coverage is not counted" : ps ? "path support is not scored" : pu ? "the pileup is not counted" : nullptr;
+    if (refused)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_align_batch: %s under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)", refused);
     align_select(m, align_best_n, prob_read, prob_chain, read_prob0);
     n = prob_read.size();
     proxy.resize(n);
@@ -276,15 +270,15 @@ void align_call::pick_winners()
     });
 }
 
-// coverage and path support count the reported record of every read and nothing else
+// coverage, path support and the pileup count the reported record of every read and nothing else
 int align_call::count_winners()
 {
     std::vector<uint32_t> winners, reads;
     for (uint64_t r = 0; r < R; r++)
         if (pick[r] >= 0) { winners.push_back((uint32_t)pick[r]); reads.push_back((uint32_t)r); }
+    int rc = VGA_OK;
     cov_win_view v;
-    int rc = cov_stage_winners(ctx, lists, winners, v);
-    if (rc != VGA_OK) return rc;
+    if (lists && (rc = cov_stage_winners(ctx, lists, winners, v)) != VGA_OK) return rc;
     if (cov) {
         if ((rc = cov_add_winners(ctx, cov, winners.size())) != VGA_OK) return rc;
         tr.mark("coverage");
@@ -298,18 +292,11 @@ int align_call::count_winners()
         if ((rc = ps_score_winners(ctx, ps, v, reads, R, &q)) != VGA_OK) return rc;
         tr.mark("path support");
     }
+    if (pu) {  // from lists of its own
+        if ((rc = pu_add_winners(ctx, pu, winners)) != VGA_OK) return rc;
+        tr.mark("pileup");
+    }
     return VGA_OK;
-}
-
-// the pileup counts the same records, from lists of its own
-int align_call::pile_up_winners()
-{
-    std::vector<uint32_t> winners;
-    for (uint64_t r = 0; r < R; r++)
-        if (pick[r] >= 0) winners.push_back((uint32_t)pick[r]);
-    const int rc = pu_add_winners(ctx, pu, winners);
-    if (rc == VGA_OK) tr.mark("pileup");
-    return rc;
 }
 
 int align_call::fill_result()
@@ -395,8 +382,7 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     if ((rc = c.run_poa()) != VGA_OK) return rc;
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     c.pick_winners();
-    if (c.lists && (rc = c.count_winners()) != VGA_OK) return rc;
-    if (c.pu && (rc = c.pile_up_winners()) != VGA_OK) return rc;
+    if ((c.lists || c.pu) && (rc = c.count_winners()) != VGA_OK) return rc;
     if ((rc = c.fill_result()) != VGA_OK) return rc;
     *out = c.res.release();
     return VGA_OK;

@@ -9,15 +9,10 @@
 // adds the winners' lists to the counters: a difference array over the bases, a word per node, a word per edge slot.
 #pragma once
 
-#include "vga_common.hpp"
-#include "vga_poa_launch.hpp"
-#include "vga_subgraph.hpp"
+#include "vga_oplist.hpp"
 
-// one problem's list: n_nodes node ids, then n_events words (position << 1 | 1 for a -1 event), at word `off` of its buffer
-struct cov_rec {
-    uint32_t off, n_nodes, n_events;
-    uint32_t flags;  // 0 nothing (the problem has no alignment yet), 1 in the call's device buffer, 2 no room there, 3 built by the host
-};
+// one problem's list (vga_oplist.hpp): n_a node ids, then n_b event words (position << 1 | 1 for a -1 event); flags 0 to 3
+using cov_rec = oplist_rec;
 
 struct cov_state;
 // The lists have two readers: the coverage counters (k_cov_add) and path support (vga_path_support.hip: k_ps_score).  The state
@@ -30,18 +25,13 @@ cov_state *cov_lists_active(vga_ctx *ctx);
 // a reader turns itself on (creates the state if it is the first) / off (the last one out releases it)
 int cov_lists_acquire(vga_ctx *ctx, uint32_t user, const char *who);
 void cov_lists_release(vga_ctx *ctx, uint32_t user);
-// start of a poa_run call of n problems whose queries hold total_q bases: the buffer of lists is sized and its cursor zeroed
-int cov_call_begin(vga_ctx *ctx, cov_state *cv, uint64_t n, uint64_t total_q);
+// the lists of the call in progress
+oplist_call &cov_lists(cov_state *cv);
 // k_cov_runs for the nb problems staged on a slot, and the copy of their records into the slot's result set `oset`
-hipError_t cov_enqueue_runs(vga_ctx *ctx, cov_state *cv, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b, const uint32_t *ids,
-                            const sg_store &store);
-// the records of a finished launch (valid once its stream is synchronised)
-const cov_rec *cov_launch_recs(const cov_state *cv, int slot, int oset);
-// keeps the record of problem p (a later run of the same problem replaces it)
-void cov_keep(cov_state *cv, uint32_t p, const cov_rec &r);
-// the host route for a problem whose list found no room: the same list from the operations as they came back (stored sink -> source)
-void cov_keep_from_ops(cov_state *cv, uint32_t p, const uint8_t *ops, const uint32_t *orow, uint32_t nops, const uint32_t *first_row, uint32_t n_nodes,
-                       const uint32_t *handles, const std::vector<uint32_t> &node_start);
+hipError_t cov_enqueue_runs(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
+                            const uint32_t *ids, const sg_store &store);
+// the host route for a problem whose list found no room: the same list from the operations as they came back
+void cov_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o);
 // the records of the winners (problem indices of the call that just ended) and the lists the host built go to the device, on the
 // context's stream; `v` is what a kernel launched on that stream afterwards reads (all null for no winners)
 struct cov_win_view {

@@ -88,11 +88,11 @@ __global__ __launch_bounds__(64) void k_pe_jobs(uint32_t n, const cov_rec *__res
         const uint32_t word = p >> 5, bit = 1u << (p & 31u);
         uint32_t a = 0, b = 0;
         if (m >= 1u && m <= PE_MAX_QUERY) {
-            for (uint32_t t = 0; t < rc.n_nodes; t++) {
+            for (uint32_t t = 0; t < rc.n_a; t++) {
                 const uint32_t id = nodes[t];
                 if (id >= 1u && id <= n_graph_nodes && (node_paths[(size_t)(id - 1u) * PW + word] & bit)) { a = id; break; }
             }
-            for (uint32_t t = rc.n_nodes; a && t-- > 0;) {
+            for (uint32_t t = rc.n_a; a && t-- > 0;) {
                 const uint32_t id = nodes[t];
                 if (id >= 1u && id <= n_graph_nodes && (node_paths[(size_t)(id - 1u) * PW + word] & bit)) { b = id; break; }
             }

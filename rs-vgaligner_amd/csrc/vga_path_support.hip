@@ -94,9 +94,9 @@ __global__ __launch_bounds__(64) void k_ps_score(uint32_t n, const cov_rec *__re
     for (uint32_t q = 0; q < n_blocks; q++) { s_b[q * 64 + lane] = 0u; s_e[q * 64 + lane] = 0u; }
     const cov_rec rc = recs[wi];
     const uint32_t *nodes = (rc.flags == 3u ? host_lists : lists) + rc.off;
-    const uint32_t *ev = nodes + rc.n_nodes;
+    const uint32_t *ev = nodes + rc.n_a;
     // ---- bases
-    const uint32_t n_runs = rc.n_events >> 1;
+    const uint32_t n_runs = rc.n_b >> 1;
     for (uint32_t base = 0; base < n_runs; base += 64) {
         const uint32_t r = base + (uint32_t)lane;
         uint32_t cur = 0, end = 0, node = 0;  // the part of the run still to be handed out, and the (0-based) node `cur` lies in
@@ -127,10 +127,10 @@ __global__ __launch_bounds__(64) void k_ps_score(uint32_t n, const cov_rec *__re
         }
     }
     // ---- edges
-    for (uint32_t base = 0; base + 1 < rc.n_nodes; base += 64) {
+    for (uint32_t base = 0; base + 1 < rc.n_a; base += 64) {
         const uint32_t i = base + (uint32_t)lane;
         uint32_t slot = 0xFFFFFFFFu;
-        if (i + 1 < rc.n_nodes) {
+        if (i + 1 < rc.n_a) {
             const uint32_t a = nodes[i], b = nodes[i + 1];
             if (a >= 1u && a <= n_graph_nodes && b >= 1u && b <= n_graph_nodes) {
                 const uint32_t want = b << 1, e1 = edge_idx[a];
@@ -415,7 +415,7 @@ static int ps_lists(vga_ctx *ctx, ps_state *ps, uint64_t n, const uint64_t *node
                 const uint32_t s = ix.node_start[node_ids[t] - 1];
                 words.push_back(s << 1);
                 words.push_back(((s + node_bases[t]) << 1) | 1u);
-                rc.n_events += 2;
+                rc.n_b += 2;
             }
         if (words.size() >= 0xFFFFFF00ull) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_path_support_lists: lists too long");
         recs[i] = rc;

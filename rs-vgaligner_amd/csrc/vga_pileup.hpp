@@ -10,46 +10,32 @@
 // difference array of match depth and to the table of the sparse operations; k_pu_finish, on read, prefix-sums the match depth into
 // the column of every base's own letter.
 //
-// The price of lists of its own is a second copy of code that has to stay in step: k_pu_events repeats k_cov_runs' walk (which
-// row opens a node, the offset carried from block to block, runs cut by position) and k_poa_text's query index, k_pu_finish
-// k_cov_depth's scan, and pu_call_begin / pu_enqueue_events / pu_add_winners the cov_* functions of the same names.  Whoever
-// changes the meaning of an operation, of a row record or of the subgraph store's handles in one of them changes it here too.
+// What the pileup shares with coverage -- the walk over the operations on the device and on the host, the record of a list and
+// the per-call store of lists -- has one copy, in vga_oplist.hpp; here is what is the pileup's own.
 #pragma once
 
-#include "vga_common.hpp"
-#include "vga_poa_launch.hpp"
-#include "vga_subgraph.hpp"
+#include "vga_oplist.hpp"
 
 // columns of the table
 enum : uint32_t { PU_COL_N = 4u, PU_COL_DEL = 5u, PU_COL_INS = 6u, PU_COLS = 7u };
 // a sparse word is position << 3 | column
 #define PU_MAX_SEQ (1ull << 29)
 
-// one problem's list: n_match event words (position << 1 | 1 for a -1 event), then n_sparse words, at word `off` of its buffer
-struct pu_rec {
-    uint32_t off, n_match, n_sparse;
-    uint32_t flags;  // low two bits: 0 nothing (the problem has no alignment yet), 1 in the call's device buffer, 2 no room there,
-                     // 3 built by the host; bit 2: the alignment starts with an insertion (it belongs to no base)
-};
-#define PU_LEADING 4u
+// one problem's list (vga_oplist.hpp): n_a event words of its runs of matches (position << 1 | 1 for a -1 event), then n_b sparse
+// words; flags 0 to 3, and PU_LEADING
+using pu_rec = oplist_rec;
 
 struct pu_state;
 // the context's pileup state while counting is on (vga_pileup_begin), else null
 pu_state *pu_active(vga_ctx *ctx);
-// start of a poa_run call of n problems whose queries hold total_q bases: the buffer of lists is sized (cap_words caps it when
-// has_cap: VGA_PILEUP_LIST_WORDS) and its cursor zeroed
-int pu_call_begin(vga_ctx *ctx, pu_state *pu, uint64_t n, uint64_t total_q, bool has_cap, uint64_t cap_words);
+// the lists of the call in progress
+oplist_call &pu_lists(pu_state *pu);
 // k_pu_events for the nb problems staged on a slot, and the copy of their records into the slot's result set `oset`
-hipError_t pu_enqueue_events(vga_ctx *ctx, pu_state *pu, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b, const uint32_t *ids,
-                             const sg_store &store);
-// the records of a finished launch (valid once its stream is synchronised)
-const pu_rec *pu_launch_recs(const pu_state *pu, int slot, int oset);
-// keeps the record of problem p (a later run of the same problem replaces it)
-void pu_keep(pu_state *pu, uint32_t p, const pu_rec &r);
-// the host route for a problem whose list found no room: the same list from the operations as they came back (stored sink ->
-// source); bases[r - 1] is the base of graph row r, query the sequence that was aligned
-void pu_keep_from_ops(pu_state *pu, uint32_t p, const uint8_t *ops, const uint32_t *orow, uint32_t nops, const uint32_t *first_row, uint32_t n_nodes,
-                      const uint32_t *handles, const std::vector<uint32_t> &node_start, const char *bases, uint32_t n_rows, const char *query);
+hipError_t pu_enqueue_events(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
+                             const uint32_t *ids, const sg_store &store);
+// the host route for a problem whose list found no room: the same list from the operations as they came back, with the bases of
+// both sides
+void pu_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o);
 // k_pu_add over the lists of the winners (problem indices of the call that just ended), on the context's stream; waits for it
 int pu_add_winners(vga_ctx *ctx, pu_state *pu, const std::vector<uint32_t> &winners);
 // k_pu_finish on the context's stream, not waited for: the table vga_pileup_read copies out (seq_length x PU_COLS), left on the

@@ -270,8 +270,17 @@ struct poa_call {
     vga_trace tr{"poa"};
     poa_ws &W;
     poa_pool pool;
-    cov_state *const cov;  // coverage or path support is on (cov_lists_active) and the graphs are in the device store: k_cov_runs beside k_poa_text
-    pu_state *const pu;    // the pileup is counted (pu_active) and the graphs are in the device store: k_pu_events behind k_cov_runs
+    // A list maker that is on while the graphs are in the device store (vga_oplist.hpp): its kernel runs behind k_poa_text.
+    // Coverage's k_cov_runs while coverage or path support is on (cov_lists_active), the pileup's k_pu_events while it is counted
+    struct list_maker {
+        oplist_call *lists;
+        const char *what;  // as the trace calls its list
+        bool has_cap;      // VGA_COV_LIST_WORDS / VGA_PILEUP_LIST_WORDS
+        uint64_t cap_words;
+        decltype(&cov_enqueue_runs) enqueue;
+        decltype(&cov_keep_from_ops) keep_from_ops;
+    };
+    std::vector<list_maker> makers;
     uint32_t max_q = 0;
     // ---- plan: node tables, estimates, launch order
     std::vector<poa_prep> G;
@@ -311,8 +320,12 @@ struct poa_call {
 
     poa_call(vga_ctx *c, poa_feed &f, const vga_poa_params *p, std::vector<poa_item> &o, poa_timing &t)
         : ctx(c), feed(f), params(p), out(o), tm(t), n(f.views.size()), views(f.views), sw(poa_read_switches()),
-          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n), cov(f.dev ? cov_lists_active(c) : nullptr),
-          pu(f.dev ? pu_active(c) : nullptr) {}
+          family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n)
+    {
+        if (!f.dev) return;
+        if (cov_state *cv = cov_lists_active(c)) makers.push_back({&cov_lists(cv), "run list", sw.has_cov_words, sw.cov_words, cov_enqueue_runs, cov_keep_from_ops});
+        if (pu_state *pu = pu_active(c)) makers.push_back({&pu_lists(pu), "pileup list", sw.has_pileup_words, sw.pileup_words, pu_enqueue_events, pu_keep_from_ops});
+    }
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
     void chk(hipError_t e) { if (e != hipSuccess && launch_err == hipSuccess) launch_err = e; }
@@ -339,8 +352,7 @@ struct poa_call {
     void stage(const launch_t &L);
     void launch_dp(launch_t &L);
     void enqueue_results(const launch_t &L);
-    void collect_coverage(const sub_t &cur, const poa_slot::out_set &S);
-    void collect_pileup(const sub_t &cur, const poa_slot::out_set &S);
+    void collect_lists(const list_maker &m, const sub_t &cur, const poa_slot::out_set &S);
     void fill();
     // fetch its text, requeue, post-process, account
     void collect();
@@ -750,10 +762,9 @@ void poa_call::enqueue_results(const launch_t &L)
         // 17 KB per problem, instead of a handle lookup per aligned base)
         if (feed.dev) chk(hipMemcpyAsync(O.h_seq.p, S.d_seq32.p, L.tot_seq, hipMemcpyDeviceToHost, st));
     }
-    // coverage: the run list of every problem, while its operations are in the slot (the refill recycles them)
-    if (cov && launch_err == hipSuccess) chk(cov_enqueue_runs(ctx, cov, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
-    // pileup: likewise, the list of its matched runs and sparse operations
-    if (pu && launch_err == hipSuccess) chk(pu_enqueue_events(ctx, pu, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
+    // coverage's run list and the pileup's list of every problem, while its operations are in the slot (the refill recycles them)
+    for (const list_maker &m : makers)
+        if (launch_err == hipSuccess) chk(m.enqueue(ctx, *m.lists, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
 }
 
 // stage, upload and enqueue DP + traceback + result copies of a sub-batch that starts at launch position i0 and ends
@@ -837,11 +848,9 @@ bool poa_call::fetch_text(const sub_t &cur, poa_slot::out_set &S)
     uint64_t no_text = 0;  // problems that found the arena full
     for (uint64_t i = cur.i0; i < cur.i1; i++) no_text += S.h_touts.p[i - cur.i0].flags == 2u ? 1u : 0u;
     bool overflow = no_text != 0;
-    // (coverage: a problem whose run list found no room is served from the operations too)
-    if (cov)
-        for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || cov_launch_recs(cov, cur.slot, cur.oset)[i - cur.i0].flags == 2u;
-    if (pu)
-        for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || (pu_launch_recs(pu, cur.slot, cur.oset)[i - cur.i0].flags & 3u) == 2u;
+    // (a problem whose run list or pileup list found no room is served from the operations too)
+    for (const list_maker &m : makers)
+        for (uint64_t i = cur.i0; i < cur.i1; i++) overflow = overflow || (m.lists->launch_recs(cur.slot, cur.oset)[i - cur.i0].flags & 3u) == 2u;
     hipError_t ce = hipSuccess;
     if (feed.keep_text) {
         // a buffer of the context's that holds the text: the smallest free one that fits, else the largest free one grows
@@ -926,38 +935,21 @@ void poa_call::requeue_handed_back(const sub_t &cur, const poa_slot::out_set &S)
     }
 }
 
-// coverage: the run-list records of a finished sub-batch join the call's; a list that found no room in the buffer is built here,
-// from the operations fetch_text brought back
-void poa_call::collect_coverage(const sub_t &cur, const poa_slot::out_set &S)
+// the list records of a finished sub-batch join the call's, for one maker; a list that found no room in the buffer is built here,
+// from what fetch_text brought back (the operations and the gathered node sequences; the query is the problem's view of the read)
+void poa_call::collect_lists(const list_maker &m, const sub_t &cur, const poa_slot::out_set &S)
 {
-    const cov_rec *recs = cov_launch_recs(cov, cur.slot, cur.oset);
+    const oplist_rec *recs = m.lists->launch_recs(cur.slot, cur.oset);
     for (uint64_t i = cur.i0; i < cur.i1; i++) {
         const uint32_t p = order[i];
         const poa_out &ho = S.h_outs.p[i - cur.i0];
         if (ho.status != POA_ST_OK) continue;
-        const cov_rec &r = recs[i - cur.i0];
-        if (r.flags != 2u) { cov_keep(cov, p, r); continue; }
-        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its run list, built from the operations\n", p);
-        cov_keep_from_ops(cov, p, S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1,
-                          feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start);
-    }
-}
-
-// pileup: the same for its lists; the host route needs the bases of both sides as well (the gathered node sequences came back with
-// the operations, the query is the problem's view of the read)
-void poa_call::collect_pileup(const sub_t &cur, const poa_slot::out_set &S)
-{
-    const pu_rec *recs = pu_launch_recs(pu, cur.slot, cur.oset);
-    for (uint64_t i = cur.i0; i < cur.i1; i++) {
-        const uint32_t p = order[i];
-        const poa_out &ho = S.h_outs.p[i - cur.i0];
-        if (ho.status != POA_ST_OK) continue;
-        const pu_rec &r = recs[i - cur.i0];
-        if ((r.flags & 3u) != 2u) { pu_keep(pu, p, r); continue; }
-        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its pileup list, built from the operations\n", p);
-        pu_keep_from_ops(pu, p, S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1,
-                         feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start, S.h_seq.p + probs[p].seq0, probs[p].N,
-                         views[p].query);
+        const oplist_rec &r = recs[i - cur.i0];
+        if ((r.flags & 3u) != 2u) { m.lists->keep(p, r); continue; }
+        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its %s, built from the operations\n", p, m.what);
+        m.keep_from_ops(*m.lists, p, {S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1, probs[p].N,
+                                      feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start.data(), S.h_seq.p + probs[p].seq0,
+                                      views[p].query});
     }
 }
 
@@ -1006,8 +998,7 @@ void poa_call::collect()
         poa_slot::out_set &S = W.slot[cur.slot].outs[cur.oset];
         if (launch_err != hipSuccess) break;
         if (!fetch_text(cur, S)) break;
-        if (cov) collect_coverage(cur, S);
-        if (pu) collect_pileup(cur, S);
+        for (const list_maker &m : makers) collect_lists(m, cur, S);
         bool pool_fail = false;
         for (uint64_t i = cur.i0; i < cur.i1; i++)
             if (S.h_outs.p[i - cur.i0].status == POA_ST_POOL) {
@@ -1150,15 +1141,11 @@ int poa_run(vga_ctx *ctx, poa_feed &feed, const vga_poa_params *params, std::vec
     poa_call c(ctx, feed, params, out, tm);
     int rc = c.validate();
     if (rc != VGA_OK || c.n == 0) return rc;
-    if (c.cov) {
+    if (!c.makers.empty()) {
         uint64_t total_q = 0;
         for (const poa_view &v : c.views) total_q += v.qlen;
-        if ((rc = cov_call_begin(ctx, c.cov, c.n, total_q)) != VGA_OK) return rc;
-    }
-    if (c.pu) {
-        uint64_t total_q = 0;
-        for (const poa_view &v : c.views) total_q += v.qlen;
-        if ((rc = pu_call_begin(ctx, c.pu, c.n, total_q, c.sw.has_pileup_words, c.sw.pileup_words)) != VGA_OK) return rc;
+        for (const auto &m : c.makers)
+            if ((rc = m.lists->begin(ctx, c.n, total_q, m.has_cap, m.cap_words)) != VGA_OK) return rc;
     }
     if ((rc = c.order_problems()) != VGA_OK) return rc;
     if ((rc = c.size_pool()) != VGA_OK) return rc;

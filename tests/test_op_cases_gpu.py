@@ -3,7 +3,8 @@ block, the closing operation alone in a block, runs that hold whole blocks, run 
 (tests/test_op_cases_cpu.py shows from the oracle alone that the sets hold them).  Per set one map + align call with coverage,
 pileup and path support counting; every comparison is exact equality: the records against the oracle's alignments GAF
 (helpers.assert_record_equals), the tables against the reference walkers over that GAF.  The block-edge and digit sets run again
-on the routes around the kernels' defaults: text on the host, a text arena and lists too small for all problems of the call."""
+on the routes around the kernels' defaults: text on the host, a text arena and lists too small for all problems of the call;
+three of the DRB1 and synthetic sets run once more with no room for any list, so that the host's walk builds them all."""
 import collections
 import re
 
@@ -179,3 +180,18 @@ def test_lists_too_small_for_some_problems(ctx, wants, monkeypatch, capfd, name)
     assert 0 < by_host["run list"] < al.poa_problems
     # (the default buffer of drb5-edges is smaller than its longest pileup list: there every problem takes this route)
     assert 0 < by_host["pileup list"] < al.poa_problems + (name == "drb5-edges")
+
+
+@pytest.mark.parametrize("name", ("drb1-sweep", "synth-nodes", "drb1-both-strands"))
+def test_lists_all_built_by_the_host(ctx, wants, monkeypatch, capfd, name):
+    """list buffers of no words at all: the host's walk builds every list of the call.  These sets hold what the DRB5 sets cannot:
+    a node entered at lane 0 inside a match run, the leading insertion, I directly behind D, reverse-strand queries"""
+    monkeypatch.setenv("VGA_COV_LIST_WORDS", "0")
+    monkeypatch.setenv("VGA_PILEUP_LIST_WORDS", "0")
+    monkeypatch.setenv("VGA_TRACE", "1")
+    capfd.readouterr()
+    al = run(ctx, wants[name], name + ", no room for any list")
+    trace = capfd.readouterr().err
+    assert al.poa_problems == len(wants[name].lines)
+    assert built_by_host(trace, "run list") == al.poa_problems
+    assert built_by_host(trace, "pileup list") == al.poa_problems
