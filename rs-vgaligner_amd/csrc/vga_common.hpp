@@ -11,7 +11,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -20,6 +22,22 @@
 #include "vga_probe_hash.hpp"
 
 #define VGA_ABI_VERSION 6
+
+// The one owner of a state or workspace that a struct holds without seeing its type: the deleter is captured by vga_make_owned,
+// where the type is complete.  Empty until made; reset() releases now, the destructor at the latest.
+template <typename T>
+using vga_owned = std::unique_ptr<T, void (*)(T *)>;
+// a new U, held as T (void for a type that is private to its file); null when the allocation fails
+template <typename T, typename U = T>
+vga_owned<T> vga_make_owned()
+{
+    return vga_owned<T>(new (std::nothrow) U(), [](T *p) { delete static_cast<U *>(p); });
+}
+
+struct cov_state;
+struct ps_state;
+struct pu_state;
+struct poa_ws;
 
 struct vga_dev_index {
     uint32_t k = 0;
@@ -57,14 +75,11 @@ struct vga_dev_index {
     std::vector<uint32_t> edges;       // packed handles
     bool loaded = false;
     // run lists and read coverage counters of this index while coverage or path support is on (vga_coverage.hip): released with the index
-    void *cov = nullptr;
-    void (*cov_free)(void *) = nullptr;
+    vga_owned<cov_state> cov{nullptr, nullptr};
     // path support of this index while it is on (vga_path_support.hip): the path bitsets and the accumulators, released with the index
-    void *ps = nullptr;
-    void (*ps_free)(void *) = nullptr;
+    vga_owned<ps_state> ps{nullptr, nullptr};
     // the pileup table of this index while it is counted (vga_pileup.hip), with event lists of its own: released with the index
-    void *pu = nullptr;
-    void (*pu_free)(void *) = nullptr;
+    vga_owned<pu_state> pu{nullptr, nullptr};
 };
 
 struct vga_timer_entry {
@@ -107,16 +122,12 @@ struct vga_ctx {
     };
     std::vector<agg_t> last_times;
     int n_cu = 256;
-    // persistent, grow-only device workspaces (owned by the modules that use them): no hipMalloc/hipFree
-    // in the steady state of a call
-    void *map_ws = nullptr;
-    void (*map_ws_free)(void *) = nullptr;
-    void *poa_ws = nullptr;
-    void (*poa_ws_free)(void *) = nullptr;
-    void *sg_ws = nullptr;
-    void (*sg_ws_free)(void *) = nullptr;
-    void *gaf_ws = nullptr;
-    void (*gaf_ws_free)(void *) = nullptr;
+    // persistent, grow-only device workspaces (made by the modules that use them): no hipMalloc/hipFree
+    // in the steady state of a call.  map_ws, sg_ws and gaf_ws are private to their files: held as void
+    vga_owned<void> map_ws{nullptr, nullptr};
+    vga_owned<struct poa_ws> poa_ws{nullptr, nullptr};
+    vga_owned<void> sg_ws{nullptr, nullptr};
+    vga_owned<void> gaf_ws{nullptr, nullptr};
     // live read batches: vga_ctx_destroy releases their device memory and detaches them, so a batch handle may be
     // destroyed after its context
     std::vector<struct vga_batch *> batches;

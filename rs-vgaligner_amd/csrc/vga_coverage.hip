@@ -104,40 +104,26 @@ struct cov_state {
     oplist_call lists;  // of the vga_align_batch call in progress
 };
 
-cov_state *cov_lists_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (cov_state *)ctx->index.cov : nullptr; }
+cov_state *cov_lists_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.cov.get() : nullptr; }
 cov_state *cov_active(vga_ctx *ctx)
 {
     cov_state *cv = cov_lists_active(ctx);
     return cv && (cv->users & COV_USER_COVERAGE) ? cv : nullptr;
 }
 
-static void cov_release(vga_ctx *ctx)
-{
-    if (ctx->index.cov && ctx->index.cov_free) ctx->index.cov_free(ctx->index.cov);
-    ctx->index.cov = nullptr;
-    ctx->index.cov_free = nullptr;
-}
-
 int cov_lists_acquire(vga_ctx *ctx, uint32_t user, const char *who)
 {
-    try {
-        if (!ctx->index.cov) {
-            ctx->index.cov = new cov_state();
-            ctx->index.cov_free = [](void *q) { delete (cov_state *)q; };
-        }
-    } catch (const std::bad_alloc &) {
-        return vga_set_error(ctx, VGA_ERR_NOMEM, "%s: out of host memory", who);
-    }
-    ((cov_state *)ctx->index.cov)->users |= user;
+    if (!ctx->index.cov && !(ctx->index.cov = vga_make_owned<cov_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "%s: out of host memory", who);
+    ctx->index.cov->users |= user;
     return VGA_OK;
 }
 
 void cov_lists_release(vga_ctx *ctx, uint32_t user)
 {
-    cov_state *cv = (cov_state *)ctx->index.cov;
+    cov_state *cv = ctx->index.cov.get();
     if (!cv) return;
     cv->users &= ~user;
-    if (!cv->users) { cov_release(ctx); return; }
+    if (!cv->users) { ctx->index.cov.reset(); return; }
     if (user == COV_USER_COVERAGE) { cv->d_diff.release(); cv->d_node.release(); cv->d_edge.release(); cv->d_depth.release(); }
 }
 
@@ -212,7 +198,7 @@ extern "C" int vga_coverage_begin(vga_ctx *ctx)
     vga_ctx_scope scope(ctx);
     int rc = cov_lists_acquire(ctx, COV_USER_COVERAGE, "vga_coverage_begin");
     if (rc != VGA_OK) return rc;
-    cov_state *cv = (cov_state *)ctx->index.cov;
+    cov_state *cv = ctx->index.cov.get();
     cv->seq_length = (uint32_t)ix.seq_length; cv->n_nodes = (uint32_t)ix.n_nodes; cv->n_edges = (uint32_t)ix.n_edges;
     hipError_t e = cv->d_diff.reserve((size_t)cv->seq_length + 1);
     if (e == hipSuccess) e = cv->d_node.reserve((size_t)cv->n_nodes + 1);

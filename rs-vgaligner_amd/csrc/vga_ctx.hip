@@ -155,9 +155,9 @@ void vga_index_release(vga_dev_index &ix)
     if (ix.d_edge_idx) (void)hipFree(ix.d_edge_idx);
     if (ix.d_edges_to) (void)hipFree(ix.d_edges_to);
     if (ix.d_edges) (void)hipFree(ix.d_edges);
-    if (ix.cov && ix.cov_free) ix.cov_free(ix.cov);  // (counting stops with the index it counted on)
-    if (ix.ps && ix.ps_free) ix.ps_free(ix.ps);      // (and so does path support)
-    if (ix.pu && ix.pu_free) ix.pu_free(ix.pu);      // (and the pileup)
+    ix.cov.reset();  // (counting stops with the index it counted on)
+    ix.ps.reset();   // (and so does path support)
+    ix.pu.reset();   // (and the pileup)
     ix = vga_dev_index();
 }
 
@@ -176,10 +176,10 @@ extern "C" void vga_ctx_destroy(vga_ctx *ctx)
         b->d_read_off2 = nullptr;
         b->ctx = nullptr;
     }
-    if (ctx->map_ws && ctx->map_ws_free) ctx->map_ws_free(ctx->map_ws);
-    if (ctx->poa_ws && ctx->poa_ws_free) ctx->poa_ws_free(ctx->poa_ws);
-    if (ctx->sg_ws && ctx->sg_ws_free) ctx->sg_ws_free(ctx->sg_ws);
-    if (ctx->gaf_ws && ctx->gaf_ws_free) ctx->gaf_ws_free(ctx->gaf_ws);
+    ctx->map_ws.reset();
+    ctx->poa_ws.reset();
+    ctx->sg_ws.reset();
+    ctx->gaf_ws.reset();
     vga_index_release(ctx->index);
     for (hipEvent_t ev : ctx->event_pool) (void)hipEventDestroy(ev);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -162,11 +162,8 @@ static int vga_chain_paths_text_impl(vga_ctx *ctx, const vga_map_result *m, vga_
     const uint64_t n_members = nc ? m->chain_anchor_off[nc] : 0;
     if (nc == 0 || n_members == 0) { *out = res.release(); return VGA_OK; }
     if (nc >= (1ull << 31)) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "too many chains in one call");
-    if (!ctx->gaf_ws) {
-        ctx->gaf_ws = new gaf_ws();
-        ctx->gaf_ws_free = [](void *q) { delete (gaf_ws *)q; };
-    }
-    gaf_ws &W = *(gaf_ws *)ctx->gaf_ws;
+    if (!ctx->gaf_ws && !(ctx->gaf_ws = vga_make_owned<void, gaf_ws>())) throw std::bad_alloc();
+    gaf_ws &W = *(gaf_ws *)ctx->gaf_ws.get();
     if (!W.st) VGA_HIP_CHECK_OOM(ctx, hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking));
     st = W.st;
     VGA_HIP_CHECK_OOM(ctx, W.h_chains.reserve(nc)); VGA_HIP_CHECK_OOM(ctx, W.d_chains.reserve(nc));

@@ -8,12 +8,12 @@
 //   prefer_a, prefer_b     the reads with key[r][p] > key[r][q], and with key[r][q] > key[r][p],
 // in 64 bits, at vga_pair_index(n_paths, p, q) of four arrays of vga_pair_count(n_paths) words laid out one after the other.
 //
-// k_gt_pairs is a product of the two matrices in the (max, +) semiring with a triangular output, and is tiled like one.  A
-// workgroup of 256 threads owns a tile of GT_TILE x GT_TILE pairs of the upper triangle (tiles below the diagonal are not
+// k_gt_pairs is a product of the two matrices in the (max, +) semiring with a triangular output, and is tiled like one (the frame
+// it shares with k_gl_pairs is vga_pair_tile.hpp).  A workgroup of 256 threads owns a tile of GT_TILE x GT_TILE pairs of the upper triangle (tiles below the diagonal are not
 // launched; a tile on it computes the whole square and stores p <= q) and a range of reads.  It stages the keys of its two path
 // ranges through LDS, GT_READS reads at a time, so a matrix element is read from HBM once per tile; a thread keeps the four
 // accumulators of its 4 x 4 pairs (p = ty + 16 i, q = tx + 16 j) in registers over all its reads and adds them to the table with
-// one 64-bit atomic each at the end.  With few tiles the reads are split over workgroups (gt_groups), which the atomics combine:
+// one 64-bit atomic each at the end.  With few tiles the reads are split over workgroups (vga_split_reads), which the atomics combine:
 // integer sums do not depend on the order.  LDS rows are [read][path] with one 64-bit key (bases << 32 | edges) per path: the 16 lanes that share
 // ty read 16 consecutive q keys (32 consecutive banks) and one broadcast p key, so no access conflicts.
 #pragma once

@@ -5,21 +5,19 @@
 // Overflow.  k_gl_pairs keeps TWICE the cost of a pair in one 32-bit register: LDS holds 2 d and 2 T, so that the absolute
 // difference of two staged values is the byte offset of its table entry and no shift is needed per pair-read.  One read adds at
 // most 2 (lambda cap + T[cap]) <= 2 (4096 * 255 + 256) = 2 089 472 to a register, so floor((2^32 - 1) / 2 089 472) = 2055 reads
-// fit; a workgroup takes at most GL_MAX_GROUP_READS = 2048 (gl_groups), which makes the flush interval the workgroup's own end:
+// fit; a workgroup takes at most GL_MAX_GROUP_READS = 2048 (vga_split_reads), which makes the flush interval the workgroup's own end:
 // there it halves the register (exact: every addend is even) and adds it to the 64-bit table with one atomic.  A call of more
 // reads is split over more workgroups, and the atomics combine them in 64 bits.
 #include "vga_genotype_lik.hpp"
-#include "vga_common.hpp"
-#include "vga_pair_index.hpp"
+#include "vga_pair_tile.hpp"
 #include "vga_path_edit.hpp"
 #include "vga_path_support.hpp"
 
 #include <algorithm>
-#include <new>
 
 namespace {
 
-constexpr uint32_t GL_THREADS = 256u, GL_SUB = 8u;  // a thread's pairs: GL_SUB x GL_SUB, GL_TILE / GL_SUB = 16 threads on a side
+constexpr uint32_t GL_THREADS = PAIR_TILE_THREADS, GL_SUB = 8u;  // a thread's pairs: GL_SUB x GL_SUB, GL_TILE / GL_SUB = 16 threads on a side
 static_assert(GL_TILE == 16u * GL_SUB && GL_THREADS == 16u * 16u, "a 16 x 16 thread grid covers the tile");
 static_assert((GL_READS * GL_TILE) % GL_THREADS == 0, "staging: whole rounds per path range");
 static_assert(2ull * (GL_MAX_LAMBDA * GL_MAX_CAP + 256ull) * GL_MAX_GROUP_READS <= 0xFFFFFFFFull, "a workgroup's reads fit the 32-bit accumulators");
@@ -47,9 +45,8 @@ __global__ __launch_bounds__(256) void k_gl_deficit(uint32_t n_reads, uint32_t n
     if (lane == 0 && scored) atomicAdd(n_scored, (unsigned long long)scored);
 }
 
-// blockIdx.x: the tile (tp, tq), tp <= tq, of the n_side x n_side tile grid in vga_pair_index order; blockIdx.y: the range of
-// reads [y reads_per_group, (y + 1) reads_per_group) cut at n_reads, reads_per_group <= GL_MAX_GROUP_READS.  table2: 256 entries,
-// 2 T[x] (x past cap repeats T[cap] and is never indexed: both deficits are <= cap).  cost: n_pairs words.
+// The tile and the reads of a workgroup: pair_tile_open (vga_pair_tile.hpp), reads_per_group <= GL_MAX_GROUP_READS.  table2: 256
+// entries, 2 T[x] (x past cap repeats T[cap] and is never indexed: both deficits are <= cap).  cost: n_pairs words.
 __global__ __launch_bounds__(256) void k_gl_pairs(uint32_t n_reads, uint32_t n_paths, uint32_t n_side, uint32_t reads_per_group, uint32_t lambda,
                                                    const uint8_t *__restrict__ deficit, const uint16_t *__restrict__ table2,
                                                    unsigned long long *__restrict__ cost)
@@ -59,14 +56,8 @@ __global__ __launch_bounds__(256) void k_gl_pairs(uint32_t n_reads, uint32_t n_p
     __shared__ __attribute__((aligned(16))) uint16_t d_p[GL_READS][GL_TILE];
     __shared__ __attribute__((aligned(16))) uint16_t d_q[GL_READS][GL_TILE];
     __shared__ uint16_t t2[256];
-    uint32_t t = blockIdx.x, tp = 0;
-    while (t >= n_side - tp) { t -= n_side - tp; tp++; }
-    const uint32_t p0 = tp * GL_TILE, q0 = (tp + t) * GL_TILE;
-    const uint32_t tid = threadIdx.x, tx = tid & 15u, ty = tid >> 4;
-    const uint32_t r_begin = blockIdx.y * reads_per_group;
-    const uint32_t r_end = min(n_reads, r_begin + reads_per_group);
-    // a thread whose first p or first q is past the last path has no pair to store (few paths: most of the tile)
-    const bool live = p0 + ty < n_paths && q0 + tx < n_paths;
+    const pair_tile T = pair_tile_open<GL_TILE>(n_reads, n_paths, n_side, reads_per_group);
+    const uint32_t tid = threadIdx.x, tx = T.tx, ty = T.ty, r_end = T.r_end;
     t2[tid] = table2[tid];  // (the first barrier of the loop below comes before its first use)
 
     uint32_t acc[GL_SUB][GL_SUB];  // twice the cost of the thread's pairs over the workgroup's reads
@@ -75,29 +66,26 @@ __global__ __launch_bounds__(256) void k_gl_pairs(uint32_t n_reads, uint32_t n_p
 #pragma unroll
         for (uint32_t j = 0; j < GL_SUB; j++) acc[i][j] = 0;
 
-    for (uint32_t r0 = r_begin; r0 < r_end; r0 += GL_READS) {
-        // 64 consecutive lanes read 64 consecutive paths of one read; a read or path past the end is staged as 0 (its load goes to
-        // element 0, so that the rounds' loads are issued together, without branches) and is never stored to the table
+    for (uint32_t r0 = T.r_begin; r0 < r_end; r0 += GL_READS) {
+        // a read or path past the end is staged as 0 (pair_tile_slot) and is never stored to the table
         constexpr uint32_t ROUNDS = GL_READS * GL_TILE / GL_THREADS;  // per path range
 #pragma unroll
         for (uint32_t side = 0; side < 2u; side++) {
             uint32_t v[ROUNDS];
 #pragma unroll
             for (uint32_t k = 0; k < ROUNDS; k++) {
-                const uint32_t idx = k * GL_THREADS + tid;
-                const uint32_t r = r0 + idx / GL_TILE, path = (side ? q0 : p0) + idx % GL_TILE;
-                const bool have = r < r_end && path < n_paths;
-                const uint32_t d = deficit[have ? (size_t)r * n_paths + path : 0];
-                v[k] = have ? 2u * d : 0u;
+                const pair_slot s = pair_tile_slot<GL_TILE>(T, n_paths, k, tid, r0, side);
+                const uint32_t d = deficit[s.have ? (size_t)s.read * n_paths + s.path : 0];
+                v[k] = s.have ? 2u * d : 0u;
             }
 #pragma unroll
             for (uint32_t k = 0; k < ROUNDS; k++) {
-                const uint32_t idx = k * GL_THREADS + tid, o = idx % GL_TILE;
-                (side ? d_q : d_p)[idx / GL_TILE][(o & 15u) * GL_SUB + (o >> 4)] = (uint16_t)v[k];
+                const pair_slot s = pair_tile_slot<GL_TILE>(T, n_paths, k, tid, r0, side);
+                (side ? d_q : d_p)[s.row][(s.col & 15u) * GL_SUB + (s.col >> 4)] = (uint16_t)v[k];
             }
         }
         __syncthreads();
-        if (live) {
+        if (T.live) {
             const uint32_t nr = min(GL_READS, r_end - r0);
             for (uint32_t rr = 0; rr < nr; rr++) {
                 const uint4 wp = *reinterpret_cast<const uint4 *>(&d_p[rr][ty * GL_SUB]);
@@ -124,29 +112,12 @@ __global__ __launch_bounds__(256) void k_gl_pairs(uint32_t n_reads, uint32_t n_p
         }
         __syncthreads();
     }
-    if (!live) return;
-#pragma unroll
-    for (uint32_t i = 0; i < GL_SUB; i++)
-#pragma unroll
-        for (uint32_t j = 0; j < GL_SUB; j++) {
-            const uint32_t p = p0 + ty + 16u * i, q = q0 + tx + 16u * j;
-            if (p > q || q >= n_paths) continue;
-            if (acc[i][j]) atomicAdd(cost + vga_pair_index(n_paths, p, q), (unsigned long long)(acc[i][j] >> 1));
-        }
+    if (!T.live) return;
+    pair_tile_each<GL_SUB>(T, n_paths, [&](uint32_t i, uint32_t j, unsigned long long at) {
+        if (acc[i][j]) atomicAdd(cost + at, (unsigned long long)(acc[i][j] >> 1));
+    });
 }
 
-// how the reads of a call are split: the rule of gt_groups (enough workgroups to fill the device when there are few tiles, never
-// fewer than GL_MIN_CHUNKS chunks per workgroup), and never more than GL_MAX_GROUP_READS reads per workgroup
-struct gl_split { uint32_t groups, reads_per_group; };
-gl_split gl_groups(uint32_t n_reads, uint32_t n_tiles, int n_cu)
-{
-    const uint32_t chunks = (n_reads + GL_READS - 1u) / GL_READS;
-    const uint32_t want = (4u * (uint32_t)std::max(n_cu, 1) + n_tiles - 1u) / n_tiles;
-    const uint32_t most = std::max(1u, chunks / GL_MIN_CHUNKS);
-    const uint32_t groups = std::max(1u, std::min({want, most, 65535u}));
-    const uint32_t per = std::min((chunks + groups - 1u) / groups, GL_MAX_GROUP_READS / GL_READS);
-    return {(chunks + per - 1u) / per, per * GL_READS};
-}
 // the reads of one call: the y dimension of k_gl_pairs' grid holds 65 535 workgroups of GL_MAX_GROUP_READS reads
 constexpr uint64_t GL_MAX_CALL_READS = 65535ull * GL_MAX_GROUP_READS;
 
@@ -161,21 +132,11 @@ void gl_launch(vga_ctx *ctx, uint32_t n_reads, uint32_t n_paths, uint32_t lambda
                        d_cost + vga_pair_count(n_paths));
     vga_timer_end(ctx, t);
     const uint32_t n_side = (n_paths + GL_TILE - 1u) / GL_TILE, n_tiles = (uint32_t)vga_pair_count(n_side);
-    const gl_split s = gl_groups(n_reads, n_tiles, ctx->n_cu);
+    const vga_read_split s = vga_split_reads(n_reads, n_tiles, ctx->n_cu, GL_READS, GL_MIN_CHUNKS, GL_MAX_GROUP_READS);
     t = vga_timer_begin(ctx, "k_gl_pairs", 0, ctx->stream);
     hipLaunchKernelGGL(k_gl_pairs, dim3(n_tiles, s.groups), dim3(GL_THREADS), 0, ctx->stream, n_reads, n_paths, n_side, s.reads_per_group, lambda, d_deficit,
                        d_table2, d_cost);
     vga_timer_end(ctx, t);
-}
-
-// a device array of exactly n elements (the cost table is 67 MB at 4096 paths: no slack)
-template <typename T>
-int gl_exact_alloc(vga_ctx *ctx, vga_dbuf<T> &d, size_t n)
-{
-    vga_alloc_urgent urgent;
-    VGA_HIP_CHECK_OOM(ctx, hipMalloc((void **)&d.p, n * sizeof(T)));
-    d.cap = n;
-    return VGA_OK;
 }
 
 bool gl_params_ok(uint32_t lambda, uint32_t cap) { return lambda >= 1u && lambda <= GL_MAX_LAMBDA && cap >= 1u && cap <= GL_MAX_CAP; }
@@ -186,7 +147,7 @@ int gl_table_upload(vga_ctx *ctx, uint32_t lambda, uint32_t cap, uint16_t *h2, v
     uint32_t t[256];
     vga_gl_table(lambda, cap, t);
     for (uint32_t x = 0; x < 256u; x++) h2[x] = (uint16_t)(2u * t[std::min(x, cap)]);
-    int rc = gl_exact_alloc(ctx, d_table2, 256);
+    int rc = pair_exact_alloc(ctx, d_table2, 256);
     if (rc != VGA_OK) return rc;
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_table2.p, h2, 256 * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
     return VGA_OK;
@@ -195,19 +156,18 @@ int gl_table_upload(vga_ctx *ctx, uint32_t lambda, uint32_t cap, uint16_t *h2, v
 }  // namespace
 
 struct gl_state {
-    uint32_t n_paths = 0, lambda = 0, cap = 0;
+    uint32_t lambda = 0, cap = 0;
     uint32_t source = VGA_GL_FROM_SUPPORT;
-    uint64_t n_pairs = 0;
     uint16_t h_table2[256] = {};
     vga_dbuf<uint16_t> d_table2;
-    vga_dbuf<unsigned long long> d_cost;  // n_pairs words of cost, then n_scored
-    vga_dbuf<uint8_t> d_deficit;          // the byte deficits of the last call, n_reads x n_paths (grow-only)
+    pair_table cost;              // n_pairs words of cost, then n_scored
+    vga_dbuf<uint8_t> d_deficit;  // the byte deficits of the last call, n_reads x n_paths (grow-only)
 };
 
 gl_state *gl_active(vga_ctx *ctx)
 {
     ps_state *ps = ps_active(ctx);
-    return ps ? ps->gl : nullptr;
+    return ps ? ps->gl.get() : nullptr;
 }
 
 uint32_t gl_source(const gl_state *gl) { return gl->source; }
@@ -216,27 +176,13 @@ int gl_add_call(vga_ctx *ctx, gl_state *gl, uint64_t n_reads, const uint32_t *d_
 {
     if (n_reads == 0) return VGA_OK;
     if (n_reads > GL_MAX_CALL_READS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "genotype likelihood: too many reads in one call");
-    VGA_HIP_CHECK_OOM(ctx, gl->d_deficit.reserve((size_t)n_reads * gl->n_paths));
-    gl_launch(ctx, (uint32_t)n_reads, gl->n_paths, gl->lambda, gl->cap, d_bases, d_edges, gl->d_deficit.p, gl->d_table2.p, gl->d_cost.p);
+    VGA_HIP_CHECK_OOM(ctx, gl->d_deficit.reserve((size_t)n_reads * gl->cost.n_paths));
+    gl_launch(ctx, (uint32_t)n_reads, gl->cost.n_paths, gl->lambda, gl->cap, d_bases, d_edges, gl->d_deficit.p, gl->d_table2.p, gl->cost.d.p);
     VGA_HIP_CHECK(ctx, hipGetLastError());
     return VGA_OK;
 }
 
 // ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
-static void gl_release(ps_state *ps)
-{
-    if (ps->gl && ps->gl_free) ps->gl_free(ps->gl);
-    ps->gl = nullptr;
-    ps->gl_free = nullptr;
-}
-
-static int gl_zero(vga_ctx *ctx, gl_state *gl)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(gl->d_cost.p, 0, ((size_t)gl->n_pairs + 1) * sizeof(unsigned long long), ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
-}
-
 extern "C" int vga_genotype_lik_table(uint32_t lambda, uint32_t cap, uint32_t *out)
 {
     if (!gl_params_ok(lambda, cap) || !out) return VGA_ERR_ARG;
@@ -249,25 +195,13 @@ extern "C" int vga_genotype_lik_begin(vga_ctx *ctx, uint32_t lambda, uint32_t ca
     if (!ctx) return VGA_ERR_ARG;
     if (!gl_params_ok(lambda, cap))
         return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_begin: lambda %u, cap %u: lambda is 1 to %u and cap 1 to %u", lambda, cap, GL_MAX_LAMBDA, GL_MAX_CAP);
-    ps_state *ps = ps_active(ctx);
-    if (!ps) return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_begin: path support is off (vga_path_support_begin)");
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    gl_release(ps);  // (a second begin starts over)
-    gl_state *gl = new (std::nothrow) gl_state();
-    if (!gl) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_genotype_lik_begin: out of host memory");
-    ps->gl = gl;
-    ps->gl_free = [](gl_state *g) { delete g; };
-    gl->n_paths = ps->n_paths;
-    gl->n_pairs = vga_pair_count(ps->n_paths);
-    gl->lambda = lambda;
-    gl->cap = cap;
-    int rc = gl_exact_alloc(ctx, gl->d_cost, (size_t)gl->n_pairs + 1);
-    if (rc == VGA_OK) rc = gl_table_upload(ctx, lambda, cap, gl->h_table2, gl->d_table2);
-    if (rc == VGA_OK) rc = gl_zero(ctx, gl);
-    if (rc != VGA_OK) gl_release(ps);
-    return rc;
+    return ps_child_begin(ctx, "vga_genotype_lik_begin", &ps_state::gl, [&](ps_state *ps, gl_state *gl) {
+        gl->lambda = lambda;
+        gl->cap = cap;
+        int rc = gl->cost.alloc(ctx, ps->n_paths, 1, 1);
+        if (rc == VGA_OK) rc = gl_table_upload(ctx, lambda, cap, gl->h_table2, gl->d_table2);
+        return rc == VGA_OK ? gl->cost.zero(ctx) : rc;
+    });
 }
 
 extern "C" int vga_genotype_lik_source(vga_ctx *ctx, uint32_t source)
@@ -287,20 +221,13 @@ extern "C" int vga_genotype_lik_reset(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
     gl_state *gl = gl_active(ctx);
-    if (!gl) return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_reset: the likelihood is off (vga_genotype_lik_begin)");
-    (void)hipSetDevice(ctx->device);
-    return gl_zero(ctx, gl);
+    return ps_child_reset(ctx, gl != nullptr, "vga_genotype_lik_reset: the likelihood is off (vga_genotype_lik_begin)", [&]() { return gl->cost.zero(ctx); });
 }
 
 extern "C" int vga_genotype_lik_end(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ps_state *ps = ps_active(ctx);
-    if (!ps) return VGA_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    gl_release(ps);
-    return VGA_OK;
+    return ps_child_end(ctx, &ps_state::gl);
 }
 
 extern "C" int vga_genotype_lik_read(vga_ctx *ctx, uint64_t n_pairs, uint64_t *cost, uint64_t *n_scored)
@@ -308,55 +235,39 @@ extern "C" int vga_genotype_lik_read(vga_ctx *ctx, uint64_t n_pairs, uint64_t *c
     if (!ctx) return VGA_ERR_ARG;
     gl_state *gl = gl_active(ctx);
     if (!gl) return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_read: the likelihood is off (vga_genotype_lik_begin)");
-    if (n_pairs != gl->n_pairs)
-        return vga_set_error(ctx, VGA_ERR_ARG, "vga_genotype_lik_read: the table has %llu pairs (%u paths), not %llu", (unsigned long long)gl->n_pairs,
-                             gl->n_paths, (unsigned long long)n_pairs);
+    const int rc = gl->cost.check(ctx, "vga_genotype_lik_read", n_pairs);
+    if (rc != VGA_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    if (cost) VGA_HIP_CHECK(ctx, hipMemcpyAsync(cost, gl->d_cost.p, (size_t)gl->n_pairs * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (n_scored) VGA_HIP_CHECK(ctx, hipMemcpyAsync(n_scored, gl->d_cost.p + gl->n_pairs, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
+    return gl->cost.read(ctx, &cost, n_scored);
 }
 
 // The kernel seam: explicit matrices through k_gl_deficit and k_gl_pairs into a table of its own.
 static int gl_pairs(vga_ctx *ctx, uint64_t n_reads, uint32_t n_paths, const uint32_t *bases, const uint32_t *edges, uint32_t lambda, uint32_t cap,
                     uint8_t *deficit_out, uint64_t *cost_out, uint64_t *n_scored)
 {
-    const size_t n_pairs = vga_pair_count(n_paths), cells = (size_t)n_reads * n_paths;
+    const size_t cells = (size_t)n_reads * n_paths;
     hipStream_t st = ctx->stream;
-    vga_dbuf<unsigned long long> d_cost;
+    pair_table cost;
     vga_dbuf<uint16_t> d_table2;
     vga_dbuf<uint32_t> d_b, d_e;
     vga_dbuf<uint8_t> d_def;
     uint16_t h2[256];
-    int rc = gl_exact_alloc(ctx, d_cost, n_pairs + 1);
+    int rc = cost.alloc(ctx, n_paths, 1, 1);
     if (rc != VGA_OK) return rc;
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_cost.p, 0, (n_pairs + 1) * sizeof(unsigned long long), st));
+    VGA_HIP_CHECK(ctx, cost.clear(st));
     vga_timers_reset(ctx);
     if (n_reads) {
+        VGA_HIP_CHECK_OOM(ctx, d_def.reserve(cells));
         rc = gl_table_upload(ctx, lambda, cap, h2, d_table2);
-        if (rc != VGA_OK) { (void)hipStreamSynchronize(st); return rc; }
-        hipError_t e = d_b.reserve(cells);
-        if (e == hipSuccess) e = d_e.reserve(cells);
-        if (e == hipSuccess) e = d_def.reserve(cells);
-        if (e != hipSuccess) (void)hipStreamSynchronize(st);  // (h2 is on its way)
-        VGA_HIP_CHECK_OOM(ctx, e);
-        e = hipMemcpyAsync(d_b.p, bases, cells * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_e.p, edges, cells * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            gl_launch(ctx, (uint32_t)n_reads, n_paths, lambda, cap, d_b.p, d_e.p, d_def.p, d_table2.p, d_cost.p);
-            e = hipGetLastError();
-        }
+        if (rc == VGA_OK) rc = pair_upload(ctx, cells, bases, edges, d_b, d_e);
+        if (rc != VGA_OK) { (void)hipStreamSynchronize(st); return rc; }  // (h2 is on its way)
+        gl_launch(ctx, (uint32_t)n_reads, n_paths, lambda, cap, d_b.p, d_e.p, d_def.p, d_table2.p, cost.d.p);
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess && deficit_out) e = hipMemcpyAsync(deficit_out, d_def.p, cells, hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) (void)hipStreamSynchronize(st);
         VGA_HIP_CHECK(ctx, e);
     }
-    hipError_t e = hipSuccess;
-    if (cost_out) e = hipMemcpyAsync(cost_out, d_cost.p, n_pairs * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_scored) e = hipMemcpyAsync(n_scored, d_cost.p + n_pairs, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    VGA_HIP_CHECK(ctx, e);
-    VGA_HIP_CHECK(ctx, es);
+    if ((rc = cost.read(ctx, &cost_out, n_scored)) != VGA_OK) return rc;
     vga_timers_collect(ctx);
     return VGA_OK;
 }

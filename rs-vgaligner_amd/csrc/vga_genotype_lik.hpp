@@ -13,7 +13,7 @@
 // have some s > 0.  The table of costs sits at vga_pair_index(n_paths, p, q), one 64-bit word per pair.
 //
 // Two kernels.  k_gl_deficit gives a wave a row: the lanes stride over the row's paths (coalesced along the path axis), reduce
-// the maximum of s across the wave, and write the row's byte deficits.  k_gl_pairs is tiled like k_gt_pairs: a workgroup of 256
+// the maximum of s across the wave, and write the row's byte deficits.  k_gl_pairs stands on the frame of vga_pair_tile.hpp: a workgroup of 256
 // threads owns a GL_TILE x GL_TILE tile of pairs of the upper triangle and a range of reads, stages the deficits of its two path
 // ranges through LDS GL_READS reads at a time, keeps one 32-bit accumulator per pair in registers (8 x 8 pairs per thread,
 // p = ty + 16 i, q = tx + 16 j), looks T up in LDS, and ends with one 64-bit atomic per pair.

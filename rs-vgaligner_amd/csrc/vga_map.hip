@@ -1048,12 +1048,9 @@ static int vga_map_batch_impl(vga_batch *b, const vga_map_params *params, vga_ma
     vga_release_deferred(ctx);  // (buffers of this context that grew during an earlier call: freed now, while it has nothing in flight)
     int rc = map_validate(ctx, params);
     if (rc != VGA_OK) return rc;
-    if (!ctx->map_ws) {
-        ctx->map_ws = new map_ws();
-        ctx->map_ws_free = [](void *p) { delete (map_ws *)p; };
-    }
+    if (!ctx->map_ws && !(ctx->map_ws = vga_make_owned<void, map_ws>())) throw std::bad_alloc();
     vga_timers_reset(ctx);
-    map_call c(b, params, *(map_ws *)ctx->map_ws);
+    map_call c(b, params, *(map_ws *)ctx->map_ws.get());
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     if (c.R > 0) {
         if ((rc = c.count()) != VGA_OK) return rc;

@@ -7,7 +7,6 @@
 #include "vga_path_support.hpp"
 
 #include <algorithm>
-#include <new>
 
 // (query, lo, hi, path): the job of one reported alignment and one path.  lo > hi: no window, the pair is not scored.
 struct pe_job { uint32_t query, lo, hi, path; };
@@ -19,7 +18,7 @@ struct pe_state {
     vga_dbuf<unsigned long long> d_seq_off;       // n_paths + 1: seq_p is d_seq[d_seq_off[p] .. d_seq_off[p + 1])
     vga_dbuf<unsigned long long> d_fwd_off, d_fwd;  // per path its forward steps as (node << 32 | step within the path), sorted
     vga_dbuf<uint8_t> d_seq;                      // one letter code per path base
-    vga_dbuf<unsigned long long> d_acc;           // n_scored, sum_edit, best, best_alone (n_paths each), n_alignments, n_too_long
+    ps_acc_block acc;                             // n_scored, sum_edit, best, best_alone (n_paths each), n_alignments, n_too_long
     // ---- the last call
     vga_dbuf<uint32_t> d_edit, d_gl_bases, d_gl_edges, d_qlen;
     vga_dbuf<unsigned long long> d_qoff;
@@ -268,7 +267,7 @@ void pe_launch_dist(vga_ctx *ctx, const bool *has, uint32_t n_jobs, const pe_job
 pe_state *pe_active(vga_ctx *ctx)
 {
     ps_state *ps = ps_active(ctx);
-    return ps ? ps->pe : nullptr;
+    return ps ? ps->pe.get() : nullptr;
 }
 
 const uint32_t *pe_gl_bases(const pe_state *pe) { return pe->d_gl_bases.p; }
@@ -276,7 +275,7 @@ const uint32_t *pe_gl_edges(const pe_state *pe) { return pe->d_gl_edges.p; }
 
 int pe_add_call(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const uint32_t *d_rows, uint64_t nw, uint64_t n_reads, const pe_queries &q, bool with_gl)
 {
-    pe_state *pe = ps->pe;
+    pe_state *pe = ps->pe.get();
     const vga_dev_index &ix = ctx->index;
     const size_t cells = (size_t)n_reads * pe->n_paths, n_jobs = (size_t)nw * pe->n_paths;
     hipStream_t st = ctx->stream;
@@ -311,7 +310,7 @@ int pe_add_call(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const uint32_
         pe_launch_dist(ctx, has, (uint32_t)n_jobs, pe->d_jobs.p, q.d_reads, pe->d_qoff.p, pe->d_qlen.p, pe->d_seq.p, pe->d_seq_off.p, d_rows, pe->n_paths, pe->d_edit.p);
         t = vga_timer_begin(ctx, "k_pe_rows", 0, st);
         hipLaunchKernelGGL(k_pe_rows, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, d_rows, pe->d_qlen.p, pe->n_paths, pe->d_edit.p,
-                           with_gl ? pe->d_gl_bases.p : nullptr, pe->d_acc.p);
+                           with_gl ? pe->d_gl_bases.p : nullptr, pe->acc.d.p);
         vga_timer_end(ctx, t);
         VGA_HIP_CHECK(ctx, hipGetLastError());
     }
@@ -321,20 +320,6 @@ int pe_add_call(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const uint32_
 }
 
 // ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
-static void pe_release(ps_state *ps)
-{
-    if (ps->pe && ps->pe_free) ps->pe_free(ps->pe);
-    ps->pe = nullptr;
-    ps->pe_free = nullptr;
-}
-
-static int pe_zero(vga_ctx *ctx, pe_state *pe)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(pe->d_acc.p, 0, (4 * (size_t)pe->n_paths + 2) * sizeof(unsigned long long), ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
-}
-
 static int pe_begin(vga_ctx *ctx, ps_state *ps, pe_state *pe)
 {
     const vga_dev_index &ix = ctx->index;
@@ -368,7 +353,7 @@ static int pe_begin(vga_ctx *ctx, ps_state *ps, pe_state *pe)
     VGA_HIP_CHECK_OOM(ctx, pe->d_fwd_off.reserve(np + 1));
     VGA_HIP_CHECK_OOM(ctx, pe->d_fwd.reserve(fwd.size() + 1));
     VGA_HIP_CHECK_OOM(ctx, pe->d_seq.reserve((size_t)total + 1));
-    VGA_HIP_CHECK_OOM(ctx, pe->d_acc.reserve(4 * (size_t)np + 2));
+    VGA_HIP_CHECK_OOM(ctx, pe->acc.reserve(np));
     VGA_HIP_CHECK_OOM(ctx, d_steps.reserve(n_steps + 1));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(pe->d_step_pos.p, pos.data(), (n_steps + 1) * 4, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(pe->d_step_off.p, ps->h_off.data(), (np + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
@@ -386,53 +371,26 @@ static int pe_begin(vga_ctx *ctx, ps_state *ps, pe_state *pe)
     }
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));  // (the host arrays above are on their way until here)
     vga_timers_collect(ctx);
-    return pe_zero(ctx, pe);
+    return pe->acc.zero(ctx);
 }
 
 extern "C" int vga_path_edit_begin(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ps_state *ps = ps_active(ctx);
-    if (!ps) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_begin: path support is off (vga_path_support_begin)");
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    pe_release(ps);  // (a second begin starts over)
-    pe_state *pe = new (std::nothrow) pe_state();
-    if (!pe) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_path_edit_begin: out of host memory");
-    ps->pe = pe;
-    ps->pe_free = [](pe_state *x) { delete x; };
-    int rc;
-    try {
-        rc = pe_begin(ctx, ps, pe);
-    } catch (const std::bad_alloc &) {
-        rc = vga_set_error(ctx, VGA_ERR_NOMEM, "vga_path_edit_begin: out of host memory");
-    }
-    if (rc != VGA_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        pe_release(ps);
-    }
-    return rc;
+    return ps_child_begin(ctx, "vga_path_edit_begin", &ps_state::pe, [&](ps_state *ps, pe_state *pe) { return pe_begin(ctx, ps, pe); });
 }
 
 extern "C" int vga_path_edit_reset(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
     pe_state *pe = pe_active(ctx);
-    if (!pe) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_reset: the edit distance is off (vga_path_edit_begin)");
-    (void)hipSetDevice(ctx->device);
-    return pe_zero(ctx, pe);
+    return ps_child_reset(ctx, pe != nullptr, "vga_path_edit_reset: the edit distance is off (vga_path_edit_begin)", [&]() { return pe->acc.zero(ctx); });
 }
 
 extern "C" int vga_path_edit_end(vga_ctx *ctx)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ps_state *ps = ps_active(ctx);
-    if (!ps) return VGA_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    pe_release(ps);
-    return VGA_OK;
+    return ps_child_end(ctx, &ps_state::pe);
 }
 
 extern "C" int vga_path_edit_read(vga_ctx *ctx, uint64_t *n_scored, uint64_t *sum_edit, uint64_t *best, uint64_t *best_alone, uint64_t *n_alignments,
@@ -442,17 +400,8 @@ extern "C" int vga_path_edit_read(vga_ctx *ctx, uint64_t *n_scored, uint64_t *su
     pe_state *pe = pe_active(ctx);
     if (!pe) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_read: the edit distance is off (vga_path_edit_begin)");
     (void)hipSetDevice(ctx->device);
-    const size_t np = pe->n_paths;
-    std::vector<unsigned long long> h(4 * np + 2);
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), pe->d_acc.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t *const dst[4] = {n_scored, sum_edit, best, best_alone};
-    for (int k = 0; k < 4; k++)
-        if (dst[k])
-            for (size_t p = 0; p < np; p++) dst[k][p] = h[k * np + p];
-    if (n_alignments) *n_alignments = h[4 * np];
-    if (n_too_long) *n_too_long = h[4 * np + 1];
-    return VGA_OK;
+    return pe->acc.read(ctx, dst, n_alignments, n_too_long);
 }
 
 extern "C" int vga_path_edit_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *edit)
@@ -460,15 +409,9 @@ extern "C" int vga_path_edit_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *edit
     if (!ctx) return VGA_ERR_ARG;
     pe_state *pe = pe_active(ctx);
     if (!pe) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_last: the edit distance is off (vga_path_edit_begin)");
-    if (!pe->have_last) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_last: no vga_align_batch has been scored on this context yet");
-    if (n_reads != pe->last_reads)
-        return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_edit_last: the last vga_align_batch had %llu reads, not %llu", (unsigned long long)pe->last_reads,
-                             (unsigned long long)n_reads);
-    (void)hipSetDevice(ctx->device);
-    const size_t bytes = (size_t)n_reads * pe->n_paths * 4;
-    if (edit && bytes) VGA_HIP_CHECK(ctx, hipMemcpyAsync(edit, pe->d_edit.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
+    uint32_t *const dst[2] = {edit, nullptr};
+    const uint32_t *const src[2] = {pe->d_edit.p, nullptr};
+    return ps_read_last(ctx, "vga_path_edit_last", pe->have_last, pe->last_reads, n_reads, pe->n_paths, dst, src);
 }
 
 // The kernel seam: explicit strings through k_pe_encode and k_pe_dist, job i = (query i, 0, |text i|, text i).

@@ -180,7 +180,43 @@ __global__ __launch_bounds__(64) void k_ps_score(uint32_t n, const cov_rec *__re
 
 }  // namespace
 
-ps_state *ps_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (ps_state *)ctx->index.ps : nullptr; }
+ps_state *ps_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.ps.get() : nullptr; }
+
+int ps_acc_block::zero(vga_ctx *ctx)
+{
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d.p, 0, words() * sizeof(unsigned long long), ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VGA_OK;
+}
+
+int ps_acc_block::read(vga_ctx *ctx, uint64_t *const col[4], uint64_t *s0, uint64_t *s1)
+{
+    const size_t np = n_paths;
+    std::vector<unsigned long long> h(words());
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), d.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 4; k++)
+        if (col[k])
+            for (size_t p = 0; p < np; p++) col[k][p] = h[k * np + p];
+    if (s0) *s0 = h[4 * np];
+    if (s1) *s1 = h[4 * np + 1];
+    return VGA_OK;
+}
+
+int ps_read_last(vga_ctx *ctx, const char *who, bool have_last, uint64_t last_reads, uint64_t n_reads, uint32_t n_paths, uint32_t *const dst[2],
+                 const uint32_t *const src[2])
+{
+    if (!have_last) return vga_set_error(ctx, VGA_ERR_ARG, "%s: no vga_align_batch has been scored on this context yet", who);
+    if (n_reads != last_reads)
+        return vga_set_error(ctx, VGA_ERR_ARG, "%s: the last vga_align_batch had %llu reads, not %llu", who, (unsigned long long)last_reads,
+                             (unsigned long long)n_reads);
+    (void)hipSetDevice(ctx->device);
+    const size_t bytes = (size_t)n_reads * n_paths * 4;
+    for (int k = 0; k < 2; k++)
+        if (dst[k] && bytes) VGA_HIP_CHECK(ctx, hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VGA_OK;
+}
 
 static void ps_launch_score(vga_ctx *ctx, const ps_state *ps, uint32_t n, const cov_win_view &v, const uint32_t *d_rows, uint32_t *d_bases,
                             uint32_t *d_edges, unsigned long long *d_acc)
@@ -207,9 +243,9 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         VGA_HIP_CHECK_OOM(ctx, ps->d_rows.reserve(nw));
         memcpy(ps->h_rows.p, reads.data(), nw * 4);
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(ps->d_rows.p, ps->h_rows.p, nw * 4, hipMemcpyHostToDevice, st));
-        ps_launch_score(ctx, ps, (uint32_t)nw, v, ps->d_rows.p, ps->d_bases.p, ps->d_edges.p, ps->d_acc.p);
+        ps_launch_score(ctx, ps, (uint32_t)nw, v, ps->d_rows.p, ps->d_bases.p, ps->d_edges.p, ps->acc.d.p);
         VGA_HIP_CHECK(ctx, hipGetLastError());
-        const bool gl_from_edit = ps->gl && gl_source(ps->gl) == VGA_GL_FROM_EDIT;
+        const bool gl_from_edit = ps->gl && gl_source(ps->gl.get()) == VGA_GL_FROM_EDIT;
         if (gl_from_edit && !ps->pe)
             return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the likelihood reads the edit distance (vga_genotype_lik_source), which is off (vga_path_edit_begin)");
         if (ps->pe) {  // the edit distance is on: its three kernels over the same winners, on the same stream
@@ -218,12 +254,12 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
             if (rc != VGA_OK) return rc;
         }
         if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
-            const int rc = gt_add_call(ctx, ps->gt, n_reads, ps->d_bases.p, ps->d_edges.p);
+            const int rc = gt_add_call(ctx, ps->gt.get(), n_reads, ps->d_bases.p, ps->d_edges.p);
             if (rc != VGA_OK) return rc;
         }
         if (ps->gl) {  // the read likelihood is on: the byte deficits of the two matrices and the cost of every pair, on the same stream
-            const int rc = gl_from_edit ? gl_add_call(ctx, ps->gl, n_reads, pe_gl_bases(ps->pe), pe_gl_edges(ps->pe))
-                                        : gl_add_call(ctx, ps->gl, n_reads, ps->d_bases.p, ps->d_edges.p);
+            const int rc = gl_from_edit ? gl_add_call(ctx, ps->gl.get(), n_reads, pe_gl_bases(ps->pe.get()), pe_gl_edges(ps->pe.get()))
+                                        : gl_add_call(ctx, ps->gl.get(), n_reads, ps->d_bases.p, ps->d_edges.p);
             if (rc != VGA_OK) return rc;
         }
     } else if (ps->pe) {  // (no winner: the call's matrix is all NONE)
@@ -241,17 +277,8 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
 // ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
 static void ps_release(vga_ctx *ctx)
 {
-    if (ctx->index.ps && ctx->index.ps_free) ctx->index.ps_free(ctx->index.ps);
-    ctx->index.ps = nullptr;
-    ctx->index.ps_free = nullptr;
+    ctx->index.ps.reset();
     cov_lists_release(ctx, COV_USER_PATHS);
-}
-
-static int ps_zero(vga_ctx *ctx, ps_state *ps)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(ps->d_acc.p, 0, (4 * (size_t)ps->n_paths + 2) * sizeof(unsigned long long), ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
 }
 
 static int ps_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, const uint64_t *steps, uint64_t *n_pairs_without_edge)
@@ -264,9 +291,8 @@ static int ps_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, co
     for (uint32_t p = 0; p <= n_paths; p++) off[p] = step_off[p] - step_off[0];
     int rc = cov_lists_acquire(ctx, COV_USER_PATHS, "vga_path_support_begin");
     if (rc != VGA_OK) return rc;
-    ps_state *ps = new ps_state();
-    ctx->index.ps = ps;
-    ctx->index.ps_free = [](void *q) { delete (ps_state *)q; };
+    if (!(ctx->index.ps = vga_make_owned<ps_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_path_support_begin: out of host memory");
+    ps_state *ps = ctx->index.ps.get();
     ps->n_paths = n_paths;
     ps->PW = (n_paths + 31u) / 32u;
     ps->h_off = off;
@@ -277,7 +303,7 @@ static int ps_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, co
     vga_dbuf<unsigned long long> d_off, d_missing;
     VGA_HIP_CHECK_OOM(ctx, ps->d_node_paths.reserve(node_words + 1));
     VGA_HIP_CHECK_OOM(ctx, ps->d_edge_paths.reserve(edge_words + 1));
-    VGA_HIP_CHECK_OOM(ctx, ps->d_acc.reserve(4 * (size_t)n_paths + 2));
+    VGA_HIP_CHECK_OOM(ctx, ps->acc.reserve(n_paths));
     VGA_HIP_CHECK_OOM(ctx, d_steps.reserve(total + 1));
     VGA_HIP_CHECK_OOM(ctx, d_off.reserve(n_paths + 1));
     VGA_HIP_CHECK_OOM(ctx, d_missing.reserve(1));
@@ -299,7 +325,7 @@ static int ps_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, co
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     vga_timers_collect(ctx);
     if (n_pairs_without_edge) *n_pairs_without_edge = missing;
-    return ps_zero(ctx, ps);
+    return ps->acc.zero(ctx);
 }
 
 extern "C" int vga_path_support_begin(vga_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, const uint64_t *steps, uint64_t *n_pairs_without_edge)
@@ -339,7 +365,7 @@ extern "C" int vga_path_support_reset(vga_ctx *ctx)
     ps_state *ps = ps_active(ctx);
     if (!ps) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_support_reset: path support is off (vga_path_support_begin)");
     (void)hipSetDevice(ctx->device);
-    return ps_zero(ctx, ps);
+    return ps->acc.zero(ctx);
 }
 
 extern "C" int vga_path_support_end(vga_ctx *ctx)
@@ -358,17 +384,8 @@ extern "C" int vga_path_support_read(vga_ctx *ctx, uint64_t *sum_bases, uint64_t
     ps_state *ps = ps_active(ctx);
     if (!ps) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_support_read: path support is off (vga_path_support_begin)");
     (void)hipSetDevice(ctx->device);
-    const size_t np = ps->n_paths;
-    std::vector<unsigned long long> h(4 * np + 2);
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), ps->d_acc.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t *const dst[4] = {sum_bases, sum_edges, top, top_alone};
-    for (int k = 0; k < 4; k++)
-        if (dst[k])
-            for (size_t p = 0; p < np; p++) dst[k][p] = h[k * np + p];
-    if (n_alignments) *n_alignments = h[4 * np];
-    if (n_unplaced) *n_unplaced = h[4 * np + 1];
-    return VGA_OK;
+    return ps->acc.read(ctx, dst, n_alignments, n_unplaced);
 }
 
 extern "C" int vga_path_support_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *bases, uint32_t *edges)
@@ -376,16 +393,9 @@ extern "C" int vga_path_support_last(vga_ctx *ctx, uint64_t n_reads, uint32_t *b
     if (!ctx) return VGA_ERR_ARG;
     ps_state *ps = ps_active(ctx);
     if (!ps) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_support_last: path support is off (vga_path_support_begin)");
-    if (!ps->have_last) return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_support_last: no vga_align_batch has been scored on this context yet");
-    if (n_reads != ps->last_reads)
-        return vga_set_error(ctx, VGA_ERR_ARG, "vga_path_support_last: the last vga_align_batch had %llu reads, not %llu", (unsigned long long)ps->last_reads,
-                             (unsigned long long)n_reads);
-    (void)hipSetDevice(ctx->device);
-    const size_t bytes = (size_t)n_reads * ps->n_paths * 4;
-    if (bases && bytes) VGA_HIP_CHECK(ctx, hipMemcpyAsync(bases, ps->d_bases.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (edges && bytes) VGA_HIP_CHECK(ctx, hipMemcpyAsync(edges, ps->d_edges.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VGA_OK;
+    uint32_t *const dst[2] = {bases, edges};
+    const uint32_t *const src[2] = {ps->d_bases.p, ps->d_edges.p};
+    return ps_read_last(ctx, "vga_path_support_last", ps->have_last, ps->last_reads, n_reads, ps->n_paths, dst, src);
 }
 
 // The kernel seam: explicit lists through k_ps_score.  Each list becomes what k_cov_runs would have written -- its node ids, then

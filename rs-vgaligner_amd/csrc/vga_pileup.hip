@@ -134,14 +134,7 @@ struct pu_state {
     oplist_call lists;  // of the vga_align_batch call in progress
 };
 
-pu_state *pu_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? (pu_state *)ctx->index.pu : nullptr; }
-
-static void pu_release(vga_ctx *ctx)
-{
-    if (ctx->index.pu && ctx->index.pu_free) ctx->index.pu_free(ctx->index.pu);
-    ctx->index.pu = nullptr;
-    ctx->index.pu_free = nullptr;
-}
+pu_state *pu_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.pu.get() : nullptr; }
 
 oplist_call &pu_lists(pu_state *pu) { return pu->lists; }
 
@@ -221,21 +214,14 @@ extern "C" int vga_pileup_begin(vga_ctx *ctx)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_pileup_begin: graph too large for 29-bit positions");
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
-    try {
-        if (!ctx->index.pu) {
-            ctx->index.pu = new pu_state();
-            ctx->index.pu_free = [](void *q) { delete (pu_state *)q; };
-        }
-    } catch (const std::bad_alloc &) {
-        return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_pileup_begin: out of host memory");
-    }
-    pu_state *pu = (pu_state *)ctx->index.pu;
+    if (!ctx->index.pu && !(ctx->index.pu = vga_make_owned<pu_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_pileup_begin: out of host memory");
+    pu_state *pu = ctx->index.pu.get();
     pu->seq_length = (uint32_t)ix.seq_length;
     hipError_t e = pu->d_mdiff.reserve((size_t)pu->seq_length + 1);
     if (e == hipSuccess) e = pu->d_counts.reserve((size_t)pu->seq_length * PU_COLS + 1);
     if (e == hipSuccess) e = pu->d_out.reserve((size_t)pu->seq_length * PU_COLS + 1);
     const int rc = e == hipSuccess ? pu_zero(ctx, pu) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_pileup_begin: %s", hipGetErrorString(e));
-    if (rc != VGA_OK) pu_release(ctx);
+    if (rc != VGA_OK) ctx->index.pu.reset();
     return rc;
 }
 
@@ -253,7 +239,7 @@ extern "C" int vga_pileup_end(vga_ctx *ctx)
     if (!ctx) return VGA_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    pu_release(ctx);
+    ctx->index.pu.reset();
     return VGA_OK;
 }
 

@@ -7,11 +7,8 @@
 
 poa_ws &poa_ws_of(vga_ctx *ctx)
 {
-    if (!ctx->poa_ws) {
-        ctx->poa_ws = new poa_ws();
-        ctx->poa_ws_free = [](void *q) { delete (poa_ws *)q; };
-    }
-    poa_ws &W = *(poa_ws *)ctx->poa_ws;
+    if (!ctx->poa_ws && !(ctx->poa_ws = vga_make_owned<poa_ws>())) throw std::bad_alloc();
+    poa_ws &W = *ctx->poa_ws;
     W.device = ctx->device;
     W.owner = ctx;
     return W;

@@ -581,11 +581,8 @@ int sg_prepare(vga_ctx *ctx, const sg_desc *descs, const uint64_t *q_src, const 
     if (n >= (1ull << 31)) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "too many chains in one call");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    if (!ctx->sg_ws) {
-        ctx->sg_ws = new sg_ws();
-        ctx->sg_ws_free = [](void *q) { delete (sg_ws *)q; };
-    }
-    sg_ws &W = *(sg_ws *)ctx->sg_ws;
+    if (!ctx->sg_ws && !(ctx->sg_ws = vga_make_owned<void, sg_ws>())) throw std::bad_alloc();
+    sg_ws &W = *(sg_ws *)ctx->sg_ws.get();
     if (!W.side) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -627,6 +624,6 @@ int sg_prepare_rest(vga_ctx *ctx, sg_store &store)
 {
     if (store.part[1].ready) return VGA_OK;
     (void)hipSetDevice(ctx->device);
-    sg_ws &W = *(sg_ws *)ctx->sg_ws;
+    sg_ws &W = *(sg_ws *)ctx->sg_ws.get();
     return sg_run_part(ctx, W, store, 1, store.split, store.n, W.side);
 }

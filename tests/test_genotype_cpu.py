@@ -73,6 +73,127 @@ def test_pair_index_header_with_a_host_compiler(tmp_path):
     assert subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout == "ok\n"
 
 
+# ---- the split of a call's reads over workgroups (vga_split_reads, shared by k_gt_pairs and k_gl_pairs)
+SPLIT_MAIN = """#include "vga_pair_index.hpp"
+#include <cstdio>
+#include <cstdlib>
+// argv: reads_per_chunk min_chunks max_group_reads, then n_reads n_tiles n_cu per case
+int main(int argc, char **argv)
+{
+    const uint32_t chunk = (uint32_t)strtoul(argv[1], 0, 10), min_chunks = (uint32_t)strtoul(argv[2], 0, 10), limit = (uint32_t)strtoul(argv[3], 0, 10);
+    for (int i = 4; i + 2 < argc; i += 3) {
+        const vga_read_split s = vga_split_reads((uint32_t)strtoul(argv[i], 0, 10), (uint32_t)strtoul(argv[i + 1], 0, 10), atoi(argv[i + 2]), chunk, min_chunks, limit);
+        printf("%u %u\\n", s.groups, s.reads_per_group);
+    }
+    return 0;
+}
+"""
+SPLIT_READS = [1, 31, 32, 33, 127, 128, 129, 2047, 2048, 2049, 65536]
+SPLIT_NO_LIMIT = 0xFFFFFFFF
+
+
+def gt_groups_of_the_parent(n_reads, n_tiles, n_cu):
+    b = pkg().binding
+    chunks = (n_reads + b.GENOTYPE_READS - 1) // b.GENOTYPE_READS
+    want = (4 * max(n_cu, 1) + n_tiles - 1) // n_tiles
+    most = max(1, chunks // b.GENOTYPE_MIN_CHUNKS)
+    groups = max(1, min(want, most, 65535))
+    per = (chunks + groups - 1) // groups
+    return (chunks + per - 1) // per, per * b.GENOTYPE_READS
+
+
+def gl_groups_of_the_parent(n_reads, n_tiles, n_cu):
+    b = pkg().binding
+    chunks = (n_reads + b.GENOTYPE_LIK_READS - 1) // b.GENOTYPE_LIK_READS
+    want = (4 * max(n_cu, 1) + n_tiles - 1) // n_tiles
+    most = max(1, chunks // b.GENOTYPE_LIK_MIN_CHUNKS)
+    groups = max(1, min(want, most, 65535))
+    per = min((chunks + groups - 1) // groups, b.GENOTYPE_LIK_MAX_GROUP_READS // b.GENOTYPE_LIK_READS)
+    return (chunks + per - 1) // per, per * b.GENOTYPE_LIK_READS
+
+
+def split_cases():
+    b = pkg().binding
+    shape = [(t, cu) for t in (1, 2, 3, 528, 2080) for cu in (0, 1, 256)]
+    gt = (b.GENOTYPE_READS, b.GENOTYPE_MIN_CHUNKS, SPLIT_NO_LIMIT, gt_groups_of_the_parent,
+          [(n, t, cu) for n in SPLIT_READS + [(1 << 31) - 1] for t, cu in shape])
+    gl = (b.GENOTYPE_LIK_READS, b.GENOTYPE_LIK_MIN_CHUNKS, b.GENOTYPE_LIK_MAX_GROUP_READS, gl_groups_of_the_parent,
+          [(n, t, cu) for n in SPLIT_READS + [65535 * b.GENOTYPE_LIK_MAX_GROUP_READS] for t, cu in shape])
+    return {"genotype": gt, "likelihood": gl}
+
+
+@pytest.mark.parametrize("flags", [["-O1"], ["-O1", "-g", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]],
+                         ids=["plain", "sanitized"])
+def test_split_rule_is_the_parent_s_two_rules(tmp_path, flags):
+    src = tmp_path / "split.cpp"
+    src.write_text(SPLIT_MAIN)
+    exe = str(tmp_path / "split")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + flags + ["-I", CSRC, str(src), "-o", exe])
+    for stage, (chunk, min_chunks, limit, parent, cases) in split_cases().items():
+        assert len(cases) == 12 * 5 * 3
+        pr = subprocess.run([exe, str(chunk), str(min_chunks), str(limit)] + [str(x) for c in cases for x in c], capture_output=True, text=True, timeout=60)
+        assert pr.returncode == 0 and not pr.stderr, pr.stderr
+        got = [tuple(int(x) for x in ln.split()) for ln in pr.stdout.splitlines()]
+        assert len(got) == len(cases)
+        for (n_reads, n_tiles, n_cu), (groups, per_group) in zip(cases, got):
+            what = (stage, n_reads, n_tiles, n_cu, groups, per_group)
+            assert (groups, per_group) == parent(n_reads, n_tiles, n_cu), what
+            assert 1 <= groups <= 65535, what
+            assert per_group % chunk == 0 and per_group > 0, what
+            assert limit == SPLIT_NO_LIMIT or per_group <= limit, what
+            assert groups * per_group >= n_reads, what
+            assert (groups - 1) * per_group < n_reads, what  # (no workgroup without a read)
+
+
+# ---- the owner of the states and workspaces (vga_owned, vga_common.hpp)
+OWNER_MAIN = """#include "vga_common.hpp"
+#include <type_traits>
+struct payload {
+    static int live, made;
+    int *p;
+    payload() : p(new int(7)) { live++; made++; }
+    ~payload() { delete p; live--; }
+};
+int payload::live = 0, payload::made = 0;
+int main()
+{
+    static_assert(!std::is_copy_constructible<vga_owned<payload>>::value && !std::is_copy_assignable<vga_owned<payload>>::value, "one owner");
+    {
+        vga_owned<payload> a{nullptr, nullptr};
+        if (a || a.get()) return 1;
+        a.reset();  // (empty: harmless)
+        a = vga_make_owned<payload>();
+        if (!a || *a->p != 7 || payload::live != 1) return 2;
+        a.reset();
+        if (a || payload::live != 0) return 3;
+        a.reset();  // (again)
+        a = vga_make_owned<payload>();
+        a = vga_make_owned<payload>();  // (reassignment releases the first)
+        if (payload::live != 1 || payload::made != 3) return 4;
+        vga_owned<void> v = vga_make_owned<void, payload>();  // (held without its type: the deleter knows it)
+        if (!v || payload::live != 2) return 5;
+        vga_owned<payload> b = std::move(a);
+        if (a || !b || payload::live != 2) return 6;
+    }  // (b and v are destroyed holding their payloads)
+    if (payload::live != 0 || payload::made != 4) return 7;
+    puts("ok");
+    return 0;
+}
+"""
+
+
+def test_owner_type_under_the_host_sanitizers(tmp_path):
+    """a stand-alone host program: no HIP call, no device code"""
+    src = tmp_path / "owner.hip"
+    src.write_text(OWNER_MAIN)
+    exe = str(tmp_path / "owner")
+    subprocess.check_call([HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+                           "-fno-sanitize-recover=all", "-I", CSRC, str(src), "-o", exe], stderr=subprocess.DEVNULL)
+    assert b"__asan_init" in open(exe, "rb").read()
+    pr = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert (pr.returncode, pr.stdout, pr.stderr) == (0, "ok\n", ""), (pr.returncode, pr.stderr)
+
+
 # ---- the reference on hand-made matrices
 def test_reference_on_hand_made_matrices():
     #         path 0  1  2

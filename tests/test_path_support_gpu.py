@@ -455,6 +455,78 @@ def test_life_cycle(oracle, drb1, monkeypatch):
         c.close()
 
 
+CHILDREN = {  # the stages that live in path support's state: how each begins, reads its table and says that it is off
+    "genotype": ("genotype_begin", "genotype", "vga_genotype_read: genotyping is off (vga_genotype_begin)"),
+    "likelihood": ("genotype_likelihood_begin", "genotype_likelihood", "vga_genotype_lik_read: the likelihood is off (vga_genotype_lik_begin)"),
+    "edit": ("path_edit_begin", "path_edit", "vga_path_edit_read: the edit distance is off (vga_path_edit_begin)"),
+}
+
+
+def same_table(got, want, what):
+    assert sorted(got) == sorted(want), what
+    for k in want:
+        assert np.array_equal(got[k], want[k]), (what, k)
+
+
+@pytest.fixture(scope="module")
+def children_case(drb1):
+    """six reads, and the table of path support and of each child when it alone is on"""
+    p = pkg()
+    seqs = [r.seq for r in p.readsim.simulate_reads(DRB1, 6, 2000, 0.03, 0.03, 0.04, seed=61)]
+    alone = {}
+    for name in [None] + list(CHILDREN):
+        c = p.Context(0)
+        try:
+            fresh(c, drb1, DRB1)
+            if name:
+                getattr(c, CHILDREN[name][0])()
+            score(c, seqs)
+            alone[name or "support"] = getattr(c, CHILDREN[name][1])() if name else c.path_support()
+        finally:
+            c.close()
+    assert alone["support"]["n_alignments"] == len(seqs) and alone["genotype"]["sum_bases"].any() and alone["likelihood"]["n_scored"] == len(seqs)
+    assert alone["edit"]["n_alignments"] == len(seqs) and alone["edit"]["n_scored"].any()
+    return seqs, alone
+
+
+@pytest.mark.parametrize("ending", ["path_support_end", "new index", "close"])
+def test_children_end_with_path_support(drb1, children_case, ending):
+    """genotyping, the likelihood and the edit distance all on over one path support: each table is what the stage gives alone, and
+    the three end with path support, with its index, and with the context"""
+    p = pkg()
+    seqs, alone = children_case
+    c = p.Context(0)
+    try:
+        fresh(c, drb1, DRB1)
+        for begin, _, _ in CHILDREN.values():
+            getattr(c, begin)()
+        score(c, seqs)
+        names = [t["name"] for t in c.kernel_times()]
+        assert all(k in names for k in ("k_ps_score", "k_gt_pairs", "k_gl_pairs", "k_pe_rows")), names
+        same_table(c.path_support(), alone["support"], "path support beside its three children")
+        for name, (_, read, _) in CHILDREN.items():
+            same_table(getattr(c, read)(), alone[name], name + " beside the others")
+        if ending == "close":
+            c.close()  # (everything still on)
+            return
+        if ending == "path_support_end":
+            c.path_support_end()
+        else:
+            upload_oracle_index(c, drb1)
+        for name, (_, read, off) in CHILDREN.items():
+            with pytest.raises(p.VgaError) as e:
+                getattr(c, read)()
+            assert e.value.code == -1 and off in str(e.value), (name, str(e.value))
+        with pytest.raises(p.VgaError) as e:
+            c.path_support()
+        assert e.value.code == -1
+        score(c, seqs)
+        names = [t["name"] for t in c.kernel_times()]
+        assert names and not any(n.startswith(("k_ps", "k_gt", "k_gl", "k_pe")) for n in names), names
+    finally:
+        c.close()
+
+
 # =====================================================================================================================
 # 4. the executable
 # =====================================================================================================================
