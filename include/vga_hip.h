@@ -545,7 +545,7 @@ int vga_genotype_lik_source(vga_ctx *ctx, uint32_t source);
  * 0 none, 1 het, 2 hom), qual, ins_qual, depth and -- what a caller needs to print a site without fetching the table -- counts,
  * the base's seven counters widened to 64 bits (cap x 7, row-major; may be NULL).  The first min(n_calls, cap) are written,
  * *n_calls is the total and *n_tested the tested bases (either may be NULL); the arrays may be NULL when cap is 0.  A counter of
- * 2^32 - 1 is an ordinary value.  The inserted letters are not called, the sites are independent, and a base on one arm of a
+ * 2^32 - 1 is an ordinary value.  The inserted letters are not called here (the insertion call below), the sites are independent, and a base on one arm of a
  * bubble sees only the reads that went through that arm.
  *   vga_variant_call        from the context's own counters, after the prefix pass vga_pileup_read does too.  Needs
  *                           vga_pileup_begin (VGA_ERR_ARG otherwise, and for E or min_depth out of range or a NULL array with
@@ -561,6 +561,54 @@ int vga_variant_call(vga_ctx *ctx, uint32_t E, uint64_t min_depth, uint64_t min_
 int vga_variant_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *counts_in /* n * 7 */, const char *letters /* n */, uint32_t E,
                            uint64_t min_depth, uint64_t min_qual, uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual,
                            uint64_t *ins_qual, uint64_t *depth, uint64_t *counts /* cap * 7 */, uint64_t *n_tested, uint64_t *n_calls);
+
+/* ---- insertion call: what the reads insert behind a graph base ----------
+ * Stands in for nothing in the reference.  The pileup says that reads insert behind a base and the variant call reports the base
+ * as ins = het or hom; this table keeps the letters.  It is defined on the alignments GAF text alone (tests/insertion_ref.py
+ * recomputes it).  Along the record reported for a read, walked exactly as the pileup walks it, a cs token "+q.." of L letters
+ * belongs to the graph base consumed most recently before it, covered or deleted; one before the first consumed base belongs to
+ * no base, adds one to n_leading and touches no counter.  Per graph base 49 counters, row-major:
+ *   len[1] .. len[8], len_more   (columns 0 .. 8)   the insertions at this base of exactly l letters, and of more than 8;
+ *   let[j][A C G T N], j = 0..7  (column 9 + 5 j + c) the insertions at this base of more than j letters whose j-th letter is
+ *                                that one: lower case equals upper case, anything but a c g t is N; an insertion of more than 8
+ *                                letters adds its first 8.
+ * So len[1] + .. + len[8] + len_more at a base is the pileup's ins there, the five let[j][.] add up to the insertions longer than
+ * j, and n_leading is the pileup's leading_ins.  With VGA_STRANDS_BOTH the letters are on the graph's forward strand.  The
+ * counters are 32-bit, exact and independent of the order of the additions; they belong to the context's index: uploading or
+ * building another index drops them and turns counting off.  The 8 is a choice, not a measurement.
+ *   the call   for one row, integer-only and without parameters: length = the bin with the most reads among 1 .. 8, more (the
+ *              shorter on a tie, more being the longest; reported as 9 for more; 0 for a row whose bins are all zero),
+ *              length_reads that bin's count; for j < min(length, 8) seq[j] = the letter with the largest let[j][.] (A < C < G < T
+ *              < N on a tie) and seq_reads[j] its count; seq[j] = 0 and seq_reads[j] = 0 behind them.  The letter counts at j mix
+ *              the insertions of every length above j, two insertions of one length at a site are not told apart
+ *              (seq_reads below length_reads is the sign), and an insertion of more than 8 letters is cut to its first 8.
+ *   vga_insertion_begin       needs an index (VGA_ERR_NO_INDEX); VGA_ERR_UNSUPPORTED for a graph of 2^26 bases or more (a
+ *                             position shares a word with the bin, and the table is indexed in 32 bits); allocates and zeroes
+ *                             seq_length x 49 counters; every later vga_align_batch on ctx adds its reported alignments.
+ *                             VGA_SUBGRAPH=host is refused by vga_align_batch while counting is on.
+ *   vga_insertion_read        counts: seq_length x 49; n_events: the insertions counted; any pointer may be NULL; does not reset.
+ *                             VGA_ERR_ARG without _begin; VGA_ERR_UNSUPPORTED once n_alignments has reached 2^32 - 1.
+ *   vga_insertion_reset       zero, keep counting (VGA_ERR_ARG without _begin).
+ *   vga_insertion_end         free, stop counting.
+ *   vga_insertion_call        the call at the n bases pos[0 .. n) from the context's own counters: the rows are gathered on the
+ *                             device, the table stays there.  length: n; length_reads: n; seq: n x 8 (letters A C G T N, or 0);
+ *                             seq_reads: n x 8; rows: n x 49, the counters widened to 64 bits (may be NULL).  VGA_ERR_ARG without
+ *                             _begin, for a pos >= seq_length and for a NULL array with n > 0.  Does not reset.  n = 0 is
+ *                             accepted.
+ *   vga_insertion_call_table  the kernel seam, and the route of several contexts whose tables were added in 64 bits: explicit
+ *                             rows (rows_in: n x 49) through the same kernel.  Needs a context only: no index, no counters
+ *                             touched.  VGA_ERR_UNSUPPORTED for a counter of 2^40 or more (found on the device).
+ * With counting off vga_align_batch does what it did before these calls existed: no extra launch, no extra allocation. */
+int vga_insertion_begin(vga_ctx *ctx);
+int vga_insertion_read(vga_ctx *ctx, uint32_t *counts /* seq_length * 49 */, uint64_t *n_alignments, uint64_t *n_events,
+                       uint64_t *n_leading);
+int vga_insertion_reset(vga_ctx *ctx);
+int vga_insertion_end(vga_ctx *ctx);
+int vga_insertion_call(vga_ctx *ctx, uint64_t n, const uint32_t *pos /* n */, uint8_t *length /* n */, uint64_t *length_reads /* n */,
+                       uint8_t *seq /* n * 8 */, uint64_t *seq_reads /* n * 8 */, uint64_t *rows /* n * 49 */);
+int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *rows_in /* n * 49 */, uint8_t *length /* n */,
+                             uint64_t *length_reads /* n */, uint8_t *seq /* n * 8 */, uint64_t *seq_reads /* n * 8 */,
+                             uint64_t *rows /* n * 49 */);
 
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.

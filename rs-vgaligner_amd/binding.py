@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "vga_genotype_lik_pairs", "vga_genotype_lik_source",
     "vga_path_edit_begin", "vga_path_edit_read", "vga_path_edit_last", "vga_path_edit_reset", "vga_path_edit_end", "vga_path_edit_pairs",
     "vga_variant_call", "vga_variant_call_table",
+    "vga_insertion_begin", "vga_insertion_read", "vga_insertion_reset", "vga_insertion_end", "vga_insertion_call", "vga_insertion_call_table",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -88,6 +89,15 @@ VARIANT_MIN_DEPTH = 4
 VARIANT_MIN_QUAL = 512
 VARIANT_ALLELES = "ACGT-"  # alleles 0..4 as <out>-variants.tsv writes them: D, the deleted base, is '-'
 VARIANT_INS_STATES = (".", "het", "hom")
+
+# the insertion table (csrc/vga_insertion.hpp): the letters of an inserted run that are kept, and the 32-bit counters of a graph
+# base -- the bins of length 1 .. 8 and `more`, then per kept position the letters A C G T N; the graph and the counters that
+# vga_insertion_begin and vga_insertion_call_table serve
+INSERTION_MAX_LEN = 8
+INSERTION_COLS = 9 + INSERTION_MAX_LEN * 5
+INSERTION_LETTERS = "ACGTN"
+INSERTION_MAX_SEQ = 1 << 26
+INSERTION_MAX_COUNT = 1 << 40
 
 
 class VgaError(RuntimeError):
@@ -275,6 +285,17 @@ def load_library():
         L.vga_variant_call.argtypes = [vp, C.c_uint32, u64, u64] + outs
         L.vga_variant_call_table.argtypes = [vp, u64, u64p, C.c_char_p, C.c_uint32, u64, u64] + outs
         L.vga_variant_call.restype = L.vga_variant_call_table.restype = C.c_int
+    if hasattr(L, "vga_insertion_begin"):  # (absent from an older build named by VGA_LIB; the Context.insertion* calls then fail)
+        u64p, u32p, u8p, u64 = _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint8), C.c_uint64
+        for name in ("vga_insertion_begin", "vga_insertion_reset", "vga_insertion_end"):
+            getattr(L, name).argtypes = [vp]
+        L.vga_insertion_read.argtypes = [vp, u32p, u64p, u64p, u64p]
+        outs = [u8p, u64p, u8p, u64p, u64p]
+        L.vga_insertion_call.argtypes = [vp, u64, u32p] + outs
+        L.vga_insertion_call_table.argtypes = [vp, u64, u64p] + outs
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_insertion_"):
+                getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -775,6 +796,52 @@ class Context:
             raise ValueError(f"{len(tab)} rows and {len(let)} letters")
         return self._variant(lambda c, *outs: self.L.vga_variant_call_table(self.h, len(tab), _u64p(tab), let, int(error), int(min_depth), int(min_qual),
                                                                            c, *outs), cap)
+
+    def insertion_begin(self) -> None:
+        """vga_insertion_begin: from now on every align() of this context adds the insertions of its reported alignments to the
+        table of inserted lengths and letters"""
+        self._check(self.L.vga_insertion_begin(self.h))
+
+    def insertions(self):
+        """vga_insertion_read -> (counts[seq_length, INSERTION_COLS] uint32: per base the bins of length 1 .. 8 and more, then the
+        letters A C G T N of each of the first 8 positions; n_alignments, n_events, n_leading); does not reset"""
+        sl = self._dims[0] if self._dims else 0
+        counts = np.zeros((max(1, sl), INSERTION_COLS), dtype=np.uint32)
+        n, ev, lead = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_insertion_read(self.h, _u32p(counts), C.byref(n), C.byref(ev), C.byref(lead)))
+        return counts[:sl], int(n.value), int(ev.value), int(lead.value)
+
+    def insertion_reset(self) -> None:
+        """vga_insertion_reset: zero the table, keep counting"""
+        self._check(self.L.vga_insertion_reset(self.h))
+
+    def insertion_end(self) -> None:
+        """vga_insertion_end: free the table, stop counting"""
+        self._check(self.L.vga_insertion_end(self.h))
+
+    def _insertion(self, call, n) -> dict:
+        """`call(*outs)` is one of the two C calls with everything before the outputs bound"""
+        m = max(1, n)
+        length, seq = np.zeros(m, dtype=np.uint8), np.zeros((m, INSERTION_MAX_LEN), dtype=np.uint8)
+        lr, sr = np.zeros(m, dtype=np.uint64), np.zeros((m, INSERTION_MAX_LEN), dtype=np.uint64)
+        rows = np.zeros((m, INSERTION_COLS), dtype=np.uint64)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        self._check(call(u8(length), _u64p(lr), u8(seq), _u64p(sr), _u64p(rows)))
+        return {"length": length[:n], "length_reads": lr[:n], "seq": seq[:n], "seq_reads": sr[:n], "rows": rows[:n]}
+
+    def insertion_call(self, pos) -> dict:
+        """vga_insertion_call: length and letters of the insertion behind each of the graph bases `pos`, from this context's own
+        counters (needs insertion_begin; does not reset) -> {length (0: none, 1 .. 8, 9: more than 8), length_reads, seq[n, 8]
+        (the bytes of A C G T N, 0 behind the last), seq_reads[n, 8], rows[n, INSERTION_COLS]: the sites' counters}"""
+        at = np.ascontiguousarray(pos, dtype=np.uint32).reshape(-1)
+        return self._insertion(lambda *outs: self.L.vga_insertion_call(self.h, len(at), _u32p(at if len(at) else np.zeros(1, dtype=np.uint32)), *outs), len(at))
+
+    def insertion_call_table(self, rows) -> dict:
+        """vga_insertion_call_table, the kernel seam: the same call from explicit rows[n, INSERTION_COLS] (uint64).  Needs a
+        context only."""
+        tab = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, INSERTION_COLS)
+        return self._insertion(lambda *outs: self.L.vga_insertion_call_table(self.h, len(tab), _u64p(tab if len(tab) else np.zeros((1, INSERTION_COLS), dtype=np.uint64)),
+                                                                             *outs), len(tab))
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

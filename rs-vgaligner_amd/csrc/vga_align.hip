@@ -17,6 +17,7 @@
 #include "vga_path_edit.hpp"
 #include "vga_path_support.hpp"
 #include "vga_pileup.hpp"
+#include "vga_insertion.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_subgraph_host.hpp"
 
@@ -52,6 +53,7 @@ struct align_call {
     cov_state *const cov;
     ps_state *const ps;
     pu_state *const pu;      // the pileup is counted: event lists of its own
+    ia_state *const ia;      // the inserted letters are counted: event lists of their own
     // ---- plan (vga_align_plan.hpp); the per-problem arrays are in launch order on the device route, in list order on the host's
     std::vector<uint64_t> prob_read, prob_chain, read_prob0;
     std::vector<uint32_t> slot_of;  // where the q-th (read, chain) pair of the selection sits among the problems
@@ -76,7 +78,7 @@ struct align_call {
 
     align_call(vga_batch *batch, const vga_map_result *chains, uint32_t best_n, const vga_poa_params *p)
         : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), lists(cov_lists_active(batch->ctx)), cov(cov_active(batch->ctx)),
-          ps(ps_active(batch->ctx)), pu(pu_active(batch->ctx)) {}
+          ps(ps_active(batch->ctx)), pu(pu_active(batch->ctx)), ia(ia_active(batch->ctx)) {}
 
     uint32_t qlen(uint64_t r) const { return (uint32_t)(b->read_off[r + 1] - b->read_off[r]); }
     // VGA_STRANDS_BOTH: a read whose chains came from its reverse complement is aligned as that sequence
@@ -118,7 +120,7 @@ int align_call::reverse_complements()
 int align_call::plan()
 {
     // the list makers read the subgraph store's handles on the device
-    const char *refused = on_device ? nullptr : cov ? "read coverage is not counted" : ps ? "path support is not scored" : pu ? "the pileup is not counted" : nullptr;
+    const char *refused = on_device ? nullptr : cov ? "read coverage is not counted" : ps ? "path support is not scored" : pu ? "the pileup is not counted" : ia ? "the inserted letters are not counted" : nullptr;
     if (refused)
         return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_align_batch: %s under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)", refused);
     align_select(m, align_best_n, prob_read, prob_chain, read_prob0);
@@ -270,7 +272,7 @@ void align_call::pick_winners()
     });
 }
 
-// coverage, path support and the pileup count the reported record of every read and nothing else
+// coverage, path support, the pileup and the insertion table count the reported record of every read and nothing else
 int align_call::count_winners()
 {
     std::vector<uint32_t> winners, reads;
@@ -295,6 +297,10 @@ int align_call::count_winners()
     if (pu) {  // from lists of its own
         if ((rc = pu_add_winners(ctx, pu, winners)) != VGA_OK) return rc;
         tr.mark("pileup");
+    }
+    if (ia) {
+        if ((rc = ia_add_winners(ctx, ia, winners)) != VGA_OK) return rc;
+        tr.mark("insertions");
     }
     return VGA_OK;
 }
@@ -382,7 +388,7 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     if ((rc = c.run_poa()) != VGA_OK) return rc;
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     c.pick_winners();
-    if ((c.lists || c.pu) && (rc = c.count_winners()) != VGA_OK) return rc;
+    if ((c.lists || c.pu || c.ia) && (rc = c.count_winners()) != VGA_OK) return rc;
     if ((rc = c.fill_result()) != VGA_OK) return rc;
     *out = c.res.release();
     return VGA_OK;

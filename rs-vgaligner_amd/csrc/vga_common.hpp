@@ -37,6 +37,7 @@ vga_owned<T> vga_make_owned()
 struct cov_state;
 struct ps_state;
 struct pu_state;
+struct ia_state;
 struct poa_ws;
 
 struct vga_dev_index {
@@ -80,6 +81,9 @@ struct vga_dev_index {
     vga_owned<ps_state> ps{nullptr, nullptr};
     // the pileup table of this index while it is counted (vga_pileup.hip), with event lists of its own: released with the index
     vga_owned<pu_state> pu{nullptr, nullptr};
+    // the table of inserted lengths and letters of this index while it is counted (vga_insertion.hip), with event lists of its own:
+    // released with the index
+    vga_owned<ia_state> ia{nullptr, nullptr};
 };
 
 struct vga_timer_entry {

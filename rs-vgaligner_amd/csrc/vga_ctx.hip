@@ -158,6 +158,7 @@ void vga_index_release(vga_dev_index &ix)
     ix.cov.reset();  // (counting stops with the index it counted on)
     ix.ps.reset();   // (and so does path support)
     ix.pu.reset();   // (and the pileup)
+    ix.ia.reset();   // (and the insertion table)
     ix = vga_dev_index();
 }
 

@@ -1,10 +1,10 @@
-// vga_oplist.hpp -- what the two list makers share: coverage's k_cov_runs (vga_coverage.hip) and the pileup's k_pu_events
-// (vga_pileup.hip) condense the traceback of every finished problem into a short list, and the winners' lists are counted once the
+// vga_oplist.hpp -- what the three list makers share: coverage's k_cov_runs (vga_coverage.hip), the pileup's k_pu_events
+// (vga_pileup.hip) and the insertion table's k_ia_events (vga_insertion.hip) condense the traceback of every finished problem into a short list, and the winners' lists are counted once the
 // host has picked them.  Here is the one copy of the walk over the operations (device, and host for a list that found no room), of
 // the record of a list and of the per-call store of lists.  Each maker keeps what is its own: what counts as "in a run", what else
 // it lists, and its counters.
 //
-// There is a third reader of the same operation stream: k_poa_text (vga_poa_text.hpp, compiled into vga_poa.hip).  It is on the
+// There is a fourth reader of the same operation stream: k_poa_text (vga_poa_text.hpp, compiled into vga_poa.hip).  It is on the
 // path of every alignment, carries other state from block to block (the text's run lengths) and keeps its own copy of the
 // prologue, of node_of and of "a row opens a node when npred != 0".  Whoever changes the meaning of an operation, of a row record
 // or of the node table changes it there too.
@@ -16,12 +16,12 @@
 #include "vga_poa_launch.hpp"
 #include "vga_subgraph.hpp"
 
-// one problem's list: n_a words of the first kind, then n_b words of the second, at word `off` of its buffer (vga_coverage.hpp and
-// vga_pileup.hpp say what the kinds are)
+// one problem's list: n_a words of the first kind, then n_b words of the second, at word `off` of its buffer (vga_coverage.hpp,
+// vga_pileup.hpp and vga_insertion.hpp say what the kinds are)
 struct oplist_rec {
     uint32_t off, n_a, n_b;
     uint32_t flags;  // low two bits: 0 nothing (the problem has no alignment yet), 1 in the call's device buffer, 2 no room there,
-                     // 3 built by the host; bit 2 (pileup only): the alignment starts with an insertion (it belongs to no base)
+                     // 3 built by the host; bit 2 (pileup and insertion table): the alignment starts with an insertion (it belongs to no base)
 };
 #define PU_LEADING 4u
 
@@ -223,7 +223,7 @@ struct oplist_call {
     // start of a poa_run call of n problems whose queries hold total_q bases: the buffer of lists is sized (cap_words caps it when
     // has_cap) and its cursor zeroed.  About a word per read base is what coverage needs on a graph of short nodes with reads of
     // 10 % errors, the pileup 0.4.  Not a bound -- a problem that finds no room says so and the host builds its list
-    // (VGA_COV_LIST_WORDS and VGA_PILEUP_LIST_WORDS cap the buffers: the tests force that route with them)
+    // (VGA_COV_LIST_WORDS, VGA_PILEUP_LIST_WORDS and VGA_INS_LIST_WORDS cap the buffers: the tests force that route with them)
     int begin(vga_ctx *ctx, uint64_t n, uint64_t total_q, bool has_cap, uint64_t cap_words)
     {
         uint64_t words = std::min<uint64_t>(total_q + 256ull * n + 4096ull, 0xFFFFFF00ull);

@@ -5,6 +5,7 @@
 #include "vga_common.hpp"
 #include "vga_coverage.hpp"
 #include "vga_pileup.hpp"
+#include "vga_insertion.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_poa_pool.hpp"
 
@@ -271,11 +272,12 @@ struct poa_call {
     poa_ws &W;
     poa_pool pool;
     // A list maker that is on while the graphs are in the device store (vga_oplist.hpp): its kernel runs behind k_poa_text.
-    // Coverage's k_cov_runs while coverage or path support is on (cov_lists_active), the pileup's k_pu_events while it is counted
+    // Coverage's k_cov_runs while coverage or path support is on (cov_lists_active), the pileup's k_pu_events and the insertion
+    // table's k_ia_events while they are counted
     struct list_maker {
         oplist_call *lists;
         const char *what;  // as the trace calls its list
-        bool has_cap;      // VGA_COV_LIST_WORDS / VGA_PILEUP_LIST_WORDS
+        bool has_cap;      // VGA_COV_LIST_WORDS / VGA_PILEUP_LIST_WORDS / VGA_INS_LIST_WORDS
         uint64_t cap_words;
         decltype(&cov_enqueue_runs) enqueue;
         decltype(&cov_keep_from_ops) keep_from_ops;
@@ -325,6 +327,7 @@ struct poa_call {
         if (!f.dev) return;
         if (cov_state *cv = cov_lists_active(c)) makers.push_back({&cov_lists(cv), "run list", sw.has_cov_words, sw.cov_words, cov_enqueue_runs, cov_keep_from_ops});
         if (pu_state *pu = pu_active(c)) makers.push_back({&pu_lists(pu), "pileup list", sw.has_pileup_words, sw.pileup_words, pu_enqueue_events, pu_keep_from_ops});
+        if (ia_state *ia = ia_active(c)) makers.push_back({&ia_lists(ia), "insertion list", sw.has_ins_words, sw.ins_words, ia_enqueue_events, ia_keep_from_ops});
     }
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }

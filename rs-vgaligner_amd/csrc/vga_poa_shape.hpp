@@ -78,9 +78,10 @@ struct poa_switches {
     bool text_memcpy = false; // VGA_POA_TEXT_MEMCPY: the device text comes back by hipMemcpy, not by the copy kernel
     bool has_text_arena = false;
     uint64_t text_arena = 0;  // VGA_POA_TEXT_ARENA: caps the text arena (the overflow path)
-    bool has_cov_words = false, has_pileup_words = false;
+    bool has_cov_words = false, has_pileup_words = false, has_ins_words = false;
     uint64_t cov_words = 0;     // VGA_COV_LIST_WORDS: caps the buffer of run lists (the no-room route; 0: every problem takes it)
     uint64_t pileup_words = 0;  // VGA_PILEUP_LIST_WORDS: the same for the pileup lists
+    uint64_t ins_words = 0;     // VGA_INS_LIST_WORDS: the same for the insertion lists
     bool has_dump_rows = false;
     std::string dump_rows;    // VGA_POA_DUMP_ROWS: file for the row records of every launch's first problem
     bool has_pool_fraction = false, has_pool_bytes = false, has_pool_seg = false;
@@ -123,6 +124,7 @@ static inline poa_switches poa_read_switches()
     u64("VGA_POA_TEXT_ARENA", s.has_text_arena, s.text_arena);
     if (const char *e = getenv("VGA_COV_LIST_WORDS")) { s.has_cov_words = true; s.cov_words = (uint64_t)std::max(0ll, atoll(e)); }
     u64("VGA_PILEUP_LIST_WORDS", s.has_pileup_words, s.pileup_words);
+    u64("VGA_INS_LIST_WORDS", s.has_ins_words, s.ins_words);
     if (const char *e = getenv("VGA_POA_DUMP_ROWS")) { s.has_dump_rows = true; s.dump_rows = e; }
     if (const char *e = getenv("VGA_POOL_FRACTION")) { s.has_pool_fraction = true; s.pool_fraction = atof(e); }
     u64("VGA_POOL_BYTES", s.has_pool_bytes, s.pool_bytes);

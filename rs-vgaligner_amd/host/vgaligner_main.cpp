@@ -63,7 +63,10 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // neither allele explains in 1/256 bit (1280, 257..8192); --call-min-depth N: the depth from which a base is
                           // tested (4, at least 1); --call-min-qual N: the margin from which a call is reported (512)
                           {"", "--call-variants", false, "call-variants"}, {"", "--call-error", true, "call-error"},
-                          {"", "--call-min-depth", true, "call-min-depth"}, {"", "--call-min-qual", true, "call-min-qual"}};
+                          {"", "--call-min-depth", true, "call-min-depth"}, {"", "--call-min-qual", true, "call-min-qual"},
+                          // not in the reference: length and letters of what the reads insert at the sites --call-variants reports
+                          // with an insertion, counted and called on the GPU (one TSV file)
+                          {"", "--call-insertions", false, "call-insertions"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -204,6 +207,9 @@ int map_main(int argc, char **argv)
     o.call_error = (uint32_t)call_error;
     call_value("call-min-depth", 1, UINT64_MAX, o.call_min_depth);
     call_value("call-min-qual", 0, UINT64_MAX, o.call_min_qual);
+    o.call_insertions = m.count("call-insertions") > 0;
+    if (o.call_insertions && !o.also_align) throw Error("--call-insertions calls from alignments: it needs --also-align");
+    if (o.call_insertions && !o.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -280,6 +286,8 @@ int map_main(int argc, char **argv)
                 (unsigned long long)out.n_leading_ins);
     if (o.call_variants)
         fprintf(stderr, "[vgaligner] call-variants: %llu bases tested, %llu calls\n", (unsigned long long)out.n_variant_tested, (unsigned long long)out.n_variant_calls);
+    if (o.call_insertions)
+        fprintf(stderr, "[vgaligner] call-insertions: %llu sites, %llu longer than 8\n", (unsigned long long)out.n_insertion_sites, (unsigned long long)out.n_insertion_long);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -325,7 +333,7 @@ int main(int argc, char **argv)
                         "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]\n"
                         "                                       [--genotype-from support|edit]]\n"
                         "                [--path-edit]\n"
-                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512]]\n");
+                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -198,6 +198,12 @@ struct MapOptions {
     bool call_variants = false;
     uint32_t call_error = 1280;
     uint64_t call_min_depth = 4, call_min_qual = 512;
+    // --call-insertions (not in the reference; needs call_variants): count, on the GPU, the lengths and the first eight letters of
+    // what the reads insert behind every graph base (vga_insertion_begin), call length and letters at exactly the sites of
+    // <out>-variants.tsv whose insertion state is het or hom, in that order (vga_insertion_call; several contexts: each hands its
+    // whole table over, 196 bytes per base and context over PCIe, they are added in 64 bits, then vga_insertion_call_table on the
+    // first with the summed rows of the sites), and write <out>-insertions.tsv
+    bool call_insertions = false;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -214,6 +220,7 @@ struct MapOutput {
     uint64_t n_chunks = 0, n_devices = 0;
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
+    uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)
     uint64_t n_path_scored = 0, n_path_unplaced = 0;  // alignments scored against the paths, and those no path supports (MapOptions::path_support)

@@ -1,6 +1,7 @@
 // vgh_tables.cpp -- the analysis tables of map_reads / map_reads_multi (vgh_tables.hpp): reading them from a context, adding them
 // over the contexts, the two rankings and the TSV files.  Nothing of this is in the reference.
 #include "vgh_tables.hpp"
+#include "../csrc/vga_insertion.hpp"
 #include "../csrc/vga_pair_index.hpp"
 
 #include <algorithm>
@@ -122,6 +123,34 @@ void variant_write(const Index &ix, const VariantCalls &v, const std::string &ou
     write_file(out_prefix + "-variants.tsv", t);
 }
 
+// one line per called site: where it is and what the variant call says of it, then length (1 .. 8, or >8), the reads of that
+// length, the letters and the reads of each
+void insertion_write(const Index &ix, const VariantCalls &v, const InsertionCalls &c, MapOutput &out, const std::string &out_prefix)
+{
+    static const char *const STATES[] = {".", "het", "hom"};
+    std::string t = "node\toffset\tstate\tins_qual\tdepth\tins_count\tlength\tlength_reads\tseq\tseq_reads\n";
+    uint64_t id = 1;  // the sites come in base order: the node moves forward only
+    out.n_insertion_sites = c.site.size();
+    out.n_insertion_long = 0;
+    for (size_t s = 0; s < c.site.size(); s++) {
+        const uint64_t j = c.site[s], p = v.pos[j];
+        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= p) id++;
+        const uint32_t len = c.length[s], kept = std::min<uint32_t>(len, IA_MAX_LEN);
+        out.n_insertion_long += len > IA_MAX_LEN ? 1u : 0u;
+        put_u64(t, id); t += '\t'; put_u64(t, p - ix.node_ref[id - 1].seq_idx); t += '\t'; t += STATES[(v.gt[j] >> 6) < 3u ? (v.gt[j] >> 6) : 0u]; t += '\t';
+        put_u64(t, v.ins_qual[j]); t += '\t'; put_u64(t, v.depth[j]); t += '\t'; put_u64(t, v.counts[j * 7 + 6]); t += '\t';
+        if (len > IA_MAX_LEN) t += ">8"; else put_u64(t, len);
+        t += '\t'; put_u64(t, c.length_reads[s]); t += '\t';
+        for (uint32_t k = 0; k < kept; k++) t += (char)c.seq[s * IA_MAX_LEN + k];
+        if (!kept) t += '.';
+        t += '\t';
+        for (uint32_t k = 0; k < kept; k++) { if (k) t += ','; put_u64(t, c.seq_reads[s * IA_MAX_LEN + k]); }
+        if (!kept) t += '.';
+        t += '\n';
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-insertions.tsv", t);
+}
+
 void path_support_write(const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
 {
     const size_t np = opt.paths.n_paths();
@@ -239,6 +268,7 @@ void check_aligner(const MapOptions &opt)
     if (opt.pileup && !opt.also_align) throw Error("--pileup counts alignments: it needs --also-align");
     if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
     if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
+    if (opt.call_insertions && !opt.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -259,6 +289,7 @@ void Tables::begin(vga_ctx *ctx) const
         if (opt_.genotype_likelihood && opt_.genotype_from_edit) check(ctx, vga_genotype_lik_source(ctx, VGA_GL_FROM_EDIT));
     }
     if (piling()) check(ctx, vga_pileup_begin(ctx));
+    if (inserting()) check(ctx, vga_insertion_begin(ctx));
 }
 
 void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const
@@ -336,6 +367,17 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         variant_fetch(ctx, variants_, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
             return vga_variant_call(ctx, opt_.call_error, opt_.call_min_depth, opt_.call_min_qual, cap, pos, gt, qual, iq, depth, counts, nt, nc);
         });
+    if (inserting() && call_now) {  // the sites of the calls just made, from the context's own counters
+        const std::vector<uint32_t> pos = insertion_sites();
+        InsertionCalls &c = ins_calls_;
+        check(ctx, vga_insertion_call(ctx, pos.size(), pos.data(), c.length.data(), c.length_reads.data(), c.seq.data(), c.seq_reads.data(), nullptr));
+    } else if (inserting()) {  // the whole table for the sum: 196 bytes per base
+        Counters t;
+        std::vector<uint32_t> c(ix_.seq_length * IA_COLS + 1);
+        check(ctx, vga_insertion_read(ctx, c.data(), &t.n[0], nullptr, &t.n[1]));
+        t.v = {widen(c, ix_.seq_length * IA_COLS)};
+        insertions_.add(t);
+    }
     if (piling() && getenv("VGA_TRACE"))
         fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
                 std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -347,6 +389,7 @@ void Tables::end(vga_ctx *ctx) const
     if (coverage()) (void)vga_coverage_end(ctx);
     if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
     if (piling()) (void)vga_pileup_end(ctx);
+    if (inserting()) (void)vga_insertion_end(ctx);
 }
 
 void Tables::add(const Tables &o)
@@ -357,6 +400,20 @@ void Tables::add(const Tables &o)
     costs_.add(o.costs_);
     edit_.add(o.edit_);
     pileup_.add(o.pileup_);
+    insertions_.add(o.insertions_);
+}
+
+std::vector<uint32_t> Tables::insertion_sites()
+{
+    std::vector<uint32_t> pos;
+    InsertionCalls &c = ins_calls_;
+    c.site.clear();
+    for (uint64_t j = 0; j < variants_.n_calls; j++)
+        if ((variants_.gt[j] >> 6) == 1u || (variants_.gt[j] >> 6) == 2u) { c.site.push_back(j); pos.push_back(variants_.pos[j]); }
+    const size_t n = pos.size();
+    c.length.assign(n + 1, 0); c.length_reads.assign(n + 1, 0); c.seq.assign((n + 1) * IA_MAX_LEN, 0); c.seq_reads.assign((n + 1) * IA_MAX_LEN, 0);
+    pos.reserve(n + 1);
+    return pos;
 }
 
 void Tables::call(vga_ctx *ctx)
@@ -367,6 +424,15 @@ void Tables::call(vga_ctx *ctx)
                                       pos, gt, qual, iq, depth, counts, nt, nc);
     });
     trace_mark("variants called");
+    if (!inserting()) return;
+    insertions_.pad({ix_.seq_length * IA_COLS});
+    const std::vector<uint32_t> pos = insertion_sites();
+    std::vector<uint64_t> rows(pos.size() * IA_COLS + 1);
+    for (size_t s = 0; s < pos.size(); s++)
+        std::copy_n(insertions_.v[0].begin() + (long)((uint64_t)pos[s] * IA_COLS), IA_COLS, rows.begin() + (long)(s * IA_COLS));
+    InsertionCalls &c = ins_calls_;
+    check(ctx, vga_insertion_call_table(ctx, pos.size(), rows.data(), c.length.data(), c.length_reads.data(), c.seq.data(), c.seq_reads.data(), nullptr));
+    trace_mark("insertions called");
 }
 
 void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix)
@@ -409,6 +475,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
         out.n_variant_tested = variants_.n_tested; out.n_variant_calls = variants_.n_calls;
         if (files) variant_write(ix_, variants_, out_prefix);
         trace_mark("variants written");
+    }
+    if (inserting()) {
+        insertion_write(ix_, variants_, ins_calls_, out, out_prefix);
+        trace_mark("insertions written");
     }
     if (opt_.pileup) {
         pileup_.pad({ix_.seq_length * 7});
