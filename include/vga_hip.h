@@ -124,6 +124,12 @@ int vga_batch_create(vga_ctx *ctx, const char *reads_concat, const uint64_t *rea
 /* May be called before or after vga_ctx_destroy of the batch's context: destroying the context releases the
  * batch's device memory and detaches it (later map / align calls on it return VGA_ERR_ARG). */
 void vga_batch_destroy(vga_batch *b);
+/* The two halves of a batch as the map and align kernels read them: forward[total] and reverse[total] (either may be NULL),
+ * read r at read_off[r] in both.  from_host = 0: the device's copy (built with k_revcomp_reads if the batch has none yet);
+ * from_host = 1: the host's (vga_batch_revcomp_host).  The kernel seam of the reverse complement, as vga_poa_batch is for POA:
+ * the library itself never reads a reverse half back.  VGA_ERR_ARG for a NULL batch or one whose context is gone.
+ * (Added within ABI 6: one function, no struct.) */
+int vga_batch_strands(vga_batch *b, int from_host, char *forward, char *reverse);
 
 /* ---- map: anchors + chains ------------------------------------------------------------------ */
 typedef struct {

@@ -29,7 +29,7 @@ PILEUP_COLUMNS = ("A", "C", "G", "T", "N", "del", "ins")
 # every symbol include/vga_hip.h declares
 ABI_SYMBOLS = [
     "vga_ctx_create", "vga_ctx_destroy", "vga_last_error", "vga_ctx_synchronize", "vga_abi_version",
-    "vga_index_upload", "vga_batch_create", "vga_batch_destroy", "vga_map_default_params", "vga_map_batch",
+    "vga_index_upload", "vga_batch_create", "vga_batch_destroy", "vga_batch_strands", "vga_map_default_params", "vga_map_batch",
     "vga_map_result_free", "vga_poa_default_params", "vga_poa_result_free", "vga_poa_batch", "vga_align_batch",
     "vga_align_result_free", "vga_last_kernel_times", "vga_chain_paths_text", "vga_chain_text_free",
     "vga_align_prepare", "vga_ctx_set_pool_fraction", "vga_ctx_set_host_threads",
@@ -201,6 +201,9 @@ def load_library():
     L.vga_index_upload.argtypes = [vp, _P(IndexDesc)]
     L.vga_batch_create.argtypes = [vp, C.c_char_p, _P(C.c_uint64), C.c_uint64, _P(vp)]
     L.vga_batch_destroy.argtypes = [vp]
+    if hasattr(L, "vga_batch_strands"):  # (absent from an older build named by VGA_LIB; Batch.strands then fails)
+        L.vga_batch_strands.argtypes = [vp, C.c_int, _P(C.c_char), _P(C.c_char)]
+        L.vga_batch_strands.restype = C.c_int
     L.vga_map_default_params.argtypes = [_P(MapParams)]
     L.vga_map_batch.argtypes = [vp, _P(MapParams), _P(_P(MapResult))]
     L.vga_map_result_free.argtypes = [_P(MapResult)]
@@ -513,18 +516,28 @@ class AlignOut:
 
 
 class Batch:
-    def __init__(self, ctx: "Context", seqs: Sequence[str]):
+    def __init__(self, ctx: "Context", seqs: Sequence):
+        """seqs: str (ASCII) or bytes, which may hold any byte value"""
         self.ctx = ctx
         L = ctx.L
         self.seqs = list(seqs)
-        self._concat = "".join(self.seqs).encode()
+        raw = [s if isinstance(s, (bytes, bytearray)) else s.encode() for s in self.seqs]
+        self._concat = b"".join(raw)
         off = np.zeros(len(self.seqs) + 1, dtype=np.uint64)
         if self.seqs:
-            off[1:] = np.cumsum([len(s) for s in self.seqs], dtype=np.uint64)
+            off[1:] = np.cumsum([len(s) for s in raw], dtype=np.uint64)
         self._off = off
         h = C.c_void_p()
         ctx._check(L.vga_batch_create(ctx.h, self._concat, _u64p(off), len(self.seqs), C.byref(h)))
         self.h = h
+
+    def strands(self, from_host: bool = False):
+        """vga_batch_strands, the kernel seam of the reverse complement -> (forward, reverse): the two halves of the batch as
+        the map and align kernels read them, read r at its offset in both; the device's copy, or the host's with from_host"""
+        n = len(self._concat)
+        fwd, rev = C.create_string_buffer(max(1, n)), C.create_string_buffer(max(1, n))
+        self.ctx._check(self.ctx.L.vga_batch_strands(self.h, 1 if from_host else 0, fwd, rev))
+        return fwd.raw[:n], rev.raw[:n]
 
     def map(self, params: Optional[MapParams] = None) -> MapOut:
         L = self.ctx.L

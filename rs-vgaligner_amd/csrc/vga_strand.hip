@@ -7,6 +7,7 @@
 #include "vga_common.hpp"
 
 #include <algorithm>
+#include <cstring>
 
 #define VGA_RC_NT 256
 #define VGA_RC_TILE (VGA_RC_NT * 4)  // output bytes per tile: one 32-bit word per thread
@@ -117,4 +118,38 @@ void vga_batch_revcomp_host(vga_batch *b)
         for (uint64_t i = 0; i < L; i++) s[T + off + i] = (char)vga_switch_base((uint8_t)s[off + L - 1 - i]);
     }, (unsigned)std::max<uint64_t>(1, T / 4000000));
     b->rc_host = true;
+}
+
+// The kernel seam: what the two routes above left (or now leave) in the batch, copied out.  Nothing else reads a reverse half
+// back; the map and align kernels take it where it is.
+static int batch_strands(vga_batch *b, int from_host, char *forward, char *reverse)
+{
+    vga_ctx *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    const uint64_t T = b->total_bases;
+    if (from_host) {
+        vga_batch_revcomp_host(b);
+        if (T && forward) memcpy(forward, b->reads.data(), T);
+        if (T && reverse) memcpy(reverse, b->reads.data() + T, T);
+        return VGA_OK;
+    }
+    vga_timers_reset(ctx);
+    const int rc = vga_batch_revcomp_device(b);
+    if (rc != VGA_OK) return rc;
+    if (T && forward) VGA_HIP_CHECK(ctx, hipMemcpyAsync(forward, b->d_reads, T, hipMemcpyDeviceToHost, ctx->stream));
+    if (T && reverse) VGA_HIP_CHECK(ctx, hipMemcpyAsync(reverse, b->d_reads + T, T, hipMemcpyDeviceToHost, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    vga_timers_collect(ctx);
+    return VGA_OK;
+}
+
+extern "C" int vga_batch_strands(vga_batch *b, int from_host, char *forward, char *reverse)
+{
+    if (!b || !b->ctx) return VGA_ERR_ARG;  // b->ctx == nullptr: the context was destroyed
+    try {
+        return batch_strands(b, from_host, forward, reverse);
+    } catch (const std::bad_alloc &) {
+        return vga_set_error(b->ctx, VGA_ERR_NOMEM, "vga_batch_strands: out of host memory");
+    }
 }
