@@ -616,6 +616,68 @@ int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *rows_in /
                              uint64_t *length_reads /* n */, uint8_t *seq /* n * 8 */, uint64_t *seq_reads /* n * 8 */,
                              uint64_t *rows /* n * 49 */);
 
+/* ---- phase: which alleles of the heterozygous calls travel together on the reads ----------
+ * Stands in for nothing in the reference.  The variant call reports independent diploid sites; this is the read-backed linkage
+ * between the heterozygous ones.  It is defined on the alignments GAF text, the node starts, the graph's letters and the sites
+ * alone (tests/phase_ref.py recomputes it).
+ *   sites        H graph bases pos[0] < pos[1] < .. with two alleles x[h] < y[h] in A < C < G < T < D (0 .. 4).
+ *   observation  of the record reported for a read at site h, the record walked exactly as the pileup walks it: a ":N" that
+ *                covers the base observes the base's own letter, "*gq" observes q (a q that is not a c g t observes "other"),
+ *                "-g.." observes D, a "+q.." observes nothing.  A record can consume a base more than once (a self-loop):
+ *                sx = some observation equals x, sy likewise; obs = 0 for sx and not sy, 1 for sy and not sx, 2 when the base
+ *                is consumed otherwise, 3 when it is not consumed.
+ *   site_reads   [h][0 .. 2]: the records with obs 0, 1 and 2 at site h.
+ *   links        [h][d - 1][2 a + b], 1 <= d <= 8 (the window: a choice, not a measurement), h + d < H, a, b in {0, 1}: the
+ *                records with obs a at site h and obs b at site h + d; rows with h + d >= H are zero.
+ *   the store    one record per reported alignment, three words {off, n_runs, n_sparse}, and its words from word `off` on:
+ *                  n_runs run-event words, in pairs:  position << 1  where a run of matched bases starts (the word covers that
+ *                    position),  (position behind the run's last base) << 1 | 1  where it ends (the word does not cover it);
+ *                  n_sparse sparse words  position << 3 | column:  0 .. 3 the read shows A C G T at the base, 4 another letter,
+ *                    5 the base is deleted, 6 an insertion behind the base (no observation).
+ *                These are the pileup's lists (k_pu_events), kept as they are.
+ *   vga_phase_begin        needs vga_pileup_begin on ctx (VGA_ERR_ARG otherwise; VGA_ERR_NO_INDEX without an index).  From then on
+ *                          every vga_align_batch copies the pileup lists of its reported alignments into a grow-only device store
+ *                          of the context (k_ph_keep), device-made and host-made lists alike.  The store starts at
+ *                          VGA_PHASE_STORE_WORDS words (2^20) and doubles; when it cannot grow or would pass 2^32 - 1 words
+ *                          vga_align_batch fails with VGA_ERR_NOMEM and says how many reads were kept.  Calling it again empties
+ *                          the store.  The store belongs to the context's index and to its pileup: a new index or
+ *                          vga_pileup_end drops it.
+ *   vga_phase_read         recs: n_reads x 3, words: n_words; *n_reads and *n_words are always written, so a first call with NULL
+ *                          arrays sizes the second.  VGA_ERR_ARG without _begin.  Does not reset.
+ *   vga_phase_reset        empties the store, keeps it on (VGA_ERR_ARG without _begin).
+ *   vga_phase_end          frees the store and stops keeping.
+ *   vga_phase_links        links (n_sites x 8 x 4) and site_reads (n_sites x 3) from the context's own store and the letters of
+ *                          its index, *n_reads the stored records (k_ph_obs and k_ph_link over tiles of reads; the tile's read
+ *                          count is a multiple of 64 sized from 64 MiB and n_sites, VGA_PHASE_READ_TILE overrides it).
+ *                          VGA_ERR_ARG without _begin, for sites that do not ascend strictly inside the graph, for alleles that
+ *                          are not x < y <= 4, and for a NULL array with n_sites > 0; VGA_ERR_UNSUPPORTED above 2^24 sites.
+ *                          n_sites = 0 is accepted.  Does not reset.
+ *   vga_phase_links_lists  the kernel seam, and the route of several contexts whose stores were concatenated: explicit records
+ *                          and words on a graph of n_bases bases, and ref[h] the own letter of site h: 0 .. 3 for A C G T, 4 for
+ *                          any other letter (a run of matches observes "other" there).  Needs a context only: no index, no
+ *                          store touched.  Everything a kernel follows is checked first: a record inside the n_words words, run
+ *                          words in start / end pairs with end above start and at most n_bases, sparse positions below n_bases
+ *                          and columns below 7, the sites as above, ref <= 4; a violation is VGA_ERR_ARG and launches nothing.
+ *   vga_phase_chain        no context, on the host, integer-only; the one definition (csrc/vga_phase.hpp).  For h in order the
+ *                          smallest d in 1 .. min(8, h) whose l = links[h - d][d - 1] has cis = l[0] + l[3] and trans = l[1] +
+ *                          l[2] that differ, by at least min_links (1 .. 65535; the command line's default is 2: a choice, not a
+ *                          measurement), gives ps[h] = ps[h - d], flip[h] = flip[h - d] xor (trans > cis), link_d[h] = d;
+ *                          otherwise h opens a set: ps[h] = h + 1 (its own line among the sites), flip 0, link_d 0.  Haplotype a
+ *                          carries flip ? y : x, haplotype b the other allele.  VGA_ERR_ARG for min_links out of range or a NULL
+ *                          array with n_sites > 0.
+ * With the store off vga_align_batch does what it did before these calls existed: no k_ph_* launch, no extra allocation. */
+int vga_phase_begin(vga_ctx *ctx);
+int vga_phase_read(vga_ctx *ctx, uint32_t *recs /* n_reads * 3 */, uint32_t *words /* n_words */, uint64_t *n_reads, uint64_t *n_words);
+int vga_phase_reset(vga_ctx *ctx);
+int vga_phase_end(vga_ctx *ctx);
+int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos /* n_sites */, const uint8_t *x, const uint8_t *y,
+                    uint32_t *links /* n_sites * 32 */, uint32_t *site_reads /* n_sites * 3 */, uint64_t *n_reads);
+int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs /* n_reads * 3 */, uint64_t n_words,
+                          const uint32_t *words, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
+                          const uint8_t *ref, uint32_t *links /* n_sites * 32 */, uint32_t *site_reads /* n_sites * 3 */);
+int vga_phase_chain(uint64_t n_sites, const uint32_t *links /* n_sites * 32 */, uint32_t min_links, uint32_t *ps, uint8_t *flip,
+                    uint8_t *link_d);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "vga_path_edit_begin", "vga_path_edit_read", "vga_path_edit_last", "vga_path_edit_reset", "vga_path_edit_end", "vga_path_edit_pairs",
     "vga_variant_call", "vga_variant_call_table",
     "vga_insertion_begin", "vga_insertion_read", "vga_insertion_reset", "vga_insertion_end", "vga_insertion_call", "vga_insertion_call_table",
+    "vga_phase_begin", "vga_phase_read", "vga_phase_reset", "vga_phase_end", "vga_phase_links", "vga_phase_links_lists", "vga_phase_chain",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -98,6 +99,13 @@ INSERTION_COLS = 9 + INSERTION_MAX_LEN * 5
 INSERTION_LETTERS = "ACGTN"
 INSERTION_MAX_SEQ = 1 << 26
 INSERTION_MAX_COUNT = 1 << 40
+
+# the phase links (csrc/vga_phase.hpp): sites at most this far apart in site order are linked, the default of --phase-min-links
+# and its upper bound, the columns of a sparse word of the store (A C G T, another letter, deleted, insertion)
+PHASE_WINDOW = 8
+PHASE_MIN_LINKS = 2
+PHASE_MAX_MIN_LINKS = 65535
+PHASE_COLS = 7
 
 
 class VgaError(RuntimeError):
@@ -299,6 +307,17 @@ def load_library():
         for name in ABI_SYMBOLS:
             if name.startswith("vga_insertion_"):
                 getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_phase_begin"):  # (absent from an older build named by VGA_LIB; the Context.phase* calls then fail)
+        u64p, u32p, u8p, u64 = _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint8), C.c_uint64
+        for name in ("vga_phase_begin", "vga_phase_reset", "vga_phase_end"):
+            getattr(L, name).argtypes = [vp]
+        L.vga_phase_read.argtypes = [vp, u32p, u32p, u64p, u64p]
+        L.vga_phase_links.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u32p, u64p]
+        L.vga_phase_links_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u32p]
+        L.vga_phase_chain.argtypes = [u64, u32p, C.c_uint32, u32p, u8p, u8p]
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_phase_"):
+                getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -374,6 +393,21 @@ def genotype_likelihood_table(lam: int = GENOTYPE_LIK_LAMBDA, cap: int = GENOTYP
     if rc != VGA_OK:
         raise VgaError(rc, "genotype_likelihood_table: lam %r is 1 to %d and cap %r 1 to %d" % (lam, GENOTYPE_LIK_MAX_LAMBDA, cap, GENOTYPE_LIK_MAX_CAP))
     return t
+
+
+def phase_chain(links, min_links: int = PHASE_MIN_LINKS):
+    """vga_phase_chain -> (ps uint32[H], flip uint8[H], link_d uint8[H]) from links[H, 8, 4]: the library's one definition of the
+    chain rule (csrc/vga_phase.hpp); needs no context and no device"""
+    ln = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, PHASE_WINDOW, 4)
+    n = len(ln)
+    if not 0 <= int(min_links) < 1 << 32:
+        raise VgaError(-1, "phase_chain: min_links %r" % (min_links,))
+    ps, flip, link_d = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, n), dtype=np.uint8)
+    u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+    rc = load_library().vga_phase_chain(n, _u32p(ln if n else np.zeros(1, dtype=np.uint32)), int(min_links), _u32p(ps), u8(flip), u8(link_d))
+    if rc != VGA_OK:
+        raise VgaError(rc, "phase_chain: min_links %r is 1 to %d" % (min_links, PHASE_MAX_MIN_LINKS))
+    return ps[:n], flip[:n], link_d[:n]
 
 
 def genotype_likelihood_rank(cost, n_paths: int, top: Optional[int] = None):
@@ -855,6 +889,61 @@ class Context:
         tab = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, INSERTION_COLS)
         return self._insertion(lambda *outs: self.L.vga_insertion_call_table(self.h, len(tab), _u64p(tab if len(tab) else np.zeros((1, INSERTION_COLS), dtype=np.uint64)),
                                                                              *outs), len(tab))
+
+    def phase_begin(self) -> None:
+        """vga_phase_begin: from now on every align() of this context keeps the pileup lists of its reported alignments (needs
+        pileup_begin)"""
+        self._check(self.L.vga_phase_begin(self.h))
+
+    def phase_reads(self):
+        """vga_phase_read -> (recs[n_reads, 3] uint32: off, n_runs, n_sparse; words uint32): the store as phase_links_lists takes
+        it; does not reset"""
+        n, w = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_phase_read(self.h, None, None, C.byref(n), C.byref(w)))
+        recs, words = np.zeros((max(1, n.value), 3), dtype=np.uint32), np.zeros(max(1, w.value), dtype=np.uint32)
+        self._check(self.L.vga_phase_read(self.h, _u32p(recs), _u32p(words), C.byref(n), C.byref(w)))
+        return recs[:n.value], words[:w.value]
+
+    def phase_reset(self) -> None:
+        """vga_phase_reset: empty the store, keep it on"""
+        self._check(self.L.vga_phase_reset(self.h))
+
+    def phase_end(self) -> None:
+        """vga_phase_end: free the store, stop keeping"""
+        self._check(self.L.vga_phase_end(self.h))
+
+    @staticmethod
+    def _phase_sites(pos, *alleles):
+        at = np.ascontiguousarray(pos, dtype=np.uint32).reshape(-1)
+        cols = [np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for a in alleles]
+        if any(len(c) != len(at) for c in cols):
+            raise VgaError(-1, "phase: %d sites and alleles of %s" % (len(at), [len(c) for c in cols]))
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        return len(at), pad(at), [pad(c) for c in cols]
+
+    def phase_links(self, pos, x, y):
+        """vga_phase_links: the links between the sites pos (ascending graph bases) with alleles x < y (0 .. 4 = A C G T D), from
+        this context's own store -> (links[H, 8, 4] uint32, site_reads[H, 3] uint32, n_reads); does not reset"""
+        n, at, (xs, ys) = self._phase_sites(pos, x, y)
+        links, sr = np.zeros((max(1, n), PHASE_WINDOW, 4), dtype=np.uint32), np.zeros((max(1, n), 3), dtype=np.uint32)
+        n_reads = C.c_uint64(0)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        self._check(self.L.vga_phase_links(self.h, n, _u32p(at), u8(xs), u8(ys), _u32p(links), _u32p(sr), C.byref(n_reads)))
+        return links[:n], sr[:n], int(n_reads.value)
+
+    def phase_links_lists(self, recs, words, n_bases, pos, x, y, ref):
+        """vga_phase_links_lists, the kernel seam: the same from explicit records recs[n_reads, 3] and their words on a graph of
+        n_bases bases; ref[h] is the own letter of site h (0 .. 3 = A C G T, 4 anything else) -> (links, site_reads).  Needs a
+        context only."""
+        rc = np.ascontiguousarray(recs, dtype=np.uint32).reshape(-1, 3)
+        wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        n, at, (xs, ys, rf) = self._phase_sites(pos, x, y, ref)
+        links, sr = np.zeros((max(1, n), PHASE_WINDOW, 4), dtype=np.uint32), np.zeros((max(1, n), 3), dtype=np.uint32)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=np.uint32)
+        self._check(self.L.vga_phase_links_lists(self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), n, _u32p(at), u8(xs), u8(ys), u8(rf),
+                                                 _u32p(links), _u32p(sr)))
+        return links[:n], sr[:n]
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

@@ -38,6 +38,7 @@ struct cov_state;
 struct ps_state;
 struct pu_state;
 struct ia_state;
+struct ph_state;
 struct poa_ws;
 
 struct vga_dev_index {
@@ -84,6 +85,8 @@ struct vga_dev_index {
     // the table of inserted lengths and letters of this index while it is counted (vga_insertion.hip), with event lists of its own:
     // released with the index
     vga_owned<ia_state> ia{nullptr, nullptr};
+    // the store of the winners' pileup lists while the phase store is on (vga_phase.hip): released with the index, and with the pileup
+    vga_owned<ph_state> ph{nullptr, nullptr};
 };
 
 struct vga_timer_entry {

@@ -1,0 +1,415 @@
+// vga_phase.hip -- the read-backed linkage of heterozygous sites: k_ph_keep, k_ph_obs, k_ph_link and the C entry points
+// vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain.  See vga_phase.hpp for the shape.
+//
+// Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
+// read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
+// not at all.  Per (site, read) three bits are ORed together (saw x, saw y, saw anything else), so a read that consumes a base
+// twice gives the same answer in any order; obs = 0 for x alone, 1 for y alone, 2 for anything else consumed.  link[h][d - 1][2 a +
+// b] counts the reads with obs a at site h and b at site h + d.  ORs and sums of integers: the tables are exact and repeatable.
+#include "vga_phase.hpp"
+#include "vga_pileup.hpp"
+
+// the store keeps k_pu_events' words as they are
+static_assert(PH_COL_OTHER == PU_COL_N && PH_COL_DEL == PU_COL_DEL && PH_COL_INS == PU_COL_INS && PH_COLS == PU_COLS && PH_MAX_SEQ == PU_MAX_SEQ,
+              "the pileup's sparse columns and positions");
+
+namespace {
+
+// One wave per winner: its pileup list (device buffer, or the host-built lists for record flags 3) goes to dst[wi] of the store.
+// The host has scanned the staged records: dst[wi] + n_a + n_b lies inside the store.
+__global__ __launch_bounds__(64) void k_ph_keep(uint32_t n, const oplist_rec *__restrict__ recs, const uint32_t *__restrict__ lists,
+                                                 const uint32_t *__restrict__ host_lists, const uint32_t *__restrict__ dst, uint32_t *__restrict__ store)
+{
+    const uint32_t wi = blockIdx.x;
+    if (wi >= n) return;
+    const oplist_rec rc = recs[wi];
+    const uint32_t *src = ((rc.flags & 3u) == 3u ? host_lists : lists) + rc.off;
+    uint32_t *out = store + dst[wi];
+    const uint32_t words = rc.n_a + rc.n_b;
+    for (uint32_t i = threadIdx.x; i < words; i += 64) out[i] = src[i];
+}
+
+// the first site at or behind position p (n_sites when there is none): pos ascends strictly
+__device__ __forceinline__ uint32_t ph_lower(const uint32_t *__restrict__ pos, uint32_t n_sites, uint32_t p)
+{
+    uint32_t lo = 0, hi = n_sites;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pos[mid] < p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// sets `bits` of (site h, read r of the tile): a byte per pair, site-major, four reads to a 32-bit word
+__device__ __forceinline__ void ph_set(uint32_t *__restrict__ obs, uint32_t tile_reads, uint32_t h, uint32_t r, uint32_t bits)
+{
+    const size_t at = (size_t)h * tile_reads + r;
+    atomicOr(obs + (at >> 2), bits << (8u * (uint32_t)(at & 3u)));
+}
+
+// One wave per stored read of the tile.  The lanes stride over the sparse words (the site at the word's position, if any, sees
+// the word's allele; an insertion word is no observation) and over the pairs of run events (every site in [start, end) sees the
+// base's own letter).  A word's position only ever enters the search over the sites: no index is taken from it.
+__global__ __launch_bounds__(64) void k_ph_obs(uint32_t n, const ph_rec *__restrict__ recs, const uint32_t *__restrict__ words, uint32_t n_sites,
+                                                const uint32_t *__restrict__ pos, const uint8_t *__restrict__ sx, const uint8_t *__restrict__ sy,
+                                                const uint8_t *__restrict__ ref, uint32_t tile_reads, uint32_t *__restrict__ obs)
+{
+    const uint32_t ri = blockIdx.x;
+    if (ri >= n) return;
+    const uint32_t lane = threadIdx.x;
+    const ph_rec rc = recs[ri];
+    const uint32_t *ev = words + rc.off, *sp = ev + rc.n_runs;
+    for (uint32_t i = lane; i < rc.n_sparse; i += 64) {
+        const uint32_t w = sp[i], p = w >> 3, col = w & 7u;
+        if (col >= PH_COL_INS) continue;
+        const uint32_t h = ph_lower(pos, n_sites, p);
+        if (h >= n_sites || pos[h] != p) continue;
+        const uint32_t a = col < 4u ? col : col == PH_COL_DEL ? PH_ALLELE_DEL : 0xFFu;
+        ph_set(obs, tile_reads, h, ri, a == sx[h] ? PH_SAW_X : a == sy[h] ? PH_SAW_Y : PH_SAW_OTHER);
+    }
+    for (uint32_t i = lane; i < rc.n_runs / 2u; i += 64) {
+        const uint32_t start = ev[2u * i] >> 1, end = ev[2u * i + 1u] >> 1;
+        for (uint32_t h = ph_lower(pos, n_sites, start); h < n_sites && pos[h] < end; h++) {
+            const uint32_t a = ref[h] < 4u ? ref[h] : 0xFFu;
+            ph_set(obs, tile_reads, h, ri, a == sx[h] ? PH_SAW_X : a == sy[h] ? PH_SAW_Y : PH_SAW_OTHER);
+        }
+    }
+}
+
+// the observation of a byte of the tile: 0 x alone, 1 y alone, 2 anything else consumed, 3 not consumed
+__device__ __forceinline__ uint32_t ph_code(uint32_t o)
+{
+    const uint32_t xy = o & (PH_SAW_X | PH_SAW_Y);
+    return xy == PH_SAW_X ? 0u : xy == PH_SAW_Y ? 1u : o ? 2u : 3u;
+}
+
+// One workgroup per site h.  Its waves stride over the tile's reads, a read per lane: the byte of site h and those of the sites
+// h + 1 .. h + PH_WINDOW (each row read coalesced), the four combinations per distance counted with ballots and popcounts into
+// wave-uniform counters, the waves' counters summed through LDS.  The workgroup owns link[h] and site_reads[h] and the tiles run
+// one after another on the stream: plain loads and stores add the tile's sums.
+__global__ __launch_bounds__(PH_LINK_BLOCK) void k_ph_link(uint32_t n_sites, uint32_t tile_reads, uint32_t n, const uint8_t *__restrict__ obs,
+                                                            uint32_t *__restrict__ links, uint32_t *__restrict__ site_reads)
+{
+    __shared__ uint32_t part[PH_LINK_BLOCK / 64u][PH_LINK_ROW + PH_SITE_COLS];
+    const uint32_t h = blockIdx.x;
+    if (h >= n_sites) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nd = n_sites - 1u - h < PH_WINDOW ? n_sites - 1u - h : PH_WINDOW;
+    const uint8_t *row = obs + (size_t)h * tile_reads;
+    // Two passes over the reads, four distances each: the counters of all eight beside the ballots do not fit the scalar
+    // registers.  No load is under a lane mask: a lane behind the tile's last read takes that read and is masked out of site h's
+    // ballots, and a distance behind the last site is skipped by the whole workgroup (its byte reads "not consumed").
+#pragma unroll 1
+    for (uint32_t half = 0; half < 2u; half++) {
+        uint32_t cnt[PH_LINK_ROW / 2u], seen[PH_SITE_COLS];
+#pragma unroll
+        for (uint32_t k = 0; k < PH_LINK_ROW / 2u; k++) cnt[k] = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < PH_SITE_COLS; k++) seen[k] = 0;
+        const uint32_t d0 = half * (PH_WINDOW / 2u) + 1u;
+        for (uint32_t base = wave * 64u; base < n; base += PH_LINK_BLOCK) {
+            const uint32_t r = base + lane < n ? base + lane : n - 1u;
+            const uint64_t live = __builtin_amdgcn_ballot_w64(base + lane < n);
+            const uint32_t a = ph_code(row[r]);
+            uint32_t o[PH_WINDOW / 2u];  // (the four loads are in flight together)
+#pragma unroll
+            for (uint32_t d = 0; d < PH_WINDOW / 2u; d++) o[d] = d0 + d <= nd ? row[(d0 + d) * tile_reads + r] : 0u;  // (uniform)
+            const uint64_t a_x = __builtin_amdgcn_ballot_w64(a == 0u) & live, a_y = __builtin_amdgcn_ballot_w64(a == 1u) & live;
+            seen[0] += (uint32_t)__builtin_popcountll(a_x);
+            seen[1] += (uint32_t)__builtin_popcountll(a_y);
+            seen[2] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(a == 2u) & live);
+#pragma unroll
+            for (uint32_t d = 0; d < PH_WINDOW / 2u; d++) {
+                const uint32_t b = ph_code(o[d]);
+                const uint64_t b_x = __builtin_amdgcn_ballot_w64(b == 0u), b_y = __builtin_amdgcn_ballot_w64(b == 1u);
+                uint32_t *c = cnt + d * PH_LINK_COLS;
+                c[0] += (uint32_t)__builtin_popcountll(a_x & b_x);
+                c[1] += (uint32_t)__builtin_popcountll(a_x & b_y);
+                c[2] += (uint32_t)__builtin_popcountll(a_y & b_x);
+                c[3] += (uint32_t)__builtin_popcountll(a_y & b_y);
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (uint32_t k = 0; k < PH_LINK_ROW / 2u; k++) part[wave][half * (PH_LINK_ROW / 2u) + k] = cnt[k];
+#pragma unroll
+            for (uint32_t k = 0; k < PH_SITE_COLS; k++) part[wave][PH_LINK_ROW + k] = seen[k];  // (the same in both passes)
+        }
+    }
+    __syncthreads();
+    if (tid < PH_LINK_ROW + PH_SITE_COLS) {
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < PH_LINK_BLOCK / 64u; w++) s += part[w][tid];
+        uint32_t *out = tid < PH_LINK_ROW ? links + (size_t)h * PH_LINK_ROW + tid : site_reads + (size_t)h * PH_SITE_COLS + (tid - PH_LINK_ROW);
+        *out += s;
+    }
+}
+
+}  // namespace
+
+// The store of a context's index while it is on (vga_dev_index::ph: released with the index): the words on the device, the
+// records on the host
+struct ph_state {
+    uint32_t *d_words = nullptr;
+    uint64_t cap = 0, n_words = 0, first_words = PH_STORE_WORDS0;
+    std::vector<ph_rec> recs;
+    vga_hbuf<uint32_t> h_dst;
+    vga_dbuf<uint32_t> d_dst;
+    ~ph_state()
+    {
+        if (d_words) (void)hipFree(d_words);
+    }
+};
+
+ph_state *ph_active(vga_ctx *ctx) { return ctx && ctx->index.loaded && ctx->index.pu ? ctx->index.ph.get() : nullptr; }
+
+int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t nw)
+{
+    if (nw == 0) return VGA_OK;
+    hipStream_t st = ctx->stream;
+    VGA_HIP_CHECK(ctx, ph->h_dst.reserve(nw));
+    VGA_HIP_CHECK(ctx, ph->d_dst.reserve(nw));
+    uint64_t at = ph->n_words;
+    for (size_t i = 0; i < nw; i++) {
+        ph->h_dst.p[i] = (uint32_t)at;
+        at += (uint64_t)lists.h_win.p[i].n_a + lists.h_win.p[i].n_b;
+        if (at > PH_MAX_WORDS)
+            return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_align_batch: the phase store would pass 2^32 - 1 words: %zu reads kept", ph->recs.size());
+    }
+    if (at > ph->cap) {  // grows by doubling; what is stored moves on the context's stream
+        uint64_t cap = ph->cap ? ph->cap : std::max<uint64_t>(ph->first_words, 1);
+        while (cap < at) cap *= 2;
+        cap = std::min<uint64_t>(cap, PH_MAX_WORDS);
+        uint32_t *grown = nullptr;
+        {
+            vga_alloc_urgent urgent;
+            if (hipMalloc((void **)&grown, cap * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_align_batch: the phase store cannot grow to %llu words: %zu reads kept", (unsigned long long)cap,
+                                     ph->recs.size());
+            }
+        }
+        if (ph->n_words) {
+            const hipError_t e = hipMemcpyAsync(grown, ph->d_words, ph->n_words * 4, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) {
+                (void)hipFree(grown);
+                return vga_set_error(ctx, VGA_ERR_HIP, "vga_align_batch: moving the phase store: %s", hipGetErrorString(e));
+            }
+        }
+        if (ph->d_words) vga_defer_release(ph->d_words, nullptr, nullptr, 0);
+        if (getenv("VGA_TRACE")) fprintf(stderr, "[vga-trace] phase: the store grows from %llu to %llu words\n", (unsigned long long)ph->cap, (unsigned long long)cap);
+        ph->d_words = grown;
+        ph->cap = cap;
+    }
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(ph->d_dst.p, ph->h_dst.p, nw * 4, hipMemcpyHostToDevice, st));
+    const int t = vga_timer_begin(ctx, "k_ph_keep", (at - ph->n_words) * 8, st);
+    hipLaunchKernelGGL(k_ph_keep, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, lists.d_win.p, lists.d_lists.p, lists.d_host_lists.p, ph->d_dst.p, ph->d_words);
+    vga_timer_end(ctx, t);
+    VGA_HIP_CHECK(ctx, hipGetLastError());
+    for (size_t i = 0; i < nw; i++) ph->recs.push_back(ph_rec{ph->h_dst.p[i], lists.h_win.p[i].n_a, lists.h_win.p[i].n_b});
+    ph->n_words = at;
+    return VGA_OK;
+}
+
+// ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
+extern "C" int vga_phase_begin(vga_ctx *ctx)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_phase_begin: no index uploaded");
+    if (!ctx->index.pu) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_begin: the pileup is not counted (vga_pileup_begin): its lists are what the store keeps");
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (!ctx->index.ph && !(ctx->index.ph = vga_make_owned<ph_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_phase_begin: out of host memory");
+    ph_state *ph = ctx->index.ph.get();
+    ph->n_words = 0;
+    ph->recs.clear();
+    if (const char *e = getenv("VGA_PHASE_STORE_WORDS")) ph->first_words = (uint64_t)std::max(1ll, atoll(e));
+    return VGA_OK;
+}
+
+extern "C" int vga_phase_reset(vga_ctx *ctx)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    ph_state *ph = ph_active(ctx);
+    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_reset: the store is off (vga_phase_begin)");
+    ph->n_words = 0;
+    ph->recs.clear();
+    return VGA_OK;
+}
+
+extern "C" int vga_phase_end(vga_ctx *ctx)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    ctx->index.ph.reset();
+    return VGA_OK;
+}
+
+extern "C" int vga_phase_read(vga_ctx *ctx, uint32_t *recs, uint32_t *words, uint64_t *n_reads, uint64_t *n_words)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    ph_state *ph = ph_active(ctx);
+    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_read: the store is off (vga_phase_begin)");
+    (void)hipSetDevice(ctx->device);
+    if (recs && !ph->recs.empty()) memcpy(recs, ph->recs.data(), ph->recs.size() * sizeof(ph_rec));
+    if (words && ph->n_words) {
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(words, ph->d_words, ph->n_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (n_reads) *n_reads = ph->recs.size();
+    if (n_words) *n_words = ph->n_words;
+    return VGA_OK;
+}
+
+namespace {
+
+static_assert(sizeof(ph_rec) == 12, "a record is three words in the interface");
+
+struct ph_sites {
+    uint64_t n;
+    const uint32_t *pos;
+    const uint8_t *x, *y, *ref;
+};
+
+// what the kernels rely on: sites that ascend strictly inside the graph, x < y <= D, ref <= other
+int ph_check_sites(vga_ctx *ctx, const char *who, const ph_sites &s, uint64_t n_bases, const uint32_t *links, const uint32_t *site_reads)
+{
+    if (s.n > PH_MAX_SITES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu sites, 2^24 at most", who, (unsigned long long)s.n);
+    if (s.n && (!s.pos || !s.x || !s.y || !links || !site_reads)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)s.n);
+    for (uint64_t h = 0; h < s.n; h++) {
+        if (s.pos[h] >= n_bases) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu at base %u, the graph has %llu", who, (unsigned long long)h, s.pos[h], (unsigned long long)n_bases);
+        if (h && s.pos[h] <= s.pos[h - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu does not lie behind the one before it", who, (unsigned long long)h);
+        if (!(s.x[h] < s.y[h] && s.y[h] <= PH_ALLELE_DEL))
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has alleles %u, %u (x < y <= 4)", who, (unsigned long long)h, s.x[h], s.y[h]);
+        if (s.ref && s.ref[h] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has own letter %u (0 .. 4)", who, (unsigned long long)h, s.ref[h]);
+    }
+    return VGA_OK;
+}
+
+uint32_t ph_tile_reads(uint64_t n_reads, uint64_t n_sites)
+{
+    const uint64_t all = (n_reads + 63u) & ~63ull;
+    uint64_t t = (PH_TILE_BYTES / n_sites) & ~63ull;
+    if (const char *e = getenv("VGA_PHASE_READ_TILE")) t = ((uint64_t)std::max(1ll, atoll(e)) + 63u) & ~63ull;
+    return (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(t, std::min<uint64_t>(all, 1ull << 24)));
+}
+
+// k_ph_obs and k_ph_link over the n_reads stored reads (records on the host, words on the device), tile by tile, and the two
+// tables back to the host.  Everything was checked by the caller.
+int ph_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, uint32_t *links, uint32_t *site_reads)
+{
+    hipStream_t st = ctx->stream;
+    vga_timers_reset(ctx);
+    if (s.n == 0) return VGA_OK;
+    const uint32_t H = (uint32_t)s.n;
+    if (n_reads == 0) {
+        memset(links, 0, (size_t)H * PH_LINK_ROW * 4);
+        memset(site_reads, 0, (size_t)H * PH_SITE_COLS * 4);
+        return VGA_OK;
+    }
+    const uint32_t T = ph_tile_reads(n_reads, s.n);
+    vga_dbuf<ph_rec> d_recs;
+    vga_dbuf<uint32_t> d_pos, d_obs, d_out;  // d_out: links, then site_reads
+    vga_dbuf<uint8_t> d_bytes;               // x, y, ref
+    const size_t obs_words = (size_t)H * T / 4u, out_words = (size_t)H * (PH_LINK_ROW + PH_SITE_COLS);
+    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
+    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve(H));
+    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3));
+    VGA_HIP_CHECK_OOM(ctx, d_obs.reserve(obs_words));
+    VGA_HIP_CHECK_OOM(ctx, d_out.reserve(out_words));
+    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H;
+    uint32_t *d_links = d_out.p, *d_sr = d_out.p + (size_t)H * PH_LINK_ROW;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_out.p, 0, out_words * 4, st));
+    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
+        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_obs.p, 0, obs_words * 4, st));
+        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
+        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_ph_link", (uint64_t)H * n, st);
+        hipLaunchKernelGGL(k_ph_link, dim3(H), dim3(PH_LINK_BLOCK), 0, st, H, T, n, (const uint8_t *)d_obs.p, d_links, d_sr);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+    }
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(links, d_links, (size_t)H * PH_LINK_ROW * 4, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(site_reads, d_sr, (size_t)H * PH_SITE_COLS * 4, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    vga_timers_collect(ctx);
+    return VGA_OK;
+}
+
+}  // namespace
+
+extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, uint32_t *links, uint32_t *site_reads,
+                               uint64_t *n_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    ph_state *ph = ph_active(ctx);
+    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_links: the store is off (vga_phase_begin)");
+    ph_sites s = {n_sites, pos, x, y, nullptr};
+    const int rc = ph_check_sites(ctx, "vga_phase_links", s, ctx->index.seq_length, links, site_reads);
+    if (rc != VGA_OK) return rc;
+    std::vector<uint8_t> ref(n_sites + 1);
+    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
+    s.ref = ref.data();
+    if (n_reads) *n_reads = ph->recs.size();
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    return ph_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, links, site_reads);
+}
+
+extern "C" int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
+                                     uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref, uint32_t *links,
+                                     uint32_t *site_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const char *who = "vga_phase_links_lists";
+    if (n_bases > PH_MAX_SEQ || n_words > PH_MAX_WORDS || n_reads > PH_MAX_WORDS)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu bases, %llu reads, %llu words: 2^29 bases and 2^32 - 1 reads and words at most", who,
+                             (unsigned long long)n_bases, (unsigned long long)n_reads, (unsigned long long)n_words);
+    const ph_sites s = {n_sites, pos, x, y, ref};
+    const int rc = ph_check_sites(ctx, who, s, n_bases, links, site_reads);
+    if (rc != VGA_OK) return rc;
+    if ((n_sites && !ref) || (n_reads && !recs) || (n_words && !words)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array", who);
+    const ph_rec *rr = (const ph_rec *)recs;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const ph_rec &c = rr[r];
+        if ((uint64_t)c.off + c.n_runs + c.n_sparse > n_words || (c.n_runs & 1u))
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: words %u + %u + %u of %llu, run words in pairs", who, (unsigned long long)r, c.off, c.n_runs,
+                                 c.n_sparse, (unsigned long long)n_words);
+        const uint32_t *ev = words + c.off, *sp = ev + c.n_runs;
+        for (uint32_t i = 0; i < c.n_runs; i += 2) {
+            const uint32_t a = ev[i], b = ev[i + 1];
+            if ((a & 1u) || !(b & 1u) || (b >> 1) <= (a >> 1) || (b >> 1) > n_bases)
+                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: run words %u, %u are no start and end inside %llu bases", who, (unsigned long long)r, a, b,
+                                     (unsigned long long)n_bases);
+        }
+        for (uint32_t i = 0; i < c.n_sparse; i++)
+            if ((sp[i] >> 3) >= n_bases || (sp[i] & 7u) >= PH_COLS)
+                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: sparse word %u (position below %llu, column below 7)", who, (unsigned long long)r, sp[i],
+                                     (unsigned long long)n_bases);
+    }
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    vga_dbuf<uint32_t> d_words;
+    VGA_HIP_CHECK_OOM(ctx, d_words.reserve((size_t)n_words + 1));
+    if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    return ph_run(ctx, rr, n_reads, d_words.p, s, links, site_reads);
+}
+
+extern "C" int vga_phase_chain(uint64_t n_sites, const uint32_t *links, uint32_t min_links, uint32_t *ps, uint8_t *flip, uint8_t *link_d)
+{
+    if (min_links < 1u || min_links > PH_MIN_LINKS_MAX || n_sites > PH_MAX_SITES) return VGA_ERR_ARG;
+    if (n_sites && (!links || !ps || !flip || !link_d)) return VGA_ERR_ARG;
+    ph_chain(n_sites, links, min_links, ps, flip, link_d);
+    return VGA_OK;
+}

@@ -7,6 +7,7 @@
 // context's leading_ins when no base was consumed yet.  All counters are 32-bit integers added with vector atomics: sums of
 // integers do not depend on order, so the table is exact and repeatable.
 #include "vga_pileup.hpp"
+#include "vga_phase.hpp"
 
 namespace {
 
@@ -187,6 +188,10 @@ int pu_add_winners(vga_ctx *ctx, pu_state *pu, const std::vector<uint32_t> &winn
                        pu->d_mdiff.p, pu->d_counts.p);
     vga_timer_end(ctx, t);
     VGA_HIP_CHECK(ctx, hipGetLastError());
+    if (ph_state *ph = ph_active(ctx)) {  // the phase store keeps the lists that were just staged (vga_phase.hpp)
+        const int kept = ph_keep_winners(ctx, ph, pu->lists, nw);
+        if (kept != VGA_OK) { (void)hipStreamSynchronize(st); return kept; }
+    }
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     pu->n_alignments += nw;
     pu->leading_ins += leading;
@@ -239,6 +244,7 @@ extern "C" int vga_pileup_end(vga_ctx *ctx)
     if (!ctx) return VGA_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    ctx->index.ph.reset();  // (the phase store keeps the pileup's lists: it ends with it)
     ctx->index.pu.reset();
     return VGA_OK;
 }

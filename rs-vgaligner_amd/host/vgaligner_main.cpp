@@ -66,7 +66,11 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"", "--call-min-depth", true, "call-min-depth"}, {"", "--call-min-qual", true, "call-min-qual"},
                           // not in the reference: length and letters of what the reads insert at the sites --call-variants reports
                           // with an insertion, counted and called on the GPU (one TSV file)
-                          {"", "--call-insertions", false, "call-insertions"}};
+                          {"", "--call-insertions", false, "call-insertions"},
+                          // not in the reference: the read-backed links between the heterozygous sites --call-variants reports,
+                          // counted on the GPU, and the phase chain on them (one TSV file); --phase-min-links N: the reads by which
+                          // cis and trans must differ for a link to join two sites (2, 1..65535)
+                          {"", "--phase", false, "phase"}, {"", "--phase-min-links", true, "phase-min-links"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -210,6 +214,15 @@ int map_main(int argc, char **argv)
     o.call_insertions = m.count("call-insertions") > 0;
     if (o.call_insertions && !o.also_align) throw Error("--call-insertions calls from alignments: it needs --also-align");
     if (o.call_insertions && !o.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
+    o.phase = m.count("phase") > 0;
+    if (o.phase && !o.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
+    if (m.count("phase-min-links")) {
+        const std::string v = m["phase-min-links"];
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoul(v) < 1 || std::stoul(v) > 65535)
+            throw Error("--phase-min-links takes a number from 1 to 65535: not " + v);
+        if (!o.phase) throw Error("--phase-min-links has no meaning without --phase");
+        o.phase_min_links = (uint32_t)std::stoul(v);
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -288,6 +301,9 @@ int map_main(int argc, char **argv)
         fprintf(stderr, "[vgaligner] call-variants: %llu bases tested, %llu calls\n", (unsigned long long)out.n_variant_tested, (unsigned long long)out.n_variant_calls);
     if (o.call_insertions)
         fprintf(stderr, "[vgaligner] call-insertions: %llu sites, %llu longer than 8\n", (unsigned long long)out.n_insertion_sites, (unsigned long long)out.n_insertion_long);
+    if (o.phase)
+        fprintf(stderr, "[vgaligner] phase: %llu heterozygous sites, %llu phase sets, %llu reads kept\n", (unsigned long long)out.n_phase_sites,
+                (unsigned long long)out.n_phase_sets, (unsigned long long)out.n_phase_reads);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -333,7 +349,8 @@ int main(int argc, char **argv)
                         "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]\n"
                         "                                       [--genotype-from support|edit]]\n"
                         "                [--path-edit]\n"
-                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]]\n");
+                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
+                        "                                 [--phase [--phase-min-links 2]]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

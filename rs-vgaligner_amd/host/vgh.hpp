@@ -204,6 +204,12 @@ struct MapOptions {
     // whole table over, 196 bytes per base and context over PCIe, they are added in 64 bits, then vga_insertion_call_table on the
     // first with the summed rows of the sites), and write <out>-insertions.tsv
     bool call_insertions = false;
+    // --phase [--phase-min-links N] (not in the reference; needs call_variants): keep, on the GPU, the pileup list of every
+    // reported alignment (vga_phase_begin), count the read-backed links between the heterozygous sites of <out>-variants.tsv up to
+    // eight sites apart (vga_phase_links; several contexts: each hands its whole store over PCIe, the stores are concatenated,
+    // then vga_phase_links_lists on the first), chain them on the host (vga_phase.hpp: ph_chain) and write <out>-phase.tsv
+    bool phase = false;
+    uint32_t phase_min_links = 2;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -220,6 +226,7 @@ struct MapOutput {
     uint64_t n_chunks = 0, n_devices = 0;
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
+    uint64_t n_phase_sites = 0, n_phase_sets = 0, n_phase_reads = 0;  // heterozygous sites, phase sets and reads kept (MapOptions::phase)
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)

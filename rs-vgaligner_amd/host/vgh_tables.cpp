@@ -3,6 +3,7 @@
 #include "vgh_tables.hpp"
 #include "../csrc/vga_insertion.hpp"
 #include "../csrc/vga_pair_index.hpp"
+#include "../csrc/vga_phase.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -35,6 +36,14 @@ void Counters::pad(const std::vector<size_t> &sizes)
     if (v.size() < sizes.size()) v.resize(sizes.size());
     for (size_t k = 0; k < sizes.size(); k++)
         if (v[k].size() < sizes[k]) v[k].resize(sizes[k], 0);
+}
+
+void PhaseStore::add(const PhaseStore &o)
+{
+    if (words.size() + o.words.size() > PH_MAX_WORDS) throw Error("--phase: the stores of the contexts hold more than 2^32 - 1 words together");
+    const uint32_t shift = (uint32_t)words.size();
+    for (size_t i = 0; i < o.recs.size(); i++) recs.push_back(o.recs[i] + (i % 3 == 0 ? shift : 0u));
+    words.insert(words.end(), o.words.begin(), o.words.end());
 }
 
 bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit; }
@@ -149,6 +158,36 @@ void insertion_write(const Index &ix, const VariantCalls &v, const InsertionCall
         t += '\n';
     }
     if (!out_prefix.empty()) write_file(out_prefix + "-insertions.tsv", t);
+}
+
+// one line per heterozygous site: where it is, the genotype with haplotype a first, the set, the link that joined it (how many
+// sites back, 0 for none) with the reads for and against it, and what the reads show at the site
+void phase_write(const Index &ix, const PhaseLinks &p, uint32_t min_links, MapOutput &out, const std::string &out_prefix)
+{
+    static const char ALLELES[] = "ACGT-";
+    const size_t n = p.pos.size();
+    std::vector<uint32_t> ps(n + 1);
+    std::vector<uint8_t> flip(n + 1), link_d(n + 1);
+    ph_chain(n, p.links.data(), min_links, ps.data(), flip.data(), link_d.data());
+    std::string t = "node\toffset\tgt\tps\tlink\tcis\ttrans\tx_reads\ty_reads\tother_reads\n";
+    uint64_t id = 1;  // the sites come in base order: the node moves forward only
+    out.n_phase_sites = n; out.n_phase_sets = 0; out.n_phase_reads = p.n_reads;
+    for (size_t h = 0; h < n; h++) {
+        const uint64_t at = p.pos[h];
+        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= at) id++;
+        out.n_phase_sets += link_d[h] == 0 ? 1u : 0u;
+        uint64_t cis = 0, trans = 0;
+        if (link_d[h]) {
+            const uint32_t *l = p.links.data() + ((h - link_d[h]) * PH_WINDOW + (link_d[h] - 1u)) * PH_LINK_COLS;
+            cis = (uint64_t)l[0] + l[3]; trans = (uint64_t)l[1] + l[2];
+        }
+        put_u64(t, id); t += '\t'; put_u64(t, at - ix.node_ref[id - 1].seq_idx); t += '\t';
+        t += ALLELES[flip[h] ? p.y[h] : p.x[h]]; t += '|'; t += ALLELES[flip[h] ? p.x[h] : p.y[h]]; t += '\t';
+        put_u64(t, ps[h]); t += '\t'; put_u64(t, link_d[h]); t += '\t'; put_u64(t, cis); t += '\t'; put_u64(t, trans);
+        for (uint32_t c = 0; c < PH_SITE_COLS; c++) { t += '\t'; put_u64(t, p.site_reads[h * PH_SITE_COLS + c]); }
+        t += '\n';
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-phase.tsv", t);
 }
 
 void path_support_write(const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
@@ -269,6 +308,8 @@ void check_aligner(const MapOptions &opt)
     if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
     if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
     if (opt.call_insertions && !opt.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
+    if (opt.phase && !opt.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
+    if (opt.phase && (opt.phase_min_links < 1 || opt.phase_min_links > PH_MIN_LINKS_MAX)) throw Error("--phase-min-links is 1 to 65535");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -290,6 +331,7 @@ void Tables::begin(vga_ctx *ctx) const
     }
     if (piling()) check(ctx, vga_pileup_begin(ctx));
     if (inserting()) check(ctx, vga_insertion_begin(ctx));
+    if (phasing()) check(ctx, vga_phase_begin(ctx));
 }
 
 void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const
@@ -378,6 +420,19 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         t.v = {widen(c, ix_.seq_length * IA_COLS)};
         insertions_.add(t);
     }
+    if (phasing() && call_now) {  // the heterozygous sites of the calls just made, from the context's own store
+        phase_sites();
+        PhaseLinks &p = phase_;
+        check(ctx, vga_phase_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.links.data(), p.site_reads.data(), &p.n_reads));
+    } else if (phasing()) {  // the whole store: the context may be gone before the summed call
+        PhaseStore s;
+        uint64_t n_reads = 0, n_words = 0;
+        check(ctx, vga_phase_read(ctx, nullptr, nullptr, &n_reads, &n_words));
+        s.recs.resize(n_reads * 3 + 1); s.words.resize(n_words + 1);
+        check(ctx, vga_phase_read(ctx, s.recs.data(), s.words.data(), &n_reads, &n_words));
+        s.recs.resize(n_reads * 3); s.words.resize(n_words);
+        phase_store_.add(s);
+    }
     if (piling() && getenv("VGA_TRACE"))
         fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
                 std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -388,6 +443,7 @@ void Tables::end(vga_ctx *ctx) const
 {
     if (coverage()) (void)vga_coverage_end(ctx);
     if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
+    if (phasing()) (void)vga_phase_end(ctx);
     if (piling()) (void)vga_pileup_end(ctx);
     if (inserting()) (void)vga_insertion_end(ctx);
 }
@@ -401,6 +457,20 @@ void Tables::add(const Tables &o)
     edit_.add(o.edit_);
     pileup_.add(o.pileup_);
     insertions_.add(o.insertions_);
+    phase_store_.add(o.phase_store_);
+}
+
+void Tables::phase_sites()
+{
+    PhaseLinks &p = phase_;
+    p.pos.clear(); p.x.clear(); p.y.clear();
+    for (uint64_t j = 0; j < variants_.n_calls; j++) {
+        const uint8_t x = variants_.gt[j] & 7u, y = (variants_.gt[j] >> 3) & 7u;
+        if (x < y) { p.pos.push_back(variants_.pos[j]); p.x.push_back(x); p.y.push_back(y); }
+    }
+    const size_t n = p.pos.size();
+    p.links.assign((n + 1) * PH_LINK_ROW, 0); p.site_reads.assign((n + 1) * PH_SITE_COLS, 0);
+    p.pos.reserve(n + 1); p.x.reserve(n + 1); p.y.reserve(n + 1);
 }
 
 std::vector<uint32_t> Tables::insertion_sites()
@@ -424,6 +494,17 @@ void Tables::call(vga_ctx *ctx)
                                       pos, gt, qual, iq, depth, counts, nt, nc);
     });
     trace_mark("variants called");
+    if (phasing()) {
+        phase_sites();
+        PhaseLinks &p = phase_;
+        std::vector<uint8_t> ref(p.pos.size() + 1);
+        for (size_t h = 0; h < p.pos.size(); h++) ref[h] = ph_ref_of(ix_.seq_fwd[p.pos[h]]);
+        const PhaseStore &s = phase_store_;
+        p.n_reads = s.recs.size() / 3;
+        check(ctx, vga_phase_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
+                                         p.y.data(), ref.data(), p.links.data(), p.site_reads.data()));
+        trace_mark("phase links counted");
+    }
     if (!inserting()) return;
     insertions_.pad({ix_.seq_length * IA_COLS});
     const std::vector<uint32_t> pos = insertion_sites();
@@ -475,6 +556,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
         out.n_variant_tested = variants_.n_tested; out.n_variant_calls = variants_.n_calls;
         if (files) variant_write(ix_, variants_, out_prefix);
         trace_mark("variants written");
+    }
+    if (phasing()) {
+        phase_write(ix_, phase_, opt_.phase_min_links, out, out_prefix);
+        trace_mark("phase written");
     }
     if (inserting()) {
         insertion_write(ix_, variants_, ins_calls_, out, out_prefix);

@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -44,6 +44,19 @@ struct InsertionCalls {
     std::vector<uint64_t> length_reads, seq_reads;  // seq_reads: 8 per site
 };
 
+// The heterozygous sites of VariantCalls in that order, and their links (MapOptions::phase)
+struct PhaseLinks {
+    std::vector<uint32_t> pos;
+    std::vector<uint8_t> x, y;
+    std::vector<uint32_t> links, site_reads;  // 32 and 3 per site
+    uint64_t n_reads = 0;
+};
+// The phase stores of several contexts, concatenated: three words per read (off, n_runs, n_sparse) and the words
+struct PhaseStore {
+    std::vector<uint32_t> recs, words;
+    void add(const PhaseStore &o);
+};
+
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
 struct ReadRows {
     std::string path, edit;
@@ -65,7 +78,8 @@ public:
     bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit); }
     bool piling() const { return opt_.pileup || opt_.call_variants; }
     bool inserting() const { return opt_.call_insertions; }
-    bool any() const { return coverage() || scoring() || piling() || inserting(); }
+    bool phasing() const { return opt_.phase; }
+    bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
     // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
     bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
 
@@ -75,13 +89,14 @@ public:
     // call's result; mark(what): a trace mark after each of the two tables)
     void chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const;
     // What the context has counted and scored so far joins this object.  call_now: the variants are called from the context's own
-    // counters, and the insertions at their sites; otherwise its pileup table and its insertion table are kept for the sum.  (`slot` names the context in the trace.)
+    // counters, and the insertions at their sites, and the heterozygous sites are linked from its own store; otherwise its pileup
+    // table, its insertion table and its whole phase store are kept for the sum.  (`slot` names the context in the trace.)
     void take(vga_ctx *ctx, uint32_t slot, bool call_now);
     // turns the analyses off on a context that stays with the caller
     void end(vga_ctx *ctx) const;
     void add(const Tables &o);
     // the variants of the summed pileup table, and the insertions at their sites from the summed insertion table, called on `ctx`
-    // (any context: its own counters are not touched)
+    // and the links of the heterozygous sites from the concatenated stores (any context: its own counters are not touched)
     void call(vga_ctx *ctx);
     // the TSV files beside the GAF files (out_prefix == "": none) and the fields of `out`
     void write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix);
@@ -98,6 +113,10 @@ private:
     VariantCalls variants_;
     Counters insertions_;  // seq_length x 49; n: alignments, leading insertions (only kept for the sum of several contexts)
     InsertionCalls ins_calls_;
+    PhaseStore phase_store_;  // (only kept for the route of several contexts)
+    PhaseLinks phase_;
+    // the heterozygous variant calls as sites; sizes the tables of phase_
+    void phase_sites();
     // the positions of the variant calls whose insertion state is het or hom; fills ins_calls_.site and sizes its arrays
     std::vector<uint32_t> insertion_sites();
 };
