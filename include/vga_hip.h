@@ -665,6 +665,25 @@ int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *rows_in /
  *                          otherwise h opens a set: ps[h] = h + 1 (its own line among the sites), flip 0, link_d 0.  Haplotype a
  *                          carries flip ? y : x, haplotype b the other allele.  VGA_ERR_ARG for min_links out of range or a NULL
  *                          array with n_sites > 0.
+ *   haplotype tags         which stored reads go with which haplotype of which phase set; integers only.  With ps and flip as
+ *                          vga_phase_chain returns them, site h votes in read r when obs(r, h) <= 1, and its vote is obs xor
+ *                          flip[h]: 0 for haplotype a (which carries flip ? y : x), 1 for haplotype b.  votes_a and votes_b of
+ *                          (r, p) count the votes of the sites with ps[h] = p.  A row {read, ps, votes_a, votes_b} (four uint32)
+ *                          exists for every (r, p) with a vote; rows are ordered by read (the index of the record in the store),
+ *                          then by ps ascending.  The read goes with a when votes_a > votes_b, with b when votes_b > votes_a, and
+ *                          with neither on a tie.  There is no "best set per read" rule: every set a read votes in has its row.
+ *   vga_phase_tags         the rows from the context's own store at the sites pos, x, y (as vga_phase_links takes them) under
+ *                          ps and flip; *n_reads the stored records (may be NULL).  At most cap rows are written and *n_rows, the
+ *                          number there are, is always written: a caller that finds *n_rows > cap asks again with that cap (as
+ *                          with vga_variant_call).  Per tile of reads k_ph_obs, then k_ph_tag (count), k_ph_tag_scan (exclusive
+ *                          scan; the running total goes from tile to tile in a device word) and k_ph_tag (emit): the rows do not
+ *                          depend on the tile size.  VGA_ERR_ARG for everything vga_phase_links refuses, for ps[h] outside 1 ..
+ *                          h + 1, for ps[ps[h] - 1] != ps[h] (the named site must open its set), for flip[h] > 1, for a NULL
+ *                          array with n_sites > 0, a NULL n_rows, and NULL rows with cap > 0.  n_sites = 0 or an empty store:
+ *                          0 rows.  Does not reset.
+ *   vga_phase_tags_lists   the kernel seam, and the route of several contexts: the same from explicit records and words, with
+ *                          every check of vga_phase_links_lists and the ones above; a violation launches nothing and leaves rows
+ *                          and *n_rows as they were.
  * With the store off vga_align_batch does what it did before these calls existed: no k_ph_* launch, no extra allocation. */
 int vga_phase_begin(vga_ctx *ctx);
 int vga_phase_read(vga_ctx *ctx, uint32_t *recs /* n_reads * 3 */, uint32_t *words /* n_words */, uint64_t *n_reads, uint64_t *n_words);
@@ -677,6 +696,11 @@ int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, cons
                           const uint8_t *ref, uint32_t *links /* n_sites * 32 */, uint32_t *site_reads /* n_sites * 3 */);
 int vga_phase_chain(uint64_t n_sites, const uint32_t *links /* n_sites * 32 */, uint32_t min_links, uint32_t *ps, uint8_t *flip,
                     uint8_t *link_d);
+int vga_phase_tags(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos /* n_sites */, const uint8_t *x, const uint8_t *y, const uint32_t *ps,
+                   const uint8_t *flip, uint64_t cap, uint32_t *rows /* cap * 4 */, uint64_t *n_rows, uint64_t *n_reads);
+int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs /* n_reads * 3 */, uint64_t n_words,
+                         const uint32_t *words, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref,
+                         const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows /* cap * 4 */, uint64_t *n_rows);
 
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "vga_variant_call", "vga_variant_call_table",
     "vga_insertion_begin", "vga_insertion_read", "vga_insertion_reset", "vga_insertion_end", "vga_insertion_call", "vga_insertion_call_table",
     "vga_phase_begin", "vga_phase_read", "vga_phase_reset", "vga_phase_end", "vga_phase_links", "vga_phase_links_lists", "vga_phase_chain",
+    "vga_phase_tags", "vga_phase_tags_lists",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -106,6 +107,8 @@ PHASE_WINDOW = 8
 PHASE_MIN_LINKS = 2
 PHASE_MAX_MIN_LINKS = 65535
 PHASE_COLS = 7
+# a row of the haplotype tags: read, ps, votes_a, votes_b
+PHASE_TAG_COLS = 4
 
 
 class VgaError(RuntimeError):
@@ -315,8 +318,11 @@ def load_library():
         L.vga_phase_links.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u32p, u64p]
         L.vga_phase_links_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u32p]
         L.vga_phase_chain.argtypes = [u64, u32p, C.c_uint32, u32p, u8p, u8p]
+        if hasattr(L, "vga_phase_tags"):  # (the haplotype tags came later than the links)
+            L.vga_phase_tags.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u8p, u64, u32p, u64p, u64p]
+            L.vga_phase_tags_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
         for name in ABI_SYMBOLS:
-            if name.startswith("vga_phase_"):
+            if name.startswith("vga_phase_") and hasattr(L, name):
                 getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -944,6 +950,46 @@ class Context:
         self._check(self.L.vga_phase_links_lists(self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), n, _u32p(at), u8(xs), u8(ys), u8(rf),
                                                  _u32p(links), _u32p(sr)))
         return links[:n], sr[:n]
+
+    def _phase_tags(self, call, n, ps, flip, cap):
+        """`call(ps, flip, cap, rows, n_rows)` is one of the two C calls with everything else bound: asked again with room for
+        every row when the first answer holds more rows than it had room for"""
+        sets = np.ascontiguousarray(ps, dtype=np.uint32).reshape(-1)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8).reshape(-1)
+        if len(sets) != n or len(fl) != n:
+            raise VgaError(-1, "phase tags: %d sites, %d ps and %d flip" % (n, len(sets), len(fl)))
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        cap = max(0, int(cap))
+        while True:
+            rows, n_rows = np.zeros((max(1, cap), PHASE_TAG_COLS), dtype=np.uint32), C.c_uint64(0)
+            self._check(call(_u32p(pad(sets)), pad(fl).ctypes.data_as(_P(C.c_uint8)), cap, _u32p(rows), C.byref(n_rows)))
+            if n_rows.value <= cap:
+                return rows[:n_rows.value]
+            cap = int(n_rows.value)
+
+    def phase_tags(self, pos, x, y, ps, flip, cap: int = 1 << 16):
+        """vga_phase_tags: which stored reads of this context go with which haplotype of which phase set, at the sites pos, x, y
+        of phase_links under the ps and flip of phase_chain -> (rows[n, 4] uint32: read (index in the store), ps, votes_a,
+        votes_b, in read order and then by ps; n_reads).  A read goes with a when votes_a > votes_b, with b when votes_b > votes_a.
+        Does not reset."""
+        n, at, (xs, ys) = self._phase_sites(pos, x, y)
+        n_reads = C.c_uint64(0)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        rows = self._phase_tags(lambda sets, fl, cap, rows, n_rows: self.L.vga_phase_tags(self.h, n, _u32p(at), u8(xs), u8(ys), sets, fl, cap, rows, n_rows,
+                                                                                       C.byref(n_reads)), n, ps, flip, cap)
+        return rows, int(n_reads.value)
+
+    def phase_tags_lists(self, recs, words, n_bases, pos, x, y, ref, ps, flip, cap: int = 1 << 16):
+        """vga_phase_tags_lists, the kernel seam: the same from explicit records and words (phase_links_lists) -> rows[n, 4].
+        Needs a context only."""
+        rc = np.ascontiguousarray(recs, dtype=np.uint32).reshape(-1, 3)
+        wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        n, at, (xs, ys, rf) = self._phase_sites(pos, x, y, ref)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=np.uint32)
+        return self._phase_tags(lambda sets, fl, cap, rows, n_rows: self.L.vga_phase_tags_lists(self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)),
+                                                                                             n, _u32p(at), u8(xs), u8(ys), u8(rf), sets, fl, cap, rows, n_rows),
+                                n, ps, flip, cap)
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

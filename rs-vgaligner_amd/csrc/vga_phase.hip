@@ -1,5 +1,6 @@
-// vga_phase.hip -- the read-backed linkage of heterozygous sites: k_ph_keep, k_ph_obs, k_ph_link and the C entry points
-// vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain.  See vga_phase.hpp for the shape.
+// vga_phase.hip -- the read-backed linkage of heterozygous sites and the reads' haplotype tags: k_ph_keep, k_ph_obs, k_ph_link,
+// k_ph_tag, k_ph_tag_scan and the C entry points vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain / _tags /
+// _tags_lists.  See vga_phase.hpp for the shape.
 //
 // Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
 // read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
@@ -146,6 +147,82 @@ __global__ __launch_bounds__(PH_LINK_BLOCK) void k_ph_link(uint32_t n_sites, uin
     }
 }
 
+// One lane per read of the tile, behind k_ph_obs.  The sets come in ascending ps, set s holding the sites order[set_start[s]] ..
+// order[set_start[s + 1] - 1] (a word of order is site << 1 | flip); all of that is wave-uniform, and the 64 bytes a wave loads of
+// one site row are one line.  A site votes where the read shows x or y alone: vote = obs xor flip, 0 for haplotype a.  The two
+// counters of a set live in registers.  EMIT = false counts the sets with a vote into rows_of[read]; EMIT = true finds there the
+// read's first row within the tile (k_ph_tag_scan) and writes its rows at run[0] + that, those below cap only.  No load is under
+// a lane mask: a lane behind the tile's last read takes that read and writes nothing.
+template <bool EMIT>
+__global__ __launch_bounds__(PH_TAG_BLOCK) void k_ph_tag(uint32_t n, uint32_t tile_reads, uint32_t r0, const uint8_t *__restrict__ obs, uint32_t n_sets,
+                                                          const uint32_t *__restrict__ set_start, const uint32_t *__restrict__ set_ps,
+                                                          const uint32_t *__restrict__ order, uint32_t *__restrict__ rows_of,
+                                                          const uint64_t *__restrict__ run, uint64_t cap, uint32_t *__restrict__ rows)
+{
+    const uint32_t i = blockIdx.x * PH_TAG_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t r = live ? i : n - 1u;
+    const uint8_t *col = obs + r;
+    uint64_t at = 0;
+    uint32_t made = 0;
+    if (EMIT) at = run[0] + rows_of[r];
+    uint32_t k = set_start[0];
+    for (uint32_t s = 0; s < n_sets; s++) {
+        const uint32_t end = set_start[s + 1u];
+        uint32_t va = 0, vb = 0;
+#pragma unroll 4
+        for (; k < end; k++) {
+            const uint32_t o = order[k];
+            const uint32_t v = ph_code(col[(size_t)(o >> 1) * tile_reads]) ^ (o & 1u);  // (2 and 3 stay above 1 under the flip)
+            va += v == 0u ? 1u : 0u;
+            vb += v == 1u ? 1u : 0u;
+        }
+        if (va + vb == 0u) continue;
+        if (EMIT) {
+            if (live && at < cap) reinterpret_cast<uint4 *>(rows)[at] = make_uint4(r0 + r, set_ps[s], va, vb);
+            at++;
+        } else
+            made++;
+    }
+    if (!EMIT && live) rows_of[i] = made;
+}
+
+// One workgroup: the exclusive scan of the tile's n row counts, in place, and the running total of the rows of all tiles so far:
+// run[0] = the rows before this tile, run[1] = the rows up to its end.  The kernels of a tag call follow each other on one stream.
+__global__ __launch_bounds__(PH_SCAN_BLOCK) void k_ph_tag_scan(uint32_t n, uint32_t *__restrict__ rows_of, uint64_t *__restrict__ run)
+{
+    __shared__ uint32_t sums[PH_SCAN_BLOCK / 64u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += PH_SCAN_BLOCK) {
+        const uint32_t i = base + tid;
+        const uint32_t v = i < n ? rows_of[i] : 0u;
+        uint32_t s = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t t = __shfl_up(s, d, 64);
+            if (lane >= d) s += t;
+        }
+        if (lane == 63u) sums[wave] = s;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < PH_SCAN_BLOCK / 64u; w++) {
+            const uint32_t t = sums[w];
+            before += w < wave ? t : 0u;
+            all += t;
+        }
+        if (i < n) rows_of[i] = carry + before + s - v;
+        carry += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const uint64_t was = run[1];
+        run[0] = was;
+        run[1] = was + carry;
+    }
+}
+
 }  // namespace
 
 // The store of a context's index while it is on (vga_dev_index::ph: released with the index): the words on the device, the
@@ -274,16 +351,63 @@ struct ph_sites {
 };
 
 // what the kernels rely on: sites that ascend strictly inside the graph, x < y <= D, ref <= other
-int ph_check_sites(vga_ctx *ctx, const char *who, const ph_sites &s, uint64_t n_bases, const uint32_t *links, const uint32_t *site_reads)
+int ph_check_sites(vga_ctx *ctx, const char *who, const ph_sites &s, uint64_t n_bases, bool have_outputs)
 {
     if (s.n > PH_MAX_SITES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu sites, 2^24 at most", who, (unsigned long long)s.n);
-    if (s.n && (!s.pos || !s.x || !s.y || !links || !site_reads)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)s.n);
+    if (s.n && (!s.pos || !s.x || !s.y || !have_outputs)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)s.n);
     for (uint64_t h = 0; h < s.n; h++) {
         if (s.pos[h] >= n_bases) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu at base %u, the graph has %llu", who, (unsigned long long)h, s.pos[h], (unsigned long long)n_bases);
         if (h && s.pos[h] <= s.pos[h - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu does not lie behind the one before it", who, (unsigned long long)h);
         if (!(s.x[h] < s.y[h] && s.y[h] <= PH_ALLELE_DEL))
             return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has alleles %u, %u (x < y <= 4)", who, (unsigned long long)h, s.x[h], s.y[h]);
         if (s.ref && s.ref[h] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has own letter %u (0 .. 4)", who, (unsigned long long)h, s.ref[h]);
+    }
+    return VGA_OK;
+}
+
+// what vga_phase_links_lists and vga_phase_tags_lists check before anything is launched: the sizes, the sites, and every word of
+// every record that a kernel follows
+int ph_check_lists(vga_ctx *ctx, const char *who, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
+                   const ph_sites &s, bool have_outputs)
+{
+    if (n_bases > PH_MAX_SEQ || n_words > PH_MAX_WORDS || n_reads > PH_MAX_WORDS)
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu bases, %llu reads, %llu words: 2^29 bases and 2^32 - 1 reads and words at most", who,
+                             (unsigned long long)n_bases, (unsigned long long)n_reads, (unsigned long long)n_words);
+    const int rc = ph_check_sites(ctx, who, s, n_bases, have_outputs);
+    if (rc != VGA_OK) return rc;
+    if ((s.n && !s.ref) || (n_reads && !recs) || (n_words && !words)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array", who);
+    const ph_rec *rr = (const ph_rec *)recs;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const ph_rec &c = rr[r];
+        if ((uint64_t)c.off + c.n_runs + c.n_sparse > n_words || (c.n_runs & 1u))
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: words %u + %u + %u of %llu, run words in pairs", who, (unsigned long long)r, c.off, c.n_runs,
+                                 c.n_sparse, (unsigned long long)n_words);
+        const uint32_t *ev = words + c.off, *sp = ev + c.n_runs;
+        for (uint32_t i = 0; i < c.n_runs; i += 2) {
+            const uint32_t a = ev[i], b = ev[i + 1];
+            if ((a & 1u) || !(b & 1u) || (b >> 1) <= (a >> 1) || (b >> 1) > n_bases)
+                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: run words %u, %u are no start and end inside %llu bases", who, (unsigned long long)r, a, b,
+                                     (unsigned long long)n_bases);
+        }
+        for (uint32_t i = 0; i < c.n_sparse; i++)
+            if ((sp[i] >> 3) >= n_bases || (sp[i] & 7u) >= PH_COLS)
+                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: sparse word %u (position below %llu, column below 7)", who, (unsigned long long)r, sp[i],
+                                     (unsigned long long)n_bases);
+    }
+    return VGA_OK;
+}
+
+// the sets as vga_phase_chain numbers them: ps[h] names the site that opens the set of h (1-based, at or before h), flip is 0 or 1
+int ph_check_sets(vga_ctx *ctx, const char *who, uint64_t n_sites, const uint32_t *ps, const uint8_t *flip, uint64_t cap, const uint32_t *rows,
+                  const uint64_t *n_rows)
+{
+    if (!n_rows || (cap && !rows)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null output (n_rows always, rows with cap above 0)", who);
+    if (n_sites && (!ps || !flip)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)n_sites);
+    for (uint64_t h = 0; h < n_sites; h++) {
+        if (ps[h] < 1u || ps[h] > h + 1u || ps[ps[h] - 1u] != ps[h])
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu is in set %u: a set is named by the site that opens it, 1 .. %llu here", who, (unsigned long long)h,
+                                 ps[h], (unsigned long long)(h + 1u));
+        if (flip[h] > 1u) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has flip %u (0 or 1)", who, (unsigned long long)h, flip[h]);
     }
     return VGA_OK;
 }
@@ -346,6 +470,105 @@ int ph_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d
     return VGA_OK;
 }
 
+// k_ph_obs, then k_ph_tag (count), k_ph_tag_scan and k_ph_tag (emit) over the n_reads stored reads, tile by tile: the rows of all
+// tiles land in one array in (read, ps) order, the first `cap` of them, and the total in *n_rows.  Everything was checked by the
+// caller.
+int ph_tag_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, const uint32_t *ps, const uint8_t *flip,
+               uint64_t cap, uint32_t *rows, uint64_t *n_rows)
+{
+    hipStream_t st = ctx->stream;
+    vga_timers_reset(ctx);
+    *n_rows = 0;
+    if (s.n == 0 || n_reads == 0) return VGA_OK;
+    const uint32_t H = (uint32_t)s.n;
+    // the sites by set, the sets in ascending ps (a set is named by the site that opens it: its first site), stable by site inside
+    std::vector<uint32_t> set_of(H), host(3 * (size_t)H + 1);
+    uint32_t S = 0;
+    for (uint32_t h = 0; h < H; h++)
+        if (ps[h] == h + 1u) set_of[h] = S++;
+    uint32_t *set_start = host.data(), *set_ps = set_start + S + 1u, *order = set_ps + S;  // S + 1, S and H words
+    std::fill(set_start, set_start + S + 1u, 0u);
+    for (uint32_t h = 0; h < H; h++) set_start[set_of[ps[h] - 1u] + 1u]++;
+    for (uint32_t k = 0; k < S; k++) set_start[k + 1u] += set_start[k];
+    {
+        std::vector<uint32_t> fill(set_start, set_start + S);
+        for (uint32_t h = 0; h < H; h++) {
+            const uint32_t k = set_of[ps[h] - 1u];
+            set_ps[k] = ps[h];
+            order[fill[k]++] = h << 1 | flip[h];
+        }
+    }
+    const size_t host_words = 2 * (size_t)S + 1u + H;
+    const uint32_t T = ph_tile_reads(n_reads, s.n);
+    // no more rows than (read, set) pairs can ever be written
+    const uint64_t room = std::min<uint64_t>(cap, n_reads * (uint64_t)S);
+    vga_dbuf<ph_rec> d_recs;
+    vga_dbuf<uint32_t> d_pos, d_obs, d_sets, d_rows_of, d_rows;
+    vga_dbuf<uint64_t> d_run;
+    vga_dbuf<uint8_t> d_bytes;  // x, y, ref
+    const size_t obs_words = (size_t)H * T / 4u;
+    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
+    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve(H));
+    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3));
+    VGA_HIP_CHECK_OOM(ctx, d_obs.reserve(obs_words));
+    VGA_HIP_CHECK_OOM(ctx, d_sets.reserve(host_words));
+    VGA_HIP_CHECK_OOM(ctx, d_rows_of.reserve(T));
+    VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)room * PH_TAG_COLS + PH_TAG_COLS));
+    VGA_HIP_CHECK_OOM(ctx, d_run.reserve(2));
+    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H;
+    const uint32_t *d_set_start = d_sets.p, *d_set_ps = d_sets.p + S + 1u, *d_order = d_sets.p + 2 * (size_t)S + 1u;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_sets.p, host.data(), host_words * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_run.p, 0, 16, st));
+    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
+        const dim3 grid((n + PH_TAG_BLOCK - 1u) / PH_TAG_BLOCK);
+        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_obs.p, 0, obs_words * 4, st));
+        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
+        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_ph_tag", (uint64_t)H * n, st);
+        hipLaunchKernelGGL(k_ph_tag<false>, grid, dim3(PH_TAG_BLOCK), 0, st, n, T, (uint32_t)r0, (const uint8_t *)d_obs.p, S, d_set_start, d_set_ps, d_order,
+                           d_rows_of.p, (const uint64_t *)d_run.p, room, d_rows.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_ph_tag_scan", (uint64_t)n * 8, st);
+        hipLaunchKernelGGL(k_ph_tag_scan, dim3(1), dim3(PH_SCAN_BLOCK), 0, st, n, d_rows_of.p, d_run.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_ph_tag", (uint64_t)H * n, st);
+        hipLaunchKernelGGL(k_ph_tag<true>, grid, dim3(PH_TAG_BLOCK), 0, st, n, T, (uint32_t)r0, (const uint8_t *)d_obs.p, S, d_set_start, d_set_ps, d_order,
+                           d_rows_of.p, (const uint64_t *)d_run.p, room, d_rows.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+    }
+    uint64_t run[2] = {0, 0};
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(run, d_run.p, 16, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    const uint64_t written = std::min<uint64_t>(run[1], room);
+    if (written) {
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(rows, d_rows.p, (size_t)written * PH_TAG_COLS * 4, hipMemcpyDeviceToHost, st));
+        VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    *n_rows = run[1];
+    vga_timers_collect(ctx);
+    return VGA_OK;
+}
+
+// the words of explicit lists on the device, behind whatever the context's stream still runs
+int ph_upload_words(vga_ctx *ctx, uint64_t n_words, const uint32_t *words, vga_dbuf<uint32_t> &d_words)
+{
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    VGA_HIP_CHECK_OOM(ctx, d_words.reserve((size_t)n_words + 1));
+    if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    return VGA_OK;
+}
+
 }  // namespace
 
 extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, uint32_t *links, uint32_t *site_reads,
@@ -355,7 +578,7 @@ extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *p
     ph_state *ph = ph_active(ctx);
     if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_links: the store is off (vga_phase_begin)");
     ph_sites s = {n_sites, pos, x, y, nullptr};
-    const int rc = ph_check_sites(ctx, "vga_phase_links", s, ctx->index.seq_length, links, site_reads);
+    const int rc = ph_check_sites(ctx, "vga_phase_links", s, ctx->index.seq_length, links && site_reads);
     if (rc != VGA_OK) return rc;
     std::vector<uint8_t> ref(n_sites + 1);
     for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
@@ -371,39 +594,52 @@ extern "C" int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_
                                      uint32_t *site_reads)
 {
     if (!ctx) return VGA_ERR_ARG;
-    const char *who = "vga_phase_links_lists";
-    if (n_bases > PH_MAX_SEQ || n_words > PH_MAX_WORDS || n_reads > PH_MAX_WORDS)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu bases, %llu reads, %llu words: 2^29 bases and 2^32 - 1 reads and words at most", who,
-                             (unsigned long long)n_bases, (unsigned long long)n_reads, (unsigned long long)n_words);
     const ph_sites s = {n_sites, pos, x, y, ref};
-    const int rc = ph_check_sites(ctx, who, s, n_bases, links, site_reads);
+    const int rc = ph_check_lists(ctx, "vga_phase_links_lists", n_bases, n_reads, recs, n_words, words, s, links && site_reads);
     if (rc != VGA_OK) return rc;
-    if ((n_sites && !ref) || (n_reads && !recs) || (n_words && !words)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array", who);
     const ph_rec *rr = (const ph_rec *)recs;
-    for (uint64_t r = 0; r < n_reads; r++) {
-        const ph_rec &c = rr[r];
-        if ((uint64_t)c.off + c.n_runs + c.n_sparse > n_words || (c.n_runs & 1u))
-            return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: words %u + %u + %u of %llu, run words in pairs", who, (unsigned long long)r, c.off, c.n_runs,
-                                 c.n_sparse, (unsigned long long)n_words);
-        const uint32_t *ev = words + c.off, *sp = ev + c.n_runs;
-        for (uint32_t i = 0; i < c.n_runs; i += 2) {
-            const uint32_t a = ev[i], b = ev[i + 1];
-            if ((a & 1u) || !(b & 1u) || (b >> 1) <= (a >> 1) || (b >> 1) > n_bases)
-                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: run words %u, %u are no start and end inside %llu bases", who, (unsigned long long)r, a, b,
-                                     (unsigned long long)n_bases);
-        }
-        for (uint32_t i = 0; i < c.n_sparse; i++)
-            if ((sp[i] >> 3) >= n_bases || (sp[i] & 7u) >= PH_COLS)
-                return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu: sparse word %u (position below %llu, column below 7)", who, (unsigned long long)r, sp[i],
-                                     (unsigned long long)n_bases);
-    }
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     vga_dbuf<uint32_t> d_words;
-    VGA_HIP_CHECK_OOM(ctx, d_words.reserve((size_t)n_words + 1));
-    if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int up = ph_upload_words(ctx, n_words, words, d_words);
+    if (up != VGA_OK) return up;
     return ph_run(ctx, rr, n_reads, d_words.p, s, links, site_reads);
+}
+
+extern "C" int vga_phase_tags(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps, const uint8_t *flip,
+                              uint64_t cap, uint32_t *rows, uint64_t *n_rows, uint64_t *n_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    ph_state *ph = ph_active(ctx);
+    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_tags: the store is off (vga_phase_begin)");
+    ph_sites s = {n_sites, pos, x, y, nullptr};
+    int rc = ph_check_sites(ctx, "vga_phase_tags", s, ctx->index.seq_length, true);
+    if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_phase_tags", n_sites, ps, flip, cap, rows, n_rows);
+    if (rc != VGA_OK) return rc;
+    std::vector<uint8_t> ref(n_sites + 1);
+    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
+    s.ref = ref.data();
+    if (n_reads) *n_reads = ph->recs.size();
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    return ph_tag_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, ps, flip, cap, rows, n_rows);
+}
+
+extern "C" int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
+                                    uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref, const uint32_t *ps,
+                                    const uint8_t *flip, uint64_t cap, uint32_t *rows, uint64_t *n_rows)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const ph_sites s = {n_sites, pos, x, y, ref};
+    int rc = ph_check_lists(ctx, "vga_phase_tags_lists", n_bases, n_reads, recs, n_words, words, s, true);
+    if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_phase_tags_lists", n_sites, ps, flip, cap, rows, n_rows);
+    if (rc != VGA_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    vga_dbuf<uint32_t> d_words;
+    const int up = ph_upload_words(ctx, n_words, words, d_words);
+    if (up != VGA_OK) return up;
+    return ph_tag_run(ctx, (const ph_rec *)recs, n_reads, d_words.p, s, ps, flip, cap, rows, n_rows);
 }
 
 extern "C" int vga_phase_chain(uint64_t n_sites, const uint32_t *links, uint32_t min_links, uint32_t *ps, uint8_t *flip, uint8_t *link_d)

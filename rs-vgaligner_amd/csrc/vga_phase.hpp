@@ -1,5 +1,5 @@
 // vga_phase.hpp -- which alleles of the heterozygous variant calls travel together on the reads (vga_phase.hip), as the pileup
-// and the host see it.
+// and the host see it, and which stored reads go with which haplotype of the sets the chain forms (k_ph_tag, k_ph_tag_scan).
 //
 // Nothing in the reference stands behind this.  The variant call (vga_variant.hpp) reports independent diploid sites; a read of
 // 10 kbp crosses many of them, so the linkage is in the alignments.  The sites are known only once the last read has been piled
@@ -8,6 +8,8 @@
 // into a grow-only store of the context; vga_phase_links then runs k_ph_obs (what each stored read shows at each site) and
 // k_ph_link (the pair counts of sites up to PH_WINDOW apart) over tiles of reads.  The measure is defined on the alignments GAF
 // and the rows of <out>-variants.tsv alone (tests/phase_ref.py recomputes it).
+// vga_phase_tags runs k_ph_obs again and, behind it, k_ph_tag (count), k_ph_tag_scan and k_ph_tag (emit): one row per (read, set)
+// in which a site votes, the votes for haplotype a and for haplotype b (tests/haplotag_ref.py recomputes them).
 //
 // The constants, the word formats and the chain rule are shared by host and device (and read by tests/test_phase_cpu.py).
 #pragma once
@@ -58,6 +60,11 @@ static inline uint8_t ph_ref_of(char c)
 #define PH_TILE_BYTES (64ull << 20)
 #define PH_STORE_WORDS0 (1ull << 20)
 #define PH_LINK_BLOCK 256u
+// the haplotype tags (vga_phase_tags): a row is read, ps, votes_a, votes_b; the threads of k_ph_tag's workgroup (a read per lane)
+// and of k_ph_tag_scan's one workgroup
+#define PH_TAG_COLS 4u
+#define PH_TAG_BLOCK 64u
+#define PH_SCAN_BLOCK 1024u
 
 // The chain, integer-only: the one definition (vga_phase_chain exports it, Tables::write prints from it).  links: n x 8 x 4.
 // For h in order the smallest d in 1 .. min(PH_WINDOW, h) whose link[h - d][d - 1] has cis = l[0] + l[3] and trans = l[1] + l[2]

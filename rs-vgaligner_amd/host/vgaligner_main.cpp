@@ -70,7 +70,10 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: the read-backed links between the heterozygous sites --call-variants reports,
                           // counted on the GPU, and the phase chain on them (one TSV file); --phase-min-links N: the reads by which
                           // cis and trans must differ for a link to join two sites (2, 1..65535)
-                          {"", "--phase", false, "phase"}, {"", "--phase-min-links", true, "phase-min-links"}};
+                          {"", "--phase", false, "phase"}, {"", "--phase-min-links", true, "phase-min-links"},
+                          // not in the reference: which kept reads go with which haplotype of which phase set of --phase, counted
+                          // on the GPU (one TSV file, a row per read and set)
+                          {"", "--haplotag", false, "haplotag"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -223,6 +226,8 @@ int map_main(int argc, char **argv)
         if (!o.phase) throw Error("--phase-min-links has no meaning without --phase");
         o.phase_min_links = (uint32_t)std::stoul(v);
     }
+    o.haplotag = m.count("haplotag") > 0;
+    if (o.haplotag && !o.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -304,6 +309,10 @@ int map_main(int argc, char **argv)
     if (o.phase)
         fprintf(stderr, "[vgaligner] phase: %llu heterozygous sites, %llu phase sets, %llu reads kept\n", (unsigned long long)out.n_phase_sites,
                 (unsigned long long)out.n_phase_sets, (unsigned long long)out.n_phase_reads);
+    if (o.haplotag)
+        fprintf(stderr, "[vgaligner] haplotag: %llu rows of %llu reads: %llu a, %llu b, %llu undecided\n", (unsigned long long)out.n_haplotag_rows,
+                (unsigned long long)out.n_phase_reads, (unsigned long long)out.n_haplotag_a, (unsigned long long)out.n_haplotag_b,
+                (unsigned long long)out.n_haplotag_tied);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -350,7 +359,7 @@ int main(int argc, char **argv)
                         "                                       [--genotype-from support|edit]]\n"
                         "                [--path-edit]\n"
                         "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
-                        "                                 [--phase [--phase-min-links 2]]]\n");
+                        "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -210,6 +210,10 @@ struct MapOptions {
     // then vga_phase_links_lists on the first), chain them on the host (vga_phase.hpp: ph_chain) and write <out>-phase.tsv
     bool phase = false;
     uint32_t phase_min_links = 2;
+    // --haplotag (not in the reference; needs phase): per kept read and phase set the sites that vote for haplotype a and for
+    // haplotype b of <out>-phase.tsv, counted on the GPU from the same store (vga_phase_tags; several contexts: vga_phase_tags_lists
+    // on the first, from the concatenated stores), and write <out>-haplotag.tsv with the reads numbered as in the input file
+    bool haplotag = false;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -227,6 +231,7 @@ struct MapOutput {
     uint64_t n_pileup = 0, n_leading_ins = 0;  // alignments counted into the pileup and their insertions before any base (MapOptions::pileup)
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
     uint64_t n_phase_sites = 0, n_phase_sets = 0, n_phase_reads = 0;  // heterozygous sites, phase sets and reads kept (MapOptions::phase)
+    uint64_t n_haplotag_rows = 0, n_haplotag_a = 0, n_haplotag_b = 0, n_haplotag_tied = 0;  // rows and their haplotypes (MapOptions::haplotag)
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)

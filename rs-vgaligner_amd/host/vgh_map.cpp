@@ -442,7 +442,7 @@ struct ChunkHooks {
 };
 
 // anchors -> chains -> (alignments) of reads [b, e) on one context; the GAF text of exactly those reads
-void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &inputs, uint64_t b0, uint64_t e0, const MapOptions &opt, const Tables &tables,
+void map_chunk(vga_ctx *ctx, const Index &ix, const std::vector<QuerySequence> &inputs, uint64_t b0, uint64_t e0, const MapOptions &opt, Tables &tables,
                ChunkOut &out, const ChunkHooks &hooks, unsigned T)
 {
     const uint64_t n = e0 - b0;

@@ -46,6 +46,13 @@ void PhaseStore::add(const PhaseStore &o)
     words.insert(words.end(), o.words.begin(), o.words.end());
 }
 
+void PhaseLinks::chain(uint32_t min_links)
+{
+    const size_t n = pos.size();
+    ps.assign(n + 1, 0); flip.assign(n + 1, 0); link_d.assign(n + 1, 0);
+    ph_chain(n, links.data(), min_links, ps.data(), flip.data(), link_d.data());
+}
+
 bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit; }
 
 namespace {
@@ -73,6 +80,23 @@ void variant_fetch(vga_ctx *ctx, VariantCalls &v, F call)
         if (v.n_calls <= cap) break;
         cap = v.n_calls;
     }
+}
+
+// `call(cap, rows, &n_rows)` is one of the two library calls with everything before cap bound: asked again when the first answer
+// holds more rows than it had room for.  The store must hold exactly the reads whose numbers were noted.
+template <typename F>
+void tags_fetch(vga_ctx *ctx, PhaseTags &t, uint64_t n_stored, F call)
+{
+    if (t.read_ids.size() != n_stored)
+        throw Error("--haplotag: the phase store holds " + std::to_string(n_stored) + " reads, and " + std::to_string(t.read_ids.size()) + " reads were noted as kept");
+    uint64_t cap = std::max<uint64_t>(4096, 4 * n_stored);
+    for (;;) {
+        t.rows.resize(cap * PH_TAG_COLS);
+        check(ctx, call(cap, t.rows.data(), &t.n_rows));
+        if (t.n_rows <= cap) break;
+        cap = t.n_rows;
+    }
+    t.rows.resize(t.n_rows * PH_TAG_COLS);
 }
 
 // ---- the writers.  Each gets its table padded to the sizes it indexes.
@@ -162,13 +186,13 @@ void insertion_write(const Index &ix, const VariantCalls &v, const InsertionCall
 
 // one line per heterozygous site: where it is, the genotype with haplotype a first, the set, the link that joined it (how many
 // sites back, 0 for none) with the reads for and against it, and what the reads show at the site
-void phase_write(const Index &ix, const PhaseLinks &p, uint32_t min_links, MapOutput &out, const std::string &out_prefix)
+void phase_write(const Index &ix, PhaseLinks &p, uint32_t min_links, MapOutput &out, const std::string &out_prefix)
 {
     static const char ALLELES[] = "ACGT-";
     const size_t n = p.pos.size();
-    std::vector<uint32_t> ps(n + 1);
-    std::vector<uint8_t> flip(n + 1), link_d(n + 1);
-    ph_chain(n, p.links.data(), min_links, ps.data(), flip.data(), link_d.data());
+    p.chain(min_links);
+    const std::vector<uint32_t> &ps = p.ps;
+    const std::vector<uint8_t> &flip = p.flip, &link_d = p.link_d;
     std::string t = "node\toffset\tgt\tps\tlink\tcis\ttrans\tx_reads\ty_reads\tother_reads\n";
     uint64_t id = 1;  // the sites come in base order: the node moves forward only
     out.n_phase_sites = n; out.n_phase_sets = 0; out.n_phase_reads = p.n_reads;
@@ -188,6 +212,27 @@ void phase_write(const Index &ix, const PhaseLinks &p, uint32_t min_links, MapOu
         t += '\n';
     }
     if (!out_prefix.empty()) write_file(out_prefix + "-phase.tsv", t);
+}
+
+// one line per (kept read, phase set) in which a site votes: the read as the input file numbers it, the set as <out>-phase.tsv
+// numbers it, the haplotype with more votes (. on a tie) and the votes; by read, then by set.  The rows come in store order, which
+// is read order unless several contexts kept the reads.
+void haplotag_write(const PhaseTags &t, MapOutput &out, const std::string &out_prefix)
+{
+    std::vector<uint64_t> at(t.n_rows);
+    for (uint64_t i = 0; i < t.n_rows; i++) at[i] = i;
+    auto read_of = [&](uint64_t i) { return t.read_ids[t.rows[i * PH_TAG_COLS]]; };
+    auto before = [&](uint64_t a, uint64_t b) { return read_of(a) < read_of(b); };
+    if (!std::is_sorted(at.begin(), at.end(), before)) std::stable_sort(at.begin(), at.end(), before);
+    std::string s = "read\tps\thap\tvotes_a\tvotes_b\n";
+    out.n_haplotag_rows = t.n_rows; out.n_haplotag_a = out.n_haplotag_b = out.n_haplotag_tied = 0;
+    for (uint64_t i : at) {
+        const uint32_t *r = t.rows.data() + i * PH_TAG_COLS;
+        const char hap = r[2] > r[3] ? 'a' : r[3] > r[2] ? 'b' : '.';
+        (hap == 'a' ? out.n_haplotag_a : hap == 'b' ? out.n_haplotag_b : out.n_haplotag_tied)++;
+        put_u64(s, read_of(i)); s += '\t'; put_u64(s, r[1]); s += '\t'; s += hap; s += '\t'; put_u64(s, r[2]); s += '\t'; put_u64(s, r[3]); s += '\n';
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-haplotag.tsv", s);
 }
 
 void path_support_write(const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
@@ -310,6 +355,7 @@ void check_aligner(const MapOptions &opt)
     if (opt.call_insertions && !opt.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
     if (opt.phase && !opt.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
     if (opt.phase && (opt.phase_min_links < 1 || opt.phase_min_links > PH_MIN_LINKS_MAX)) throw Error("--phase-min-links is 1 to 65535");
+    if (opt.haplotag && !opt.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -334,9 +380,12 @@ void Tables::begin(vga_ctx *ctx) const
     if (phasing()) check(ctx, vga_phase_begin(ctx));
 }
 
-void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const
+void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark)
 {
     const size_t np = opt_.paths.n_paths();
+    if (tagging())  // the store keeps the reported alignments of the call in read order
+        for (uint64_t r = 0; r < n; r++)
+            if (aligned[r]) tags_.read_ids.push_back(b0 + r);
     // one line per pair (aligned read, path) that keep(at) lets through: the read, the path, then the pair's value in each matrix
     auto put_rows = [&](std::string &dst, std::initializer_list<const std::vector<uint32_t> *> matrices, auto keep) {
         for (uint64_t r = 0; r < n; r++)
@@ -424,6 +473,12 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         phase_sites();
         PhaseLinks &p = phase_;
         check(ctx, vga_phase_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.links.data(), p.site_reads.data(), &p.n_reads));
+        if (tagging()) {
+            p.chain(opt_.phase_min_links);
+            tags_fetch(ctx, tags_, p.n_reads, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
+                return vga_phase_tags(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(), p.flip.data(), cap, rows, n_rows, nullptr);
+            });
+        }
     } else if (phasing()) {  // the whole store: the context may be gone before the summed call
         PhaseStore s;
         uint64_t n_reads = 0, n_words = 0;
@@ -431,6 +486,9 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         s.recs.resize(n_reads * 3 + 1); s.words.resize(n_words + 1);
         check(ctx, vga_phase_read(ctx, s.recs.data(), s.words.data(), &n_reads, &n_words));
         s.recs.resize(n_reads * 3); s.words.resize(n_words);
+        if (tagging() && tags_.read_ids.size() != n_reads)
+            throw Error("--haplotag: the phase store of slot " + std::to_string(slot) + " holds " + std::to_string(n_reads) + " reads, and " +
+                        std::to_string(tags_.read_ids.size()) + " reads were noted as kept");
         phase_store_.add(s);
     }
     if (piling() && getenv("VGA_TRACE"))
@@ -458,6 +516,7 @@ void Tables::add(const Tables &o)
     pileup_.add(o.pileup_);
     insertions_.add(o.insertions_);
     phase_store_.add(o.phase_store_);
+    tags_.read_ids.insert(tags_.read_ids.end(), o.tags_.read_ids.begin(), o.tags_.read_ids.end());  // (in the order of the records)
 }
 
 void Tables::phase_sites()
@@ -504,6 +563,14 @@ void Tables::call(vga_ctx *ctx)
         check(ctx, vga_phase_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
                                          p.y.data(), ref.data(), p.links.data(), p.site_reads.data()));
         trace_mark("phase links counted");
+        if (tagging()) {
+            p.chain(opt_.phase_min_links);
+            tags_fetch(ctx, tags_, p.n_reads, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
+                return vga_phase_tags_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
+                                            p.y.data(), ref.data(), p.ps.data(), p.flip.data(), cap, rows, n_rows);
+            });
+            trace_mark("reads tagged");
+        }
     }
     if (!inserting()) return;
     insertions_.pad({ix_.seq_length * IA_COLS});
@@ -560,6 +627,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
     if (phasing()) {
         phase_write(ix_, phase_, opt_.phase_min_links, out, out_prefix);
         trace_mark("phase written");
+        if (tagging()) {
+            haplotag_write(tags_, out, out_prefix);
+            trace_mark("haplotags written");
+        }
     }
     if (inserting()) {
         insertion_write(ix_, variants_, ins_calls_, out, out_prefix);

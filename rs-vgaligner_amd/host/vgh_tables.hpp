@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -50,11 +50,22 @@ struct PhaseLinks {
     std::vector<uint8_t> x, y;
     std::vector<uint32_t> links, site_reads;  // 32 and 3 per site
     uint64_t n_reads = 0;
+    // the chain on the links (ph_chain), per site
+    std::vector<uint32_t> ps;
+    std::vector<uint8_t> flip, link_d;
+    void chain(uint32_t min_links);
 };
 // The phase stores of several contexts, concatenated: three words per read (off, n_runs, n_sparse) and the words
 struct PhaseStore {
     std::vector<uint32_t> recs, words;
     void add(const PhaseStore &o);
+};
+// The number in the input file of every kept read, in store order, and the haplotype tags: four words per row (read, ps, votes_a,
+// votes_b), the read an index into the store until Tables::write numbers it by the input file (MapOptions::haplotag)
+struct PhaseTags {
+    std::vector<uint64_t> read_ids;
+    std::vector<uint32_t> rows;
+    uint64_t n_rows = 0;
 };
 
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
@@ -79,6 +90,7 @@ public:
     bool piling() const { return opt_.pileup || opt_.call_variants; }
     bool inserting() const { return opt_.call_insertions; }
     bool phasing() const { return opt_.phase; }
+    bool tagging() const { return opt_.haplotag; }
     bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
     // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
     bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
@@ -86,17 +98,18 @@ public:
     // turns the analyses on, on a context that holds the index
     void begin(vga_ctx *ctx) const;
     // the rows of reads [b0, b0 + n), the most recent vga_align_batch of ctx, while the context still holds them (`aligned`: of that
-    // call's result; mark(what): a trace mark after each of the two tables)
-    void chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark) const;
+    // call's result; mark(what): a trace mark after each of the two tables).  The reads of the call that the phase store has kept
+    // are noted by their number.
+    void chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark);
     // What the context has counted and scored so far joins this object.  call_now: the variants are called from the context's own
-    // counters, and the insertions at their sites, and the heterozygous sites are linked from its own store; otherwise its pileup
+    // counters, and the insertions at their sites, and the heterozygous sites are linked and the reads tagged from its own store; otherwise its pileup
     // table, its insertion table and its whole phase store are kept for the sum.  (`slot` names the context in the trace.)
     void take(vga_ctx *ctx, uint32_t slot, bool call_now);
     // turns the analyses off on a context that stays with the caller
     void end(vga_ctx *ctx) const;
     void add(const Tables &o);
     // the variants of the summed pileup table, and the insertions at their sites from the summed insertion table, called on `ctx`
-    // and the links of the heterozygous sites from the concatenated stores (any context: its own counters are not touched)
+    // and the links of the heterozygous sites and the reads' tags from the concatenated stores (any context: its own counters are not touched)
     void call(vga_ctx *ctx);
     // the TSV files beside the GAF files (out_prefix == "": none) and the fields of `out`
     void write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix);
@@ -115,6 +128,7 @@ private:
     InsertionCalls ins_calls_;
     PhaseStore phase_store_;  // (only kept for the route of several contexts)
     PhaseLinks phase_;
+    PhaseTags tags_;  // (read_ids: of this context's store, then of the concatenated stores)
     // the heterozygous variant calls as sites; sizes the tables of phase_
     void phase_sites();
     // the positions of the variant calls whose insertion state is het or hom; fills ins_calls_.site and sizes its arrays
