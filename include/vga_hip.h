@@ -702,6 +702,58 @@ int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const
                          const uint32_t *words, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref,
                          const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows /* cap * 4 */, uint64_t *n_rows);
 
+/* ---- haplotype counts: what the reads of each haplotype of a phase set show at every reported call ----------
+ * Stands in for nothing in the reference.  The consumer of the haplotype tags: per phase set and per reported call inside the
+ * set's span, what the reads tagged a show there and what the reads tagged b show there, and a haploid call on each.  Integers
+ * only; defined on the alignments GAF, the node starts, the graph's letters, the rows of <out>-variants.tsv and the chain's ps and
+ * flip alone (tests/haplotype_calls_ref.py recomputes it).
+ *   calls        C graph bases cpos[0] < cpos[1] < .. (the rows of <out>-variants.tsv) and cref[c], the base's own letter: 0 .. 3
+ *                for A C G T, 4 for anything else.  The sites pos, x, y with ps and flip are those of vga_phase_tags; they need not
+ *                be a subset of the calls.
+ *   shows        read r shows column k at base p (0 .. 3 A C G T, 4 other, 5 deleted, 6 inserts behind it) when it has a sparse
+ *                word p << 3 | k, or, for k = cref (0 .. 4), when one of its runs [start, end) covers p.  A read shows a column at
+ *                a base at most once, however often it consumes the base (a self-loop), and may show several columns there:
+ *                these are counts of reads, not of events, and can lie below the pileup's on a base one read consumes twice.
+ *   tag          tag(r, S) is a when votes_a > votes_b of the haplotag row (r, S), b when votes_b > votes_a; with a tie or no
+ *                row there is none.  The rule of vga_phase_tags, on the same observation tile (k_ph_obs).
+ *   jobs         first[S] and last[S] are the smallest and largest pos of the sites of set S.  A job (c, S) for every call with
+ *                first[S] <= cpos[c] <= last[S] -- for every set: a set of one site has the one job at its own base if that base
+ *                is a call.  Ordered by c, then by ps ascending; J is their number.
+ *   counts       row j = (c, S) is 16 uint32: c, ps, a[0 .. 6], b[0 .. 6]; a[k] the kept reads with tag(r, S) = a that show
+ *                column k at cpos[c], b[k] the same for b.
+ *   haploid call of seven counts n, obs = n[0] + .. + n[5]: "." for obs = 0; else the first maximum of n[A], n[C], n[G], n[T],
+ *                n[del] in the order A < C < G < T < D, which must hold 2 n > obs, else "?"; "+" is appended when obs > 0 and
+ *                2 n[6] > obs.  No parameters: the strict majority is a choice, not a measurement.
+ *   vga_haplotype_counts        the rows from the context's own store and the letters of its index; *n_reads the stored records
+ *                               (may be NULL).  *n_rows = J is always written; with cap < J nothing is launched and no row is
+ *                               written, and the caller asks again.  Per tile of reads k_ph_obs, k_hc_tags (a byte per set and
+ *                               read), k_hc_cols (a byte per call and read) and k_hc_count (a workgroup per job); the tile's read
+ *                               count is a multiple of 64 sized from 64 MiB and n_sites + sets + n_calls, VGA_PHASE_READ_TILE
+ *                               overrides it, and the rows do not depend on it.  VGA_ERR_ARG for everything vga_phase_tags
+ *                               refuses, for cpos not strictly ascending or not inside the graph, and for a NULL array with a
+ *                               non-zero count; VGA_ERR_UNSUPPORTED for C or J above 2^24.  C = 0, n_sites = 0 or an empty
+ *                               store: 0 rows.  Does not reset the store.
+ *   vga_haplotype_counts_lists  the kernel seam, and the route of several contexts: the same from explicit records and words on
+ *                               a graph of n_bases bases, with every check of vga_phase_tags_lists (the same code) and, on top,
+ *                               cref <= 4; a violation is VGA_ERR_ARG, launches nothing and leaves rows and *n_rows as they
+ *                               were.  Needs a context only.
+ *   vga_haplotype_jobs          no context, on the host: the one definition of the job rule (csrc/vga_hapcall.hpp).  *n_jobs = J
+ *                               always; the first cap jobs as pairs (c, ps).  VGA_ERR_ARG for cpos or pos not strictly ascending,
+ *                               for a ps vga_phase_tags refuses, and for a NULL array it needs.
+ *   vga_haplotype_call          no context: the one definition of the haploid call.  counts: 7; text: 3 bytes, "A" "C" "G" "T"
+ *                               "-" "?" or ".", then "+" or nothing, then 0.
+ * Without these calls nothing changes: no k_hc_* launch, no extra allocation. */
+int vga_haplotype_counts(vga_ctx *ctx, uint64_t n_calls, const uint32_t *cpos /* n_calls */, uint64_t n_sites, const uint32_t *pos,
+                         const uint8_t *x, const uint8_t *y, const uint32_t *ps, const uint8_t *flip, uint64_t cap,
+                         uint32_t *rows /* cap * 16 */, uint64_t *n_rows, uint64_t *n_reads);
+int vga_haplotype_counts_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs /* n_reads * 3 */, uint64_t n_words,
+                               const uint32_t *words, uint64_t n_calls, const uint32_t *cpos, const uint8_t *cref, uint64_t n_sites,
+                               const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref, const uint32_t *ps,
+                               const uint8_t *flip, uint64_t cap, uint32_t *rows /* cap * 16 */, uint64_t *n_rows);
+int vga_haplotype_jobs(uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites, const uint32_t *pos, const uint32_t *ps, uint64_t cap,
+                       uint32_t *jobs /* cap * 2 */, uint64_t *n_jobs);
+int vga_haplotype_call(const uint32_t *counts /* 7 */, char *text /* 3 */);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "vga_insertion_begin", "vga_insertion_read", "vga_insertion_reset", "vga_insertion_end", "vga_insertion_call", "vga_insertion_call_table",
     "vga_phase_begin", "vga_phase_read", "vga_phase_reset", "vga_phase_end", "vga_phase_links", "vga_phase_links_lists", "vga_phase_chain",
     "vga_phase_tags", "vga_phase_tags_lists",
+    "vga_haplotype_counts", "vga_haplotype_counts_lists", "vga_haplotype_jobs", "vga_haplotype_call",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -109,6 +110,10 @@ PHASE_MAX_MIN_LINKS = 65535
 PHASE_COLS = 7
 # a row of the haplotype tags: read, ps, votes_a, votes_b
 PHASE_TAG_COLS = 4
+# a row of the haplotype counts (csrc/vga_hapcall.hpp): c, ps, a[0 .. 6], b[0 .. 6]; the calls and the jobs of one call at most
+HAPLOTYPE_ROW = 16
+HAPLOTYPE_MAX_CALLS = 1 << 24
+HAPLOTYPE_MAX_JOBS = 1 << 24
 
 
 class VgaError(RuntimeError):
@@ -321,8 +326,13 @@ def load_library():
         if hasattr(L, "vga_phase_tags"):  # (the haplotype tags came later than the links)
             L.vga_phase_tags.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u8p, u64, u32p, u64p, u64p]
             L.vga_phase_tags_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
+        if hasattr(L, "vga_haplotype_counts"):  # (the haplotype counts came later than the tags)
+            L.vga_haplotype_counts.argtypes = [vp, u64, u32p, u64, u32p, u8p, u8p, u32p, u8p, u64, u32p, u64p, u64p]
+            L.vga_haplotype_counts_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
+            L.vga_haplotype_jobs.argtypes = [u64, u32p, u64, u32p, u32p, u64, u32p, u64p]
+            L.vga_haplotype_call.argtypes = [u32p, C.c_char_p]
         for name in ABI_SYMBOLS:
-            if name.startswith("vga_phase_") and hasattr(L, name):
+            if name.startswith(("vga_phase_", "vga_haplotype_")) and hasattr(L, name):
                 getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -414,6 +424,39 @@ def phase_chain(links, min_links: int = PHASE_MIN_LINKS):
     if rc != VGA_OK:
         raise VgaError(rc, "phase_chain: min_links %r is 1 to %d" % (min_links, PHASE_MAX_MIN_LINKS))
     return ps[:n], flip[:n], link_d[:n]
+
+
+def haplotype_jobs(cpos, pos, ps):
+    """vga_haplotype_jobs -> jobs[J, 2] uint32 (c, ps): a job for every call c (cpos ascending) and phase set whose sites span
+    cpos[c], by c and then by ps; the library's one definition of the rule (csrc/vga_hapcall.hpp); needs no context and no device"""
+    cp = np.ascontiguousarray(cpos, dtype=np.uint32).reshape(-1)
+    at = np.ascontiguousarray(pos, dtype=np.uint32).reshape(-1)
+    sets = np.ascontiguousarray(ps, dtype=np.uint32).reshape(-1)
+    if len(sets) != len(at):
+        raise VgaError(-1, "haplotype_jobs: %d sites and %d ps" % (len(at), len(sets)))
+    pad = lambda a: a if len(a) else np.zeros(1, dtype=np.uint32)
+    L, cap = load_library(), 0
+    while True:
+        jobs, n = np.zeros((max(1, cap), 2), dtype=np.uint32), C.c_uint64(0)
+        rc = L.vga_haplotype_jobs(len(cp), _u32p(pad(cp)), len(at), _u32p(pad(at)), _u32p(pad(sets)), cap, _u32p(jobs), C.byref(n))
+        if rc != VGA_OK:
+            raise VgaError(rc, "haplotype_jobs: cpos and pos ascend strictly, ps[h] names the site that opens the set of h")
+        if n.value <= cap:
+            return jobs[:n.value]
+        cap = int(n.value)
+
+
+def haplotype_call(counts7) -> str:
+    """vga_haplotype_call: the haploid call of one haplotype's seven counts (A C G T other del ins) -> "A" "C" "G" "T" "-" "?"
+    or ".", with "+" behind it where more than half of the observing reads insert; the library's one definition"""
+    n = np.ascontiguousarray(counts7, dtype=np.uint32).reshape(-1)
+    if len(n) != 7:
+        raise VgaError(-1, "haplotype_call: %d counts, not 7" % len(n))
+    text = C.create_string_buffer(3)
+    rc = load_library().vga_haplotype_call(_u32p(n), text)
+    if rc != VGA_OK:
+        raise VgaError(rc, "haplotype_call")
+    return text.value.decode()
 
 
 def genotype_likelihood_rank(cost, n_paths: int, top: Optional[int] = None):
@@ -990,6 +1033,52 @@ class Context:
         return self._phase_tags(lambda sets, fl, cap, rows, n_rows: self.L.vga_phase_tags_lists(self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)),
                                                                                              n, _u32p(at), u8(xs), u8(ys), u8(rf), sets, fl, cap, rows, n_rows),
                                 n, ps, flip, cap)
+
+    def _haplotype_counts(self, call, n, ps, flip, cap):
+        """`call(ps, flip, cap, rows, n_rows)` is one of the two C calls with everything else bound: asked again with room for
+        every row when the first answer says there are more jobs than it had room for (nothing was counted then)"""
+        sets = np.ascontiguousarray(ps, dtype=np.uint32).reshape(-1)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8).reshape(-1)
+        if len(sets) != n or len(fl) != n:
+            raise VgaError(-1, "haplotype counts: %d sites, %d ps and %d flip" % (n, len(sets), len(fl)))
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        cap = max(0, int(cap))
+        while True:
+            rows, n_rows = np.zeros((max(1, cap), HAPLOTYPE_ROW), dtype=np.uint32), C.c_uint64(0)
+            self._check(call(_u32p(pad(sets)), pad(fl).ctypes.data_as(_P(C.c_uint8)), cap, _u32p(rows), C.byref(n_rows)))
+            if n_rows.value <= cap:
+                return rows[:n_rows.value]
+            cap = int(n_rows.value)
+
+    def haplotype_counts(self, cpos, pos, x, y, ps, flip, cap: Optional[int] = None):
+        """vga_haplotype_counts: for every call cpos[c] (ascending graph bases) and phase set whose sites span it, what the stored
+        reads of this context tagged a and those tagged b show there, at the sites pos, x, y of phase_links under the ps and flip of
+        phase_chain -> (rows[J, 16] uint32: c, ps, a[A C G T other del ins], b[..], by c and then by ps; n_reads).  Does not reset."""
+        cp = np.ascontiguousarray(cpos, dtype=np.uint32).reshape(-1)
+        n, at, (xs, ys) = self._phase_sites(pos, x, y)
+        n_reads = C.c_uint64(0)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=np.uint32)
+        rows = self._haplotype_counts(lambda sets, fl, cap, rows, n_rows: self.L.vga_haplotype_counts(self.h, len(cp), _u32p(pad(cp)), n, _u32p(at), u8(xs), u8(ys), sets,
+                                                                                                     fl, cap, rows, n_rows, C.byref(n_reads)),
+                                      n, ps, flip, 4 * len(cp) + 64 if cap is None else cap)
+        return rows, int(n_reads.value)
+
+    def haplotype_counts_lists(self, recs, words, n_bases, cpos, cref, pos, x, y, ref, ps, flip, cap: Optional[int] = None):
+        """vga_haplotype_counts_lists, the kernel seam: the same from explicit records and words (phase_links_lists); cref[c] is the
+        own letter of call c (0 .. 3 = A C G T, 4 anything else) -> rows[J, 16].  Needs a context only."""
+        rc = np.ascontiguousarray(recs, dtype=np.uint32).reshape(-1, 3)
+        wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        cp = np.ascontiguousarray(cpos, dtype=np.uint32).reshape(-1)
+        cr = np.ascontiguousarray(cref, dtype=np.uint8).reshape(-1)
+        if len(cr) != len(cp):
+            raise VgaError(-1, "haplotype counts: %d calls and %d own letters" % (len(cp), len(cr)))
+        n, at, (xs, ys, rf) = self._phase_sites(pos, x, y, ref)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=a.dtype)
+        return self._haplotype_counts(lambda sets, fl, cap, rows, n_rows: self.L.vga_haplotype_counts_lists(
+            self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), len(cp), _u32p(pad(cp)), u8(pad(cr)), n, _u32p(at), u8(xs), u8(ys), u8(rf), sets,
+            fl, cap, rows, n_rows), n, ps, flip, 4 * len(cp) + 64 if cap is None else cap)
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

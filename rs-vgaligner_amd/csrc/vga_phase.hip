@@ -1,6 +1,7 @@
 // vga_phase.hip -- the read-backed linkage of heterozygous sites and the reads' haplotype tags: k_ph_keep, k_ph_obs, k_ph_link,
 // k_ph_tag, k_ph_tag_scan and the C entry points vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain / _tags /
-// _tags_lists.  See vga_phase.hpp for the shape.
+// _tags_lists; and what the tagged reads of each haplotype show at the calls: k_hc_tags, k_hc_cols, k_hc_count and vga_haplotype_counts /
+// _counts_lists / _jobs / _call.  See vga_phase.hpp and vga_hapcall.hpp for the shape.
 //
 // Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
 // read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
@@ -8,11 +9,15 @@
 // twice gives the same answer in any order; obs = 0 for x alone, 1 for y alone, 2 for anything else consumed.  link[h][d - 1][2 a +
 // b] counts the reads with obs a at site h and b at site h + d.  ORs and sums of integers: the tables are exact and repeatable.
 #include "vga_phase.hpp"
+#include "vga_hapcall.hpp"
 #include "vga_pileup.hpp"
 
 // the store keeps k_pu_events' words as they are
 static_assert(PH_COL_OTHER == PU_COL_N && PH_COL_DEL == PU_COL_DEL && PH_COL_INS == PU_COL_INS && PH_COLS == PU_COLS && PH_MAX_SEQ == PU_MAX_SEQ,
               "the pileup's sparse columns and positions");
+// a column of a sparse word is a bit of a byte of k_hc_cols and a counter of a row
+static_assert(HC_COLS == PH_COLS && HC_COL_DEL == PH_COL_DEL && HC_COL_INS == PH_COL_INS && HC_ROW == 2u + 2u * HC_COLS && HC_MAX_CALLS == PH_MAX_SITES,
+              "the columns of the haplotype counts");
 
 namespace {
 
@@ -220,6 +225,105 @@ __global__ __launch_bounds__(PH_SCAN_BLOCK) void k_ph_tag_scan(uint32_t n, uint3
         const uint64_t was = run[1];
         run[0] = was;
         run[1] = was + carry;
+    }
+}
+
+// ---- the haplotype counts (vga_hapcall.hpp), behind the unchanged k_ph_obs
+
+// One lane per read of the tile: the loop of k_ph_tag over the sets in ascending ps, and instead of rows one byte per (set, read):
+// 1 where the read goes with haplotype a (votes_a > votes_b), 2 where it goes with b, 0 on a tie or without a vote -- the rule of
+// <out>-haplotag.tsv on the same tile.  No load is under a lane mask: a lane behind the tile's last read takes that read and writes
+// nothing (its bytes are never counted: k_hc_count masks them out).
+__global__ __launch_bounds__(HC_TAG_BLOCK) void k_hc_tags(uint32_t n, uint32_t tile_reads, const uint8_t *__restrict__ obs, uint32_t n_sets,
+                                                           const uint32_t *__restrict__ set_start, const uint32_t *__restrict__ order, uint8_t *__restrict__ tags)
+{
+    const uint32_t i = blockIdx.x * HC_TAG_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t r = live ? i : n - 1u;
+    const uint8_t *col = obs + r;
+    uint32_t k = set_start[0];
+    for (uint32_t s = 0; s < n_sets; s++) {
+        const uint32_t end = set_start[s + 1u];
+        uint32_t va = 0, vb = 0;
+#pragma unroll 4
+        for (; k < end; k++) {
+            const uint32_t o = order[k];
+            const uint32_t v = ph_code(col[(size_t)(o >> 1) * tile_reads]) ^ (o & 1u);
+            va += v == 0u ? 1u : 0u;
+            vb += v == 1u ? 1u : 0u;
+        }
+        if (live) tags[(size_t)s * tile_reads + i] = (uint8_t)(va > vb ? 1u : vb > va ? 2u : 0u);
+    }
+}
+
+// One wave per stored read of the tile, the shape of k_ph_obs over the calls: bit k of the byte of (call c, read r) says that the
+// read shows column k at cpos[c].  A sparse word sets its own column at the call at its position, if any -- insertion words too; a
+// run sets the own letter's column (cref: 0 .. 3, 4 for anything else) at every call in [start, end).  ORed bits: a base consumed
+// twice shows a column once.  A word's position only ever enters the search over the calls: no index is taken from it.
+__global__ __launch_bounds__(64) void k_hc_cols(uint32_t n, const ph_rec *__restrict__ recs, const uint32_t *__restrict__ words, uint32_t n_calls,
+                                                 const uint32_t *__restrict__ cpos, const uint8_t *__restrict__ cref, uint32_t tile_reads,
+                                                 uint32_t *__restrict__ cols)
+{
+    const uint32_t ri = blockIdx.x;
+    if (ri >= n) return;
+    const uint32_t lane = threadIdx.x;
+    const ph_rec rc = recs[ri];
+    const uint32_t *ev = words + rc.off, *sp = ev + rc.n_runs;
+    for (uint32_t i = lane; i < rc.n_sparse; i += 64) {
+        const uint32_t w = sp[i], p = w >> 3, col = w & 7u;
+        if (col >= PH_COLS) continue;
+        const uint32_t c = ph_lower(cpos, n_calls, p);
+        if (c >= n_calls || cpos[c] != p) continue;
+        ph_set(cols, tile_reads, c, ri, 1u << col);
+    }
+    for (uint32_t i = lane; i < rc.n_runs / 2u; i += 64) {
+        const uint32_t start = ev[2u * i] >> 1, end = ev[2u * i + 1u] >> 1;
+        for (uint32_t c = ph_lower(cpos, n_calls, start); c < n_calls && cpos[c] < end; c++)
+            ph_set(cols, tile_reads, c, ri, 1u << (cref[c] < PH_REF_OTHER ? cref[c] : PH_COL_OTHER));
+    }
+}
+
+// One workgroup per job (call c, set s): jobs holds c, the set's index and its ps.  Its waves stride over the tile's reads, a read
+// per lane: the byte of call c and the byte of set s (each row read coalesced), per column a ballot of the bit, cut with the ballots
+// of "tagged a" and "tagged b" and popcounted into fourteen wave-uniform counters, the waves' counters summed through LDS.  No load
+// is under a lane mask: a lane behind the tile's last read takes that read and is masked out of both tag ballots.  The workgroup
+// owns row j and the tiles run one after another on the stream: plain loads and stores add the tile's sums.
+__global__ __launch_bounds__(HC_COUNT_BLOCK) void k_hc_count(uint32_t n_jobs, uint32_t tile_reads, uint32_t n, const uint32_t *__restrict__ jobs,
+                                                              const uint8_t *__restrict__ tags, const uint8_t *__restrict__ cols, uint32_t *__restrict__ rows)
+{
+    __shared__ uint32_t part[HC_COUNT_BLOCK / 64u][2u * HC_COLS];
+    const uint32_t j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint8_t *crow = cols + (size_t)jobs[3u * j] * tile_reads, *trow = tags + (size_t)jobs[3u * j + 1u] * tile_reads;
+    uint32_t cnt[2u * HC_COLS];
+#pragma unroll
+    for (uint32_t k = 0; k < 2u * HC_COLS; k++) cnt[k] = 0;
+    for (uint32_t base = wave * 64u; base < n; base += HC_COUNT_BLOCK) {
+        const uint32_t r = base + lane < n ? base + lane : n - 1u;
+        const uint64_t live = __builtin_amdgcn_ballot_w64(base + lane < n);
+        const uint32_t bits = crow[r], tag = trow[r];
+        const uint64_t is_a = __builtin_amdgcn_ballot_w64(tag == 1u) & live, is_b = __builtin_amdgcn_ballot_w64(tag == 2u) & live;
+#pragma unroll
+        for (uint32_t k = 0; k < HC_COLS; k++) {
+            const uint64_t shows = __builtin_amdgcn_ballot_w64((bits >> k) & 1u);
+            cnt[k] += (uint32_t)__builtin_popcountll(shows & is_a);
+            cnt[HC_COLS + k] += (uint32_t)__builtin_popcountll(shows & is_b);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < 2u * HC_COLS; k++) part[wave][k] = cnt[k];
+    }
+    __syncthreads();
+    uint32_t *row = rows + (size_t)j * HC_ROW;
+    if (tid < 2u)
+        row[tid] = jobs[3u * j + 2u * tid];  // c and ps
+    else if (tid < HC_ROW) {
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < HC_COUNT_BLOCK / 64u; w++) s += part[w][tid - 2u];
+        row[tid] += s;
     }
 }
 
@@ -470,6 +574,28 @@ int ph_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d
     return VGA_OK;
 }
 
+// The sites by set, the sets in ascending ps (a set is named by the site that opens it: its first site), stable by site inside.
+// -> the number of sets S; set_of[h]: the index of the set that site h opens; host: set_start (S + 1 words), set_ps (S) and order
+// (H words: site << 1 | flip), as the kernels take them.
+uint32_t ph_group_sets(uint32_t H, const uint32_t *ps, const uint8_t *flip, std::vector<uint32_t> &set_of, std::vector<uint32_t> &host)
+{
+    set_of.assign(H, 0);
+    host.assign(3 * (size_t)H + 1, 0);
+    uint32_t S = 0;
+    for (uint32_t h = 0; h < H; h++)
+        if (ps[h] == h + 1u) set_of[h] = S++;
+    uint32_t *set_start = host.data(), *set_ps = set_start + S + 1u, *order = set_ps + S;
+    for (uint32_t h = 0; h < H; h++) set_start[set_of[ps[h] - 1u] + 1u]++;
+    for (uint32_t k = 0; k < S; k++) set_start[k + 1u] += set_start[k];
+    std::vector<uint32_t> fill(set_start, set_start + S);
+    for (uint32_t h = 0; h < H; h++) {
+        const uint32_t k = set_of[ps[h] - 1u];
+        set_ps[k] = ps[h];
+        order[fill[k]++] = h << 1 | flip[h];
+    }
+    return S;
+}
+
 // k_ph_obs, then k_ph_tag (count), k_ph_tag_scan and k_ph_tag (emit) over the n_reads stored reads, tile by tile: the rows of all
 // tiles land in one array in (read, ps) order, the first `cap` of them, and the total in *n_rows.  Everything was checked by the
 // caller.
@@ -481,23 +607,8 @@ int ph_tag_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_
     *n_rows = 0;
     if (s.n == 0 || n_reads == 0) return VGA_OK;
     const uint32_t H = (uint32_t)s.n;
-    // the sites by set, the sets in ascending ps (a set is named by the site that opens it: its first site), stable by site inside
-    std::vector<uint32_t> set_of(H), host(3 * (size_t)H + 1);
-    uint32_t S = 0;
-    for (uint32_t h = 0; h < H; h++)
-        if (ps[h] == h + 1u) set_of[h] = S++;
-    uint32_t *set_start = host.data(), *set_ps = set_start + S + 1u, *order = set_ps + S;  // S + 1, S and H words
-    std::fill(set_start, set_start + S + 1u, 0u);
-    for (uint32_t h = 0; h < H; h++) set_start[set_of[ps[h] - 1u] + 1u]++;
-    for (uint32_t k = 0; k < S; k++) set_start[k + 1u] += set_start[k];
-    {
-        std::vector<uint32_t> fill(set_start, set_start + S);
-        for (uint32_t h = 0; h < H; h++) {
-            const uint32_t k = set_of[ps[h] - 1u];
-            set_ps[k] = ps[h];
-            order[fill[k]++] = h << 1 | flip[h];
-        }
-    }
+    std::vector<uint32_t> set_of, host;
+    const uint32_t S = ph_group_sets(H, ps, flip, set_of, host);
     const size_t host_words = 2 * (size_t)S + 1u + H;
     const uint32_t T = ph_tile_reads(n_reads, s.n);
     // no more rows than (read, set) pairs can ever be written
@@ -566,6 +677,106 @@ int ph_upload_words(vga_ctx *ctx, uint64_t n_words, const uint32_t *words, vga_d
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     VGA_HIP_CHECK_OOM(ctx, d_words.reserve((size_t)n_words + 1));
     if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    return VGA_OK;
+}
+
+struct hc_calls {
+    uint64_t n;
+    const uint32_t *cpos;
+    const uint8_t *cref;
+};
+
+// what k_hc_cols relies on: calls that ascend strictly inside the graph, own letters 0 .. 4
+int hc_check_calls(vga_ctx *ctx, const char *who, const hc_calls &c, uint64_t n_bases)
+{
+    if (c.n > HC_MAX_CALLS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu calls, 2^24 at most", who, (unsigned long long)c.n);
+    if (c.n && !c.cpos) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu calls", who, (unsigned long long)c.n);
+    for (uint64_t j = 0; j < c.n; j++) {
+        if (c.cpos[j] >= n_bases) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu at base %u, the graph has %llu", who, (unsigned long long)j, c.cpos[j], (unsigned long long)n_bases);
+        if (j && c.cpos[j] <= c.cpos[j - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu does not lie behind the one before it", who, (unsigned long long)j);
+        if (c.cref && c.cref[j] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu has own letter %u (0 .. 4)", who, (unsigned long long)j, c.cref[j]);
+    }
+    return VGA_OK;
+}
+
+// The jobs (hc_jobs), then per tile of reads k_ph_obs, k_hc_tags, k_hc_cols and k_hc_count over the n_reads stored reads: *n_rows =
+// J always; the J rows when cap has room for them, nothing launched otherwise.  Everything was checked by the caller.
+int hc_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, const uint32_t *ps, const uint8_t *flip,
+           const hc_calls &c, uint64_t cap, uint32_t *rows, uint64_t *n_rows)
+{
+    hipStream_t st = ctx->stream;
+    vga_timers_reset(ctx);
+    vga_timers_collect(ctx);  // (a call that launches nothing reports no kernel)
+    if (s.n == 0 || c.n == 0 || n_reads == 0) {
+        *n_rows = 0;
+        return VGA_OK;
+    }
+    const uint64_t J = hc_jobs(c.n, c.cpos, s.n, s.pos, ps, 0, nullptr);
+    if (J > HC_MAX_JOBS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_haplotype_counts: %llu jobs, 2^24 at most", (unsigned long long)J);
+    *n_rows = J;
+    if (cap < J || J == 0) return VGA_OK;
+    const uint32_t H = (uint32_t)s.n, C = (uint32_t)c.n;
+    std::vector<uint32_t> set_of, host, jobs(3 * (size_t)J);
+    const uint32_t S = ph_group_sets(H, ps, flip, set_of, host);
+    hc_jobs(c.n, c.cpos, s.n, s.pos, ps, J, jobs.data());
+    for (uint64_t j = J; j-- > 0;) {  // (c, ps) pairs become c, set index, ps, from the back: in place
+        const uint32_t cj = jobs[2 * j], pj = jobs[2 * j + 1];
+        jobs[3 * j] = cj;
+        jobs[3 * j + 1] = set_of[pj - 1u];
+        jobs[3 * j + 2] = pj;
+    }
+    const size_t host_words = 2 * (size_t)S + 1u + H;
+    const uint32_t T = ph_tile_reads(n_reads, (uint64_t)H + S + C);
+    vga_dbuf<ph_rec> d_recs;
+    vga_dbuf<uint32_t> d_pos, d_tile, d_sets, d_jobs, d_rows;  // d_pos: pos, then cpos; d_tile: obs, cols, tags
+    vga_dbuf<uint8_t> d_bytes;                                 // x, y, ref, cref
+    const size_t obs_words = (size_t)H * T / 4u, cols_words = (size_t)C * T / 4u, tag_words = (size_t)S * T / 4u;
+    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
+    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve((size_t)H + C));
+    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3 + C));
+    VGA_HIP_CHECK_OOM(ctx, d_tile.reserve(obs_words + cols_words + tag_words));
+    VGA_HIP_CHECK_OOM(ctx, d_sets.reserve(host_words));
+    VGA_HIP_CHECK_OOM(ctx, d_jobs.reserve(3 * (size_t)J));
+    VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)J * HC_ROW));
+    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H, *d_cref = d_bytes.p + 3 * (size_t)H;
+    uint32_t *d_cpos = d_pos.p + H, *d_obs = d_tile.p, *d_cols = d_tile.p + obs_words;
+    uint8_t *d_tags = (uint8_t *)(d_tile.p + obs_words + cols_words);
+    const uint32_t *d_set_start = d_sets.p, *d_order = d_sets.p + 2 * (size_t)S + 1u;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_cpos, c.cpos, (size_t)C * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_cref, c.cref, C, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_sets.p, host.data(), host_words * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs.p, jobs.data(), 3 * (size_t)J * 4, hipMemcpyHostToDevice, st));
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_rows.p, 0, (size_t)J * HC_ROW * 4, st));
+    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
+        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_tile.p, 0, (obs_words + cols_words) * 4, st));  // (every tag byte that is counted is written)
+        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
+        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_hc_tags", (uint64_t)(H + S) * n, st);
+        hipLaunchKernelGGL(k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), 0, st, n, T, (const uint8_t *)d_obs, S, d_set_start, d_order,
+                           d_tags);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_hc_cols", 0, st);
+        hipLaunchKernelGGL(k_hc_cols, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, C, (const uint32_t *)d_cpos, (const uint8_t *)d_cref, T, d_cols);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+        t = vga_timer_begin(ctx, "k_hc_count", 2 * J * n, st);
+        hipLaunchKernelGGL(k_hc_count, dim3((uint32_t)J), dim3(HC_COUNT_BLOCK), 0, st, (uint32_t)J, T, n, (const uint32_t *)d_jobs.p, (const uint8_t *)d_tags,
+                           (const uint8_t *)d_cols, d_rows.p);
+        vga_timer_end(ctx, t);
+        VGA_HIP_CHECK(ctx, hipGetLastError());
+    }
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(rows, d_rows.p, (size_t)J * HC_ROW * 4, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    vga_timers_collect(ctx);
     return VGA_OK;
 }
 
@@ -640,6 +851,69 @@ extern "C" int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_r
     const int up = ph_upload_words(ctx, n_words, words, d_words);
     if (up != VGA_OK) return up;
     return ph_tag_run(ctx, (const ph_rec *)recs, n_reads, d_words.p, s, ps, flip, cap, rows, n_rows);
+}
+
+extern "C" int vga_haplotype_counts(vga_ctx *ctx, uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
+                                    const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows, uint64_t *n_rows, uint64_t *n_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    ph_state *ph = ph_active(ctx);
+    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_counts: the store is off (vga_phase_begin)");
+    ph_sites s = {n_sites, pos, x, y, nullptr};
+    hc_calls c = {n_calls, cpos, nullptr};
+    int rc = ph_check_sites(ctx, "vga_haplotype_counts", s, ctx->index.seq_length, true);
+    if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_haplotype_counts", n_sites, ps, flip, cap, rows, n_rows);
+    if (rc == VGA_OK) rc = hc_check_calls(ctx, "vga_haplotype_counts", c, ctx->index.seq_length);
+    if (rc != VGA_OK) return rc;
+    std::vector<uint8_t> ref(n_sites + 1), cref(n_calls + 1);
+    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
+    for (uint64_t j = 0; j < n_calls; j++) cref[j] = ph_ref_of(ctx->index.seq_fwd[cpos[j]]);
+    s.ref = ref.data();
+    c.cref = cref.data();
+    if (n_reads) *n_reads = ph->recs.size();
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    return hc_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, ps, flip, c, cap, rows, n_rows);
+}
+
+extern "C" int vga_haplotype_counts_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
+                                          uint64_t n_calls, const uint32_t *cpos, const uint8_t *cref, uint64_t n_sites, const uint32_t *pos, const uint8_t *x,
+                                          const uint8_t *y, const uint8_t *ref, const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows,
+                                          uint64_t *n_rows)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const ph_sites s = {n_sites, pos, x, y, ref};
+    const hc_calls c = {n_calls, cpos, cref};
+    int rc = ph_check_lists(ctx, "vga_haplotype_counts_lists", n_bases, n_reads, recs, n_words, words, s, true);
+    if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_haplotype_counts_lists", n_sites, ps, flip, cap, rows, n_rows);
+    if (rc == VGA_OK) rc = hc_check_calls(ctx, "vga_haplotype_counts_lists", c, n_bases);
+    if (rc == VGA_OK && n_calls && !cref) rc = vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_counts_lists: null array with %llu calls", (unsigned long long)n_calls);
+    if (rc != VGA_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    vga_ctx_scope scope(ctx);
+    vga_dbuf<uint32_t> d_words;
+    const int up = ph_upload_words(ctx, n_words, words, d_words);
+    if (up != VGA_OK) return up;
+    return hc_run(ctx, (const ph_rec *)recs, n_reads, d_words.p, s, ps, flip, c, cap, rows, n_rows);
+}
+
+extern "C" int vga_haplotype_jobs(uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites, const uint32_t *pos, const uint32_t *ps, uint64_t cap, uint32_t *jobs,
+                                  uint64_t *n_jobs)
+{
+    if (!n_jobs || (cap && !jobs) || (n_calls && !cpos) || (n_sites && (!pos || !ps))) return VGA_ERR_ARG;
+    for (uint64_t j = 1; j < n_calls; j++)
+        if (cpos[j] <= cpos[j - 1]) return VGA_ERR_ARG;
+    for (uint64_t h = 0; h < n_sites; h++)
+        if ((h && pos[h] <= pos[h - 1]) || ps[h] < 1u || ps[h] > h + 1u || ps[ps[h] - 1u] != ps[h]) return VGA_ERR_ARG;
+    *n_jobs = hc_jobs(n_calls, cpos, n_sites, pos, ps, cap, jobs);
+    return VGA_OK;
+}
+
+extern "C" int vga_haplotype_call(const uint32_t *counts, char *text)
+{
+    if (!counts || !text) return VGA_ERR_ARG;
+    hc_call_text(hc_call(counts), text);
+    return VGA_OK;
 }
 
 extern "C" int vga_phase_chain(uint64_t n_sites, const uint32_t *links, uint32_t min_links, uint32_t *ps, uint8_t *flip, uint8_t *link_d)

@@ -73,7 +73,10 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"", "--phase", false, "phase"}, {"", "--phase-min-links", true, "phase-min-links"},
                           // not in the reference: which kept reads go with which haplotype of which phase set of --phase, counted
                           // on the GPU (one TSV file, a row per read and set)
-                          {"", "--haplotag", false, "haplotag"}};
+                          {"", "--haplotag", false, "haplotag"},
+                          // not in the reference: what the reads tagged a and the reads tagged b of each phase set show at every
+                          // reported call inside the set's span, counted on the GPU, and a haploid call on each (one TSV file)
+                          {"", "--haplotype-calls", false, "haplotype-calls"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -228,6 +231,8 @@ int map_main(int argc, char **argv)
     }
     o.haplotag = m.count("haplotag") > 0;
     if (o.haplotag && !o.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
+    o.haplotype_calls = m.count("haplotype-calls") > 0;
+    if (o.haplotype_calls && !o.haplotag) throw Error("--haplotype-calls counts what the reads tagged by --haplotag show: it needs --haplotag");
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -313,6 +318,9 @@ int map_main(int argc, char **argv)
         fprintf(stderr, "[vgaligner] haplotag: %llu rows of %llu reads: %llu a, %llu b, %llu undecided\n", (unsigned long long)out.n_haplotag_rows,
                 (unsigned long long)out.n_phase_reads, (unsigned long long)out.n_haplotag_a, (unsigned long long)out.n_haplotag_b,
                 (unsigned long long)out.n_haplotag_tied);
+    if (o.haplotype_calls)
+        fprintf(stderr, "[vgaligner] haplotype-calls: %llu jobs, %llu rows, %llu differ\n", (unsigned long long)out.n_hapcall_jobs,
+                (unsigned long long)out.n_hapcall_rows, (unsigned long long)out.n_hapcall_differ);
     if (o.write_console) fputs(o.also_align ? out.alignments_gaf.c_str() : out.chains_gaf.c_str(), stdout);
     trace_mark("done");
     if (getenv("VGA_TRACE"))  // (what the exit has to give back: resident host memory)
@@ -359,7 +367,8 @@ int main(int argc, char **argv)
                         "                                       [--genotype-from support|edit]]\n"
                         "                [--path-edit]\n"
                         "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
-                        "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n");
+                        "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n"
+                        "                                 (with --haplotag: [--haplotype-calls])\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -214,6 +214,11 @@ struct MapOptions {
     // haplotype b of <out>-phase.tsv, counted on the GPU from the same store (vga_phase_tags; several contexts: vga_phase_tags_lists
     // on the first, from the concatenated stores), and write <out>-haplotag.tsv with the reads numbered as in the input file
     bool haplotag = false;
+    // --haplotype-calls (not in the reference; needs haplotag): per phase set and per row of <out>-variants.tsv inside the set's
+    // span, what the reads tagged a and the reads tagged b show there, counted on the GPU from the same store behind the tag call
+    // (vga_haplotype_counts; several contexts: vga_haplotype_counts_lists on the first, from the concatenated stores), a haploid
+    // call on each (vga_hapcall.hpp: hc_call), and write <out>-haplotype-calls.tsv
+    bool haplotype_calls = false;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -232,6 +237,7 @@ struct MapOutput {
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
     uint64_t n_phase_sites = 0, n_phase_sets = 0, n_phase_reads = 0;  // heterozygous sites, phase sets and reads kept (MapOptions::phase)
     uint64_t n_haplotag_rows = 0, n_haplotag_a = 0, n_haplotag_b = 0, n_haplotag_tied = 0;  // rows and their haplotypes (MapOptions::haplotag)
+    uint64_t n_hapcall_jobs = 0, n_hapcall_rows = 0, n_hapcall_differ = 0;  // jobs, lines written, lines whose two decided calls differ (MapOptions::haplotype_calls)
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)

@@ -4,6 +4,7 @@
 #include "../csrc/vga_insertion.hpp"
 #include "../csrc/vga_pair_index.hpp"
 #include "../csrc/vga_phase.hpp"
+#include "../csrc/vga_hapcall.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -97,6 +98,21 @@ void tags_fetch(vga_ctx *ctx, PhaseTags &t, uint64_t n_stored, F call)
         cap = t.n_rows;
     }
     t.rows.resize(t.n_rows * PH_TAG_COLS);
+}
+
+// `call(cap, rows, &n_rows)` is one of the two library calls with everything before cap bound: it counts nothing when there are
+// more jobs than it had room for, and is asked again
+template <typename F>
+void hap_counts_fetch(vga_ctx *ctx, HaplotypeCounts &h, uint64_t n_calls, F call)
+{
+    uint64_t cap = std::max<uint64_t>(4096, 2 * n_calls);
+    for (;;) {
+        h.rows.resize(cap * HC_ROW);
+        check(ctx, call(cap, h.rows.data(), &h.n_rows));
+        if (h.n_rows <= cap) break;
+        cap = h.n_rows;
+    }
+    h.rows.resize(h.n_rows * HC_ROW);
 }
 
 // ---- the writers.  Each gets its table padded to the sizes it indexes.
@@ -235,6 +251,32 @@ void haplotag_write(const PhaseTags &t, MapOutput &out, const std::string &out_p
     if (!out_prefix.empty()) write_file(out_prefix + "-haplotag.tsv", s);
 }
 
+// one line per job (a row of <out>-variants.tsv, a phase set whose sites span it) at which a tagged read of the set shows anything:
+// where it is, the set, the haploid call of each haplotype (hc_call), the reads each call rests on and the seven counts of each
+void haplotype_calls_write(const Index &ix, const VariantCalls &v, const HaplotypeCounts &h, MapOutput &out, const std::string &out_prefix)
+{
+    std::string t = "node\toffset\tref\tps\ta\tb\ta_obs\tb_obs\ta_A\ta_C\ta_G\ta_T\ta_N\ta_del\ta_ins\tb_A\tb_C\tb_G\tb_T\tb_N\tb_del\tb_ins\n";
+    uint64_t id = 1;  // the jobs come in base order: the node moves forward only
+    out.n_hapcall_jobs = h.n_rows; out.n_hapcall_rows = out.n_hapcall_differ = 0;
+    for (uint64_t j = 0; j < h.n_rows; j++) {
+        const uint32_t *r = h.rows.data() + j * HC_ROW, *a = r + 2, *b = a + HC_COLS;
+        uint64_t obs[2] = {0, 0};
+        for (uint32_t k = 0; k < HC_COL_INS; k++) { obs[0] += a[k]; obs[1] += b[k]; }
+        if (obs[0] + obs[1] + a[HC_COL_INS] + b[HC_COL_INS] == 0) continue;
+        const uint64_t p = v.pos[r[0]];
+        while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= p) id++;
+        const uint32_t ca = hc_call(a), cb = hc_call(b);
+        char text[3];
+        out.n_hapcall_rows++;
+        out.n_hapcall_differ += (ca & 7u) < HC_CALL_NONE && (cb & 7u) < HC_CALL_NONE && ca != cb ? 1u : 0u;
+        put_u64(t, id); t += '\t'; put_u64(t, p - ix.node_ref[id - 1].seq_idx); t += '\t'; t += ix.seq_fwd[p]; t += '\t'; put_u64(t, r[1]); t += '\t';
+        hc_call_text(ca, text); t += text; t += '\t'; hc_call_text(cb, text); t += text; t += '\t'; put_u64(t, obs[0]); t += '\t'; put_u64(t, obs[1]);
+        for (uint32_t k = 0; k < 2u * HC_COLS; k++) { t += '\t'; put_u64(t, a[k]); }
+        t += '\n';
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-haplotype-calls.tsv", t);
+}
+
 void path_support_write(const MapOptions &opt, const Counters &s, const std::string &rows, const std::string &out_prefix)
 {
     const size_t np = opt.paths.n_paths();
@@ -356,6 +398,7 @@ void check_aligner(const MapOptions &opt)
     if (opt.phase && !opt.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
     if (opt.phase && (opt.phase_min_links < 1 || opt.phase_min_links > PH_MIN_LINKS_MAX)) throw Error("--phase-min-links is 1 to 65535");
     if (opt.haplotag && !opt.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
+    if (opt.haplotype_calls && !opt.haplotag) throw Error("--haplotype-calls counts what the reads tagged by --haplotag show: it needs --haplotag");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -479,6 +522,11 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
                 return vga_phase_tags(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(), p.flip.data(), cap, rows, n_rows, nullptr);
             });
         }
+        if (hap_calling())  // every call just made, under the chain just made
+            hap_counts_fetch(ctx, hap_counts_, variants_.n_calls, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
+                return vga_haplotype_counts(ctx, variants_.n_calls, variants_.pos.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(),
+                                            p.flip.data(), cap, rows, n_rows, nullptr);
+            });
     } else if (phasing()) {  // the whole store: the context may be gone before the summed call
         PhaseStore s;
         uint64_t n_reads = 0, n_words = 0;
@@ -571,6 +619,16 @@ void Tables::call(vga_ctx *ctx)
             });
             trace_mark("reads tagged");
         }
+        if (hap_calling()) {
+            std::vector<uint8_t> cref(variants_.n_calls + 1);
+            for (uint64_t j = 0; j < variants_.n_calls; j++) cref[j] = ph_ref_of(ix_.seq_fwd[variants_.pos[j]]);
+            hap_counts_fetch(ctx, hap_counts_, variants_.n_calls, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
+                return vga_haplotype_counts_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), variants_.n_calls,
+                                                  variants_.pos.data(), cref.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), ref.data(), p.ps.data(),
+                                                  p.flip.data(), cap, rows, n_rows);
+            });
+            trace_mark("haplotypes counted");
+        }
     }
     if (!inserting()) return;
     insertions_.pad({ix_.seq_length * IA_COLS});
@@ -630,6 +688,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
         if (tagging()) {
             haplotag_write(tags_, out, out_prefix);
             trace_mark("haplotags written");
+        }
+        if (hap_calling()) {
+            haplotype_calls_write(ix_, variants_, hap_counts_, out, out_prefix);
+            trace_mark("haplotype calls written");
         }
     }
     if (inserting()) {

@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -67,6 +67,12 @@ struct PhaseTags {
     std::vector<uint32_t> rows;
     uint64_t n_rows = 0;
 };
+// The haplotype counts: sixteen words per job (c: an index into VariantCalls, ps, a[0 .. 6], b[0 .. 6]), in job order
+// (MapOptions::haplotype_calls)
+struct HaplotypeCounts {
+    std::vector<uint32_t> rows;
+    uint64_t n_rows = 0;
+};
 
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
 struct ReadRows {
@@ -91,6 +97,7 @@ public:
     bool inserting() const { return opt_.call_insertions; }
     bool phasing() const { return opt_.phase; }
     bool tagging() const { return opt_.haplotag; }
+    bool hap_calling() const { return opt_.haplotype_calls; }
     bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
     // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
     bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
@@ -102,14 +109,14 @@ public:
     // are noted by their number.
     void chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark);
     // What the context has counted and scored so far joins this object.  call_now: the variants are called from the context's own
-    // counters, and the insertions at their sites, and the heterozygous sites are linked and the reads tagged from its own store; otherwise its pileup
+    // counters, and the insertions at their sites, and the heterozygous sites are linked, the reads tagged and the haplotypes counted from its own store; otherwise its pileup
     // table, its insertion table and its whole phase store are kept for the sum.  (`slot` names the context in the trace.)
     void take(vga_ctx *ctx, uint32_t slot, bool call_now);
     // turns the analyses off on a context that stays with the caller
     void end(vga_ctx *ctx) const;
     void add(const Tables &o);
     // the variants of the summed pileup table, and the insertions at their sites from the summed insertion table, called on `ctx`
-    // and the links of the heterozygous sites and the reads' tags from the concatenated stores (any context: its own counters are not touched)
+    // and the links of the heterozygous sites, the reads' tags and the haplotype counts from the concatenated stores (any context: its own counters are not touched)
     void call(vga_ctx *ctx);
     // the TSV files beside the GAF files (out_prefix == "": none) and the fields of `out`
     void write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix);
@@ -129,6 +136,7 @@ private:
     PhaseStore phase_store_;  // (only kept for the route of several contexts)
     PhaseLinks phase_;
     PhaseTags tags_;  // (read_ids: of this context's store, then of the concatenated stores)
+    HaplotypeCounts hap_counts_;
     // the heterozygous variant calls as sites; sizes the tables of phase_
     void phase_sites();
     // the positions of the variant calls whose insertion state is het or hom; fills ins_calls_.site and sizes its arrays
