@@ -1,7 +1,7 @@
 // vga_phase.hip -- the read-backed linkage of heterozygous sites and the reads' haplotype tags: k_ph_keep, k_ph_obs, k_ph_link,
 // k_ph_tag, k_ph_tag_scan and the C entry points vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain / _tags /
 // _tags_lists; and what the tagged reads of each haplotype show at the calls: k_hc_tags, k_hc_cols, k_hc_count and vga_haplotype_counts /
-// _counts_lists / _jobs / _call.  See vga_phase.hpp and vga_hapcall.hpp for the shape.
+// _counts_lists / _jobs / _call.  See vga_phase.hpp and vga_hapcall.hpp for the shape.  Links, tags and counts run on one ph_frame.
 //
 // Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
 // read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
@@ -152,25 +152,14 @@ __global__ __launch_bounds__(PH_LINK_BLOCK) void k_ph_link(uint32_t n_sites, uin
     }
 }
 
-// One lane per read of the tile, behind k_ph_obs.  The sets come in ascending ps, set s holding the sites order[set_start[s]] ..
-// order[set_start[s + 1] - 1] (a word of order is site << 1 | flip); all of that is wave-uniform, and the 64 bytes a wave loads of
-// one site row are one line.  A site votes where the read shows x or y alone: vote = obs xor flip, 0 for haplotype a.  The two
-// counters of a set live in registers.  EMIT = false counts the sets with a vote into rows_of[read]; EMIT = true finds there the
-// read's first row within the tile (k_ph_tag_scan) and writes its rows at run[0] + that, those below cap only.  No load is under
-// a lane mask: a lane behind the tile's last read takes that read and writes nothing.
-template <bool EMIT>
-__global__ __launch_bounds__(PH_TAG_BLOCK) void k_ph_tag(uint32_t n, uint32_t tile_reads, uint32_t r0, const uint8_t *__restrict__ obs, uint32_t n_sets,
-                                                          const uint32_t *__restrict__ set_start, const uint32_t *__restrict__ set_ps,
-                                                          const uint32_t *__restrict__ order, uint32_t *__restrict__ rows_of,
-                                                          const uint64_t *__restrict__ run, uint64_t cap, uint32_t *__restrict__ rows)
+// The loop of one lane over the sets, behind k_ph_obs (col: the read's byte of site row 0).  The sets come in ascending ps, set s
+// holding the sites order[set_start[s]] .. order[set_start[s + 1] - 1] (a word of order is site << 1 | flip); all of that is
+// wave-uniform, and the 64 bytes a wave loads of one site row are one line.  A site votes where the read shows x or y alone: vote =
+// obs xor flip, 0 for haplotype a.  each(s, votes_a, votes_b) per set; the two counters of a set live in registers.
+template <typename Each>
+__device__ __forceinline__ void ph_each_set(const uint8_t *__restrict__ col, uint32_t tile_reads, uint32_t n_sets, const uint32_t *__restrict__ set_start,
+                                            const uint32_t *__restrict__ order, Each each)
 {
-    const uint32_t i = blockIdx.x * PH_TAG_BLOCK + threadIdx.x;
-    const bool live = i < n;
-    const uint32_t r = live ? i : n - 1u;
-    const uint8_t *col = obs + r;
-    uint64_t at = 0;
-    uint32_t made = 0;
-    if (EMIT) at = run[0] + rows_of[r];
     uint32_t k = set_start[0];
     for (uint32_t s = 0; s < n_sets; s++) {
         const uint32_t end = set_start[s + 1u];
@@ -182,13 +171,33 @@ __global__ __launch_bounds__(PH_TAG_BLOCK) void k_ph_tag(uint32_t n, uint32_t ti
             va += v == 0u ? 1u : 0u;
             vb += v == 1u ? 1u : 0u;
         }
-        if (va + vb == 0u) continue;
+        each(s, va, vb);
+    }
+}
+
+// One lane per read of the tile (ph_each_set).  EMIT = false counts the sets with a vote into rows_of[read]; EMIT = true finds there
+// the read's first row within the tile (k_ph_tag_scan) and writes its rows at run[0] + that, those below cap only.  No load is under
+// a lane mask: a lane behind the tile's last read takes that read and writes nothing.
+template <bool EMIT>
+__global__ __launch_bounds__(PH_TAG_BLOCK) void k_ph_tag(uint32_t n, uint32_t tile_reads, uint32_t r0, const uint8_t *__restrict__ obs, uint32_t n_sets,
+                                                          const uint32_t *__restrict__ set_start, const uint32_t *__restrict__ set_ps,
+                                                          const uint32_t *__restrict__ order, uint32_t *__restrict__ rows_of,
+                                                          const uint64_t *__restrict__ run, uint64_t cap, uint32_t *__restrict__ rows)
+{
+    const uint32_t i = blockIdx.x * PH_TAG_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t r = live ? i : n - 1u;
+    uint64_t at = 0;
+    uint32_t made = 0;
+    if (EMIT) at = run[0] + rows_of[r];
+    ph_each_set(obs + r, tile_reads, n_sets, set_start, order, [&](uint32_t s, uint32_t va, uint32_t vb) {
+        if (va + vb == 0u) return;
         if (EMIT) {
             if (live && at < cap) reinterpret_cast<uint4 *>(rows)[at] = make_uint4(r0 + r, set_ps[s], va, vb);
             at++;
         } else
             made++;
-    }
+    });
     if (!EMIT && live) rows_of[i] = made;
 }
 
@@ -230,30 +239,19 @@ __global__ __launch_bounds__(PH_SCAN_BLOCK) void k_ph_tag_scan(uint32_t n, uint3
 
 // ---- the haplotype counts (vga_hapcall.hpp), behind the unchanged k_ph_obs
 
-// One lane per read of the tile: the loop of k_ph_tag over the sets in ascending ps, and instead of rows one byte per (set, read):
-// 1 where the read goes with haplotype a (votes_a > votes_b), 2 where it goes with b, 0 on a tie or without a vote -- the rule of
-// <out>-haplotag.tsv on the same tile.  No load is under a lane mask: a lane behind the tile's last read takes that read and writes
-// nothing (its bytes are never counted: k_hc_count masks them out).
+// One lane per read of the tile (ph_each_set, as k_ph_tag), and instead of rows one byte per (set, read): 1 where the read goes with
+// haplotype a (votes_a > votes_b), 2 where it goes with b, 0 on a tie or without a vote -- the rule of <out>-haplotag.tsv on the
+// same tile.  No load is under a lane mask: a lane behind the tile's last read takes that read and writes nothing (its bytes are
+// never counted: k_hc_count masks them out).
 __global__ __launch_bounds__(HC_TAG_BLOCK) void k_hc_tags(uint32_t n, uint32_t tile_reads, const uint8_t *__restrict__ obs, uint32_t n_sets,
                                                            const uint32_t *__restrict__ set_start, const uint32_t *__restrict__ order, uint8_t *__restrict__ tags)
 {
     const uint32_t i = blockIdx.x * HC_TAG_BLOCK + threadIdx.x;
     const bool live = i < n;
     const uint32_t r = live ? i : n - 1u;
-    const uint8_t *col = obs + r;
-    uint32_t k = set_start[0];
-    for (uint32_t s = 0; s < n_sets; s++) {
-        const uint32_t end = set_start[s + 1u];
-        uint32_t va = 0, vb = 0;
-#pragma unroll 4
-        for (; k < end; k++) {
-            const uint32_t o = order[k];
-            const uint32_t v = ph_code(col[(size_t)(o >> 1) * tile_reads]) ^ (o & 1u);
-            va += v == 0u ? 1u : 0u;
-            vb += v == 1u ? 1u : 0u;
-        }
+    ph_each_set(obs + r, tile_reads, n_sets, set_start, order, [&](uint32_t s, uint32_t va, uint32_t vb) {
         if (live) tags[(size_t)s * tile_reads + i] = (uint8_t)(va > vb ? 1u : vb > va ? 2u : 0u);
-    }
+    });
 }
 
 // One wave per stored read of the tile, the shape of k_ph_obs over the calls: bit k of the byte of (call c, read r) says that the
@@ -327,6 +325,17 @@ __global__ __launch_bounds__(HC_COUNT_BLOCK) void k_hc_count(uint32_t n_jobs, ui
     }
 }
 
+// A launch on the context's stream under a timer of the kernel's name: VGA_OK, or the error that was set
+template <typename... P, typename... A>
+int ph_launch(vga_ctx *ctx, const char *name, uint64_t bytes, void (*kernel)(P...), dim3 grid, dim3 block, A... args)
+{
+    const int t = vga_timer_begin(ctx, name, bytes, ctx->stream);
+    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, static_cast<P>(args)...);
+    vga_timer_end(ctx, t);
+    VGA_HIP_CHECK(ctx, hipGetLastError());
+    return VGA_OK;
+}
+
 }  // namespace
 
 // The store of a context's index while it is on (vga_dev_index::ph: released with the index): the words on the device, the
@@ -384,10 +393,9 @@ int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t
         ph->cap = cap;
     }
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(ph->d_dst.p, ph->h_dst.p, nw * 4, hipMemcpyHostToDevice, st));
-    const int t = vga_timer_begin(ctx, "k_ph_keep", (at - ph->n_words) * 8, st);
-    hipLaunchKernelGGL(k_ph_keep, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, lists.d_win.p, lists.d_lists.p, lists.d_host_lists.p, ph->d_dst.p, ph->d_words);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = ph_launch(ctx, "k_ph_keep", (at - ph->n_words) * 8, k_ph_keep, dim3((unsigned)nw), dim3(64), nw, lists.d_win.p, lists.d_lists.p, lists.d_host_lists.p,
+                             ph->d_dst.p, ph->d_words);
+    if (rc != VGA_OK) return rc;
     for (size_t i = 0; i < nw; i++) ph->recs.push_back(ph_rec{ph->h_dst.p[i], lists.h_win.p[i].n_a, lists.h_win.p[i].n_b});
     ph->n_words = at;
     return VGA_OK;
@@ -454,19 +462,47 @@ struct ph_sites {
     const uint8_t *x, *y, *ref;
 };
 
+// What k_ph_obs and k_hc_cols rely on, for the sites and for the calls (noun: "site" / "call"): at most 2^24 positions, their arrays there (have_all),
+// ascending strictly inside the graph, the own letters 0 .. 4 where given.  more(h) checks what else position h carries, in its place.
+template <typename More>
+int ph_check_positions(vga_ctx *ctx, const char *who, const char *noun, uint64_t n, const uint32_t *pos, const uint8_t *own, bool have_all, uint64_t n_bases,
+                       More more)
+{
+    if (n > PH_MAX_SITES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu %ss, 2^24 at most", who, (unsigned long long)n, noun);
+    if (n && !have_all) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu %ss", who, (unsigned long long)n, noun);
+    for (uint64_t h = 0; h < n; h++) {
+        if (pos[h] >= n_bases)
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: %s %llu at base %u, the graph has %llu", who, noun, (unsigned long long)h, pos[h], (unsigned long long)n_bases);
+        if (h && pos[h] <= pos[h - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: %s %llu does not lie behind the one before it", who, noun, (unsigned long long)h);
+        const int rc = more(h);
+        if (rc != VGA_OK) return rc;
+        if (own && own[h] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: %s %llu has own letter %u (0 .. 4)", who, noun, (unsigned long long)h, own[h]);
+    }
+    return VGA_OK;
+}
+
 // what the kernels rely on: sites that ascend strictly inside the graph, x < y <= D, ref <= other
 int ph_check_sites(vga_ctx *ctx, const char *who, const ph_sites &s, uint64_t n_bases, bool have_outputs)
 {
-    if (s.n > PH_MAX_SITES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu sites, 2^24 at most", who, (unsigned long long)s.n);
-    if (s.n && (!s.pos || !s.x || !s.y || !have_outputs)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)s.n);
-    for (uint64_t h = 0; h < s.n; h++) {
-        if (s.pos[h] >= n_bases) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu at base %u, the graph has %llu", who, (unsigned long long)h, s.pos[h], (unsigned long long)n_bases);
-        if (h && s.pos[h] <= s.pos[h - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu does not lie behind the one before it", who, (unsigned long long)h);
-        if (!(s.x[h] < s.y[h] && s.y[h] <= PH_ALLELE_DEL))
-            return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has alleles %u, %u (x < y <= 4)", who, (unsigned long long)h, s.x[h], s.y[h]);
-        if (s.ref && s.ref[h] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has own letter %u (0 .. 4)", who, (unsigned long long)h, s.ref[h]);
-    }
-    return VGA_OK;
+    return ph_check_positions(ctx, who, "site", s.n, s.pos, s.ref, s.pos && s.x && s.y && have_outputs, n_bases, [&](uint64_t h) -> int {
+        if (s.x[h] < s.y[h] && s.y[h] <= PH_ALLELE_DEL) return VGA_OK;
+        return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has alleles %u, %u (x < y <= 4)", who, (unsigned long long)h, s.x[h], s.y[h]);
+    });
+}
+
+// The store's half of the checks, as ph_check_lists is the lists': the store is on, and the sites lie in its index
+int ph_check_store(vga_ctx *ctx, const char *who, const ph_sites &s, bool have_outputs)
+{
+    if (!ph_active(ctx)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: the store is off (vga_phase_begin)", who);
+    return ph_check_sites(ctx, who, s, ctx->index.seq_length, have_outputs);
+}
+
+// the own letters of n positions inside the context's index, as the store's routes take them for the sites and for the calls
+std::vector<uint8_t> ph_own_letters(const vga_ctx *ctx, uint64_t n, const uint32_t *pos)
+{
+    std::vector<uint8_t> own(n + 1);
+    for (uint64_t h = 0; h < n; h++) own[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
+    return own;
 }
 
 // what vga_phase_links_lists and vga_phase_tags_lists check before anything is launched: the sizes, the sites, and every word of
@@ -501,14 +537,17 @@ int ph_check_lists(vga_ctx *ctx, const char *who, uint64_t n_bases, uint64_t n_r
     return VGA_OK;
 }
 
-// the sets as vga_phase_chain numbers them: ps[h] names the site that opens the set of h (1-based, at or before h), flip is 0 or 1
+// the rule of a set's name: ps[h] names the site that opens the set of h (1-based, at or before h), and that site names itself
+bool ph_set_named(const uint32_t *ps, uint64_t h) { return ps[h] >= 1u && ps[h] <= h + 1u && ps[ps[h] - 1u] == ps[h]; }
+
+// the sets as vga_phase_chain numbers them (ph_set_named), flip is 0 or 1
 int ph_check_sets(vga_ctx *ctx, const char *who, uint64_t n_sites, const uint32_t *ps, const uint8_t *flip, uint64_t cap, const uint32_t *rows,
                   const uint64_t *n_rows)
 {
     if (!n_rows || (cap && !rows)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null output (n_rows always, rows with cap above 0)", who);
     if (n_sites && (!ps || !flip)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu sites", who, (unsigned long long)n_sites);
     for (uint64_t h = 0; h < n_sites; h++) {
-        if (ps[h] < 1u || ps[h] > h + 1u || ps[ps[h] - 1u] != ps[h])
+        if (!ph_set_named(ps, h))
             return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu is in set %u: a set is named by the site that opens it, 1 .. %llu here", who, (unsigned long long)h,
                                  ps[h], (unsigned long long)(h + 1u));
         if (flip[h] > 1u) return vga_set_error(ctx, VGA_ERR_ARG, "%s: site %llu has flip %u (0 or 1)", who, (unsigned long long)h, flip[h]);
@@ -524,160 +563,187 @@ uint32_t ph_tile_reads(uint64_t n_reads, uint64_t n_sites)
     return (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(t, std::min<uint64_t>(all, 1ull << 24)));
 }
 
-// k_ph_obs and k_ph_link over the n_reads stored reads (records on the host, words on the device), tile by tile, and the two
-// tables back to the host.  Everything was checked by the caller.
-int ph_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, uint32_t *links, uint32_t *site_reads)
+// What the three calls over the stored reads share.  An entry point checks its arguments, makes the frame (from then on the context's
+// timers hold this call's kernels, also when it launches none), takes the reads from_store or from_lists and runs ph_run, ph_tag_run or
+// hc_run: group the sets if there are any, open the tile, each_tile behind k_ph_obs with the run's own kernels, copy back, close.
+struct ph_frame {
+    vga_ctx *ctx;
+    vga_ctx_scope scope;
+    ph_sites s;  // on the host
+    const ph_rec *recs = nullptr;  // the reads: the records on the host, the words on the device
+    const uint32_t *d_words = nullptr;
+    uint64_t n_reads = 0;
+    vga_dbuf<uint32_t> own_words;  // from_lists: what d_words points to
+    std::vector<uint8_t> own_ref;  // from_store: what s.ref points to
+    // H sites in S sets (group); T reads to a tile of obs_words words, the first clear_words of the whole tile zeroed per tile (open)
+    uint32_t H, S = 0, T = 0;
+    size_t obs_words = 0, clear_words = 0;
+    std::vector<uint32_t> set_of, sets;  // group: the index of the set that a site opens; what d_sets takes
+    vga_dbuf<ph_rec> d_recs;
+    vga_dbuf<uint32_t> d_pos, d_tile, d_sets;  // d_tile: obs, then the rows the run asked for; d_sets: set_start (S + 1), set_ps (S), order
+    vga_dbuf<uint8_t> d_bytes;                 // x, y, ref
+
+    ph_frame(vga_ctx *c, const ph_sites &sites) : ctx(c), scope(c), s(sites), H((uint32_t)sites.n)
+    {
+        (void)hipSetDevice(ctx->device);
+        vga_timers_reset(ctx);
+        vga_timers_collect(ctx);  // (a call that launches nothing reports no kernel)
+    }
+
+    // the reads of the context's store (checked: it is on, the sites lie in its index), the sites' own letters from the index
+    void from_store(uint64_t *n_reads_out)
+    {
+        const ph_state *ph = ph_active(ctx);
+        own_ref = ph_own_letters(ctx, s.n, s.pos);
+        s.ref = own_ref.data();
+        recs = ph->recs.data();
+        n_reads = ph->recs.size();
+        d_words = ph->d_words;
+        if (n_reads_out) *n_reads_out = n_reads;
+    }
+
+    // the reads of explicit lists (checked: ph_check_lists): their words on the device, behind whatever the context's stream still runs
+    int from_lists(uint64_t n, const uint32_t *list_recs, uint64_t n_words, const uint32_t *words)
+    {
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+        VGA_HIP_CHECK_OOM(ctx, own_words.reserve((size_t)n_words + 1));
+        if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(own_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+        recs = (const ph_rec *)list_recs;
+        n_reads = n;
+        d_words = own_words.p;
+        return VGA_OK;
+    }
+
+    // The sites by set, the sets in ascending ps (a set is named by the site that opens it: its first site), stable by site inside.
+    // -> the number of sets S; set_of[h]: the index of the set that site h opens; sets, for open() to upload: set_start (S + 1 words),
+    // set_ps (S) and order (H words: site << 1 | flip), as the kernels take them.
+    uint32_t group(const uint32_t *ps, const uint8_t *flip)
+    {
+        set_of.assign(H, 0);
+        sets.assign(3 * (size_t)H + 1, 0);
+        for (uint32_t h = 0; h < H; h++)
+            if (ps[h] == h + 1u) set_of[h] = S++;
+        uint32_t *set_start = sets.data(), *set_ps = set_start + S + 1u, *order = set_ps + S;
+        for (uint32_t h = 0; h < H; h++) set_start[set_of[ps[h] - 1u] + 1u]++;
+        for (uint32_t k = 0; k < S; k++) set_start[k + 1u] += set_start[k];
+        std::vector<uint32_t> fill(set_start, set_start + S);
+        for (uint32_t h = 0; h < H; h++) {
+            const uint32_t k = set_of[ps[h] - 1u];
+            set_ps[k] = ps[h];
+            order[fill[k]++] = h << 1 | flip[h];
+        }
+        return S;
+    }
+
+    // T for a tile of H rows of obs, `cleared` rows zeroed per tile as obs is and `more` rows that are not; records, sites and sets go up
+    int open(uint32_t cleared = 0, uint32_t more = 0)
+    {
+        T = ph_tile_reads(n_reads, (uint64_t)H + cleared + more);
+        obs_words = (size_t)H * T / 4u;
+        clear_words = obs_words + (size_t)cleared * T / 4u;
+        const size_t set_words = S ? 2 * (size_t)S + 1u + H : 0;
+        VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
+        VGA_HIP_CHECK_OOM(ctx, d_pos.reserve(H));
+        VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3));
+        VGA_HIP_CHECK_OOM(ctx, d_tile.reserve(clear_words + (size_t)more * T / 4u));
+        VGA_HIP_CHECK_OOM(ctx, d_sets.reserve(set_words));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, ctx->stream));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, ctx->stream));
+        const uint8_t *const bytes[3] = {s.x, s.y, s.ref};
+        for (size_t k = 0; k < 3; k++) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_bytes.p + k * H, bytes[k], H, hipMemcpyHostToDevice, ctx->stream));
+        if (set_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_sets.p, sets.data(), set_words * 4, hipMemcpyHostToDevice, ctx->stream));
+        return VGA_OK;
+    }
+
+    // per tile of reads: the tile cleared, k_ph_obs, then per_tile(r0, n) for the n reads from r0
+    template <typename F>
+    int each_tile(F per_tile)
+    {
+        for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
+            VGA_HIP_CHECK(ctx, hipMemsetAsync(d_tile.p, 0, clear_words * 4, ctx->stream));
+            int rc = ph_launch(ctx, "k_ph_obs", 0, k_ph_obs, dim3(n), dim3(64), n, d_recs.p + r0, d_words, H, d_pos.p, d_bytes.p, d_bytes.p + H, d_bytes.p + 2 * (size_t)H,
+                               T, d_tile.p);
+            if (rc == VGA_OK) rc = per_tile(r0, n);
+            if (rc != VGA_OK) return rc;
+        }
+        return VGA_OK;
+    }
+
+    // behind the run's copies back: everything has arrived, and the timers hold the call's kernels
+    int close()
+    {
+        VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        vga_timers_collect(ctx);
+        return VGA_OK;
+    }
+};
+
+// k_ph_link behind k_ph_obs over the frame's reads, tile by tile, and the two tables back to the host.  The caller checked everything.
+int ph_run(ph_frame &f, uint32_t *links, uint32_t *site_reads)
 {
-    hipStream_t st = ctx->stream;
-    vga_timers_reset(ctx);
-    if (s.n == 0) return VGA_OK;
-    const uint32_t H = (uint32_t)s.n;
-    if (n_reads == 0) {
+    vga_ctx *ctx = f.ctx;
+    const uint32_t H = f.H;
+    if (H == 0) return VGA_OK;
+    if (f.n_reads == 0) {
         memset(links, 0, (size_t)H * PH_LINK_ROW * 4);
         memset(site_reads, 0, (size_t)H * PH_SITE_COLS * 4);
         return VGA_OK;
     }
-    const uint32_t T = ph_tile_reads(n_reads, s.n);
-    vga_dbuf<ph_rec> d_recs;
-    vga_dbuf<uint32_t> d_pos, d_obs, d_out;  // d_out: links, then site_reads
-    vga_dbuf<uint8_t> d_bytes;               // x, y, ref
-    const size_t obs_words = (size_t)H * T / 4u, out_words = (size_t)H * (PH_LINK_ROW + PH_SITE_COLS);
-    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
-    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve(H));
-    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3));
-    VGA_HIP_CHECK_OOM(ctx, d_obs.reserve(obs_words));
+    vga_dbuf<uint32_t> d_out;  // links, then site_reads
+    const size_t out_words = (size_t)H * (PH_LINK_ROW + PH_SITE_COLS);
     VGA_HIP_CHECK_OOM(ctx, d_out.reserve(out_words));
-    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H;
     uint32_t *d_links = d_out.p, *d_sr = d_out.p + (size_t)H * PH_LINK_ROW;
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_out.p, 0, out_words * 4, st));
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
-        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_obs.p, 0, obs_words * 4, st));
-        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
-        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_ph_link", (uint64_t)H * n, st);
-        hipLaunchKernelGGL(k_ph_link, dim3(H), dim3(PH_LINK_BLOCK), 0, st, H, T, n, (const uint8_t *)d_obs.p, d_links, d_sr);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-    }
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(links, d_links, (size_t)H * PH_LINK_ROW * 4, hipMemcpyDeviceToHost, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(site_reads, d_sr, (size_t)H * PH_SITE_COLS * 4, hipMemcpyDeviceToHost, st));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    vga_timers_collect(ctx);
-    return VGA_OK;
+    int rc = f.open();
+    if (rc != VGA_OK) return rc;
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_out.p, 0, out_words * 4, ctx->stream));
+    rc = f.each_tile([&](uint64_t, uint32_t n) {
+        return ph_launch(ctx, "k_ph_link", (uint64_t)H * n, k_ph_link, dim3(H), dim3(PH_LINK_BLOCK), H, f.T, n, (const uint8_t *)f.d_tile.p, d_links, d_sr);
+    });
+    if (rc != VGA_OK) return rc;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(links, d_links, (size_t)H * PH_LINK_ROW * 4, hipMemcpyDeviceToHost, ctx->stream));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(site_reads, d_sr, (size_t)H * PH_SITE_COLS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return f.close();
 }
 
-// The sites by set, the sets in ascending ps (a set is named by the site that opens it: its first site), stable by site inside.
-// -> the number of sets S; set_of[h]: the index of the set that site h opens; host: set_start (S + 1 words), set_ps (S) and order
-// (H words: site << 1 | flip), as the kernels take them.
-uint32_t ph_group_sets(uint32_t H, const uint32_t *ps, const uint8_t *flip, std::vector<uint32_t> &set_of, std::vector<uint32_t> &host)
+// k_ph_tag (count), k_ph_tag_scan and k_ph_tag (emit) behind k_ph_obs over the frame's reads, tile by tile: the rows of all tiles
+// land in one array in (read, ps) order, the first `cap` of them, and the total in *n_rows.  Everything was checked by the caller.
+int ph_tag_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows, uint64_t *n_rows)
 {
-    set_of.assign(H, 0);
-    host.assign(3 * (size_t)H + 1, 0);
-    uint32_t S = 0;
-    for (uint32_t h = 0; h < H; h++)
-        if (ps[h] == h + 1u) set_of[h] = S++;
-    uint32_t *set_start = host.data(), *set_ps = set_start + S + 1u, *order = set_ps + S;
-    for (uint32_t h = 0; h < H; h++) set_start[set_of[ps[h] - 1u] + 1u]++;
-    for (uint32_t k = 0; k < S; k++) set_start[k + 1u] += set_start[k];
-    std::vector<uint32_t> fill(set_start, set_start + S);
-    for (uint32_t h = 0; h < H; h++) {
-        const uint32_t k = set_of[ps[h] - 1u];
-        set_ps[k] = ps[h];
-        order[fill[k]++] = h << 1 | flip[h];
-    }
-    return S;
-}
-
-// k_ph_obs, then k_ph_tag (count), k_ph_tag_scan and k_ph_tag (emit) over the n_reads stored reads, tile by tile: the rows of all
-// tiles land in one array in (read, ps) order, the first `cap` of them, and the total in *n_rows.  Everything was checked by the
-// caller.
-int ph_tag_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, const uint32_t *ps, const uint8_t *flip,
-               uint64_t cap, uint32_t *rows, uint64_t *n_rows)
-{
+    vga_ctx *ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    vga_timers_reset(ctx);
     *n_rows = 0;
-    if (s.n == 0 || n_reads == 0) return VGA_OK;
-    const uint32_t H = (uint32_t)s.n;
-    std::vector<uint32_t> set_of, host;
-    const uint32_t S = ph_group_sets(H, ps, flip, set_of, host);
-    const size_t host_words = 2 * (size_t)S + 1u + H;
-    const uint32_t T = ph_tile_reads(n_reads, s.n);
-    // no more rows than (read, set) pairs can ever be written
-    const uint64_t room = std::min<uint64_t>(cap, n_reads * (uint64_t)S);
-    vga_dbuf<ph_rec> d_recs;
-    vga_dbuf<uint32_t> d_pos, d_obs, d_sets, d_rows_of, d_rows;
+    if (f.H == 0 || f.n_reads == 0) return VGA_OK;
+    const uint32_t H = f.H, S = f.group(ps, flip);
+    const uint64_t room = std::min<uint64_t>(cap, f.n_reads * (uint64_t)S);  // (no more rows than (read, set) pairs can ever be written)
+    vga_dbuf<uint32_t> d_rows_of, d_rows;
     vga_dbuf<uint64_t> d_run;
-    vga_dbuf<uint8_t> d_bytes;  // x, y, ref
-    const size_t obs_words = (size_t)H * T / 4u;
-    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
-    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve(H));
-    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3));
-    VGA_HIP_CHECK_OOM(ctx, d_obs.reserve(obs_words));
-    VGA_HIP_CHECK_OOM(ctx, d_sets.reserve(host_words));
-    VGA_HIP_CHECK_OOM(ctx, d_rows_of.reserve(T));
+    int rc = f.open();
+    if (rc != VGA_OK) return rc;
+    VGA_HIP_CHECK_OOM(ctx, d_rows_of.reserve(f.T));
     VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)room * PH_TAG_COLS + PH_TAG_COLS));
     VGA_HIP_CHECK_OOM(ctx, d_run.reserve(2));
-    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H;
-    const uint32_t *d_set_start = d_sets.p, *d_set_ps = d_sets.p + S + 1u, *d_order = d_sets.p + 2 * (size_t)S + 1u;
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_sets.p, host.data(), host_words * 4, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_run.p, 0, 16, st));
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
-        const dim3 grid((n + PH_TAG_BLOCK - 1u) / PH_TAG_BLOCK);
-        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_obs.p, 0, obs_words * 4, st));
-        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
-        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_ph_tag", (uint64_t)H * n, st);
-        hipLaunchKernelGGL(k_ph_tag<false>, grid, dim3(PH_TAG_BLOCK), 0, st, n, T, (uint32_t)r0, (const uint8_t *)d_obs.p, S, d_set_start, d_set_ps, d_order,
-                           d_rows_of.p, (const uint64_t *)d_run.p, room, d_rows.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_ph_tag_scan", (uint64_t)n * 8, st);
-        hipLaunchKernelGGL(k_ph_tag_scan, dim3(1), dim3(PH_SCAN_BLOCK), 0, st, n, d_rows_of.p, d_run.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_ph_tag", (uint64_t)H * n, st);
-        hipLaunchKernelGGL(k_ph_tag<true>, grid, dim3(PH_TAG_BLOCK), 0, st, n, T, (uint32_t)r0, (const uint8_t *)d_obs.p, S, d_set_start, d_set_ps, d_order,
-                           d_rows_of.p, (const uint64_t *)d_run.p, room, d_rows.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-    }
+    const uint32_t *d_sets = f.d_sets.p;  // set_start, set_ps, order
+    const auto tag = [&](auto kernel, uint64_t r0, uint32_t n) {
+        return ph_launch(ctx, "k_ph_tag", (uint64_t)H * n, kernel, dim3((n + PH_TAG_BLOCK - 1u) / PH_TAG_BLOCK), dim3(PH_TAG_BLOCK), n, f.T, r0, (const uint8_t *)f.d_tile.p,
+                         S, d_sets, d_sets + S + 1u, d_sets + 2 * (size_t)S + 1u, d_rows_of.p, d_run.p, room, d_rows.p);
+    };
+    rc = f.each_tile([&](uint64_t r0, uint32_t n) {
+        int rc = tag(k_ph_tag<false>, r0, n);
+        if (rc == VGA_OK) rc = ph_launch(ctx, "k_ph_tag_scan", (uint64_t)n * 8, k_ph_tag_scan, dim3(1), dim3(PH_SCAN_BLOCK), n, d_rows_of.p, d_run.p);
+        if (rc == VGA_OK) rc = tag(k_ph_tag<true>, r0, n);
+        return rc;
+    });
+    if (rc != VGA_OK) return rc;
     uint64_t run[2] = {0, 0};
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(run, d_run.p, 16, hipMemcpyDeviceToHost, st));
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     const uint64_t written = std::min<uint64_t>(run[1], room);
-    if (written) {
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(rows, d_rows.p, (size_t)written * PH_TAG_COLS * 4, hipMemcpyDeviceToHost, st));
-        VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    }
-    *n_rows = run[1];
-    vga_timers_collect(ctx);
-    return VGA_OK;
-}
-
-// the words of explicit lists on the device, behind whatever the context's stream still runs
-int ph_upload_words(vga_ctx *ctx, uint64_t n_words, const uint32_t *words, vga_dbuf<uint32_t> &d_words)
-{
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    VGA_HIP_CHECK_OOM(ctx, d_words.reserve((size_t)n_words + 1));
-    if (n_words) VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_words.p, words, (size_t)n_words * 4, hipMemcpyHostToDevice, ctx->stream));
-    return VGA_OK;
+    if (written) VGA_HIP_CHECK(ctx, hipMemcpyAsync(rows, d_rows.p, (size_t)written * PH_TAG_COLS * 4, hipMemcpyDeviceToHost, st));
+    rc = f.close();
+    if (rc == VGA_OK) *n_rows = run[1];
+    return rc;
 }
 
 struct hc_calls {
@@ -689,25 +755,17 @@ struct hc_calls {
 // what k_hc_cols relies on: calls that ascend strictly inside the graph, own letters 0 .. 4
 int hc_check_calls(vga_ctx *ctx, const char *who, const hc_calls &c, uint64_t n_bases)
 {
-    if (c.n > HC_MAX_CALLS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu calls, 2^24 at most", who, (unsigned long long)c.n);
-    if (c.n && !c.cpos) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu calls", who, (unsigned long long)c.n);
-    for (uint64_t j = 0; j < c.n; j++) {
-        if (c.cpos[j] >= n_bases) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu at base %u, the graph has %llu", who, (unsigned long long)j, c.cpos[j], (unsigned long long)n_bases);
-        if (j && c.cpos[j] <= c.cpos[j - 1]) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu does not lie behind the one before it", who, (unsigned long long)j);
-        if (c.cref && c.cref[j] > PH_REF_OTHER) return vga_set_error(ctx, VGA_ERR_ARG, "%s: call %llu has own letter %u (0 .. 4)", who, (unsigned long long)j, c.cref[j]);
-    }
-    return VGA_OK;
+    return ph_check_positions(ctx, who, "call", c.n, c.cpos, c.cref, c.cpos != nullptr, n_bases, [](uint64_t) { return VGA_OK; });
 }
 
-// The jobs (hc_jobs), then per tile of reads k_ph_obs, k_hc_tags, k_hc_cols and k_hc_count over the n_reads stored reads: *n_rows =
+// The jobs (hc_jobs), then per tile of reads k_hc_tags, k_hc_cols and k_hc_count behind k_ph_obs over the frame's reads: *n_rows =
 // J always; the J rows when cap has room for them, nothing launched otherwise.  Everything was checked by the caller.
-int hc_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d_words, const ph_sites &s, const uint32_t *ps, const uint8_t *flip,
-           const hc_calls &c, uint64_t cap, uint32_t *rows, uint64_t *n_rows)
+int hc_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, const hc_calls &c, uint64_t cap, uint32_t *rows, uint64_t *n_rows)
 {
+    vga_ctx *ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    vga_timers_reset(ctx);
-    vga_timers_collect(ctx);  // (a call that launches nothing reports no kernel)
-    if (s.n == 0 || c.n == 0 || n_reads == 0) {
+    const ph_sites &s = f.s;
+    if (s.n == 0 || c.n == 0 || f.n_reads == 0) {
         *n_rows = 0;
         return VGA_OK;
     }
@@ -715,69 +773,38 @@ int hc_run(vga_ctx *ctx, const ph_rec *recs, uint64_t n_reads, const uint32_t *d
     if (J > HC_MAX_JOBS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_haplotype_counts: %llu jobs, 2^24 at most", (unsigned long long)J);
     *n_rows = J;
     if (cap < J || J == 0) return VGA_OK;
-    const uint32_t H = (uint32_t)s.n, C = (uint32_t)c.n;
-    std::vector<uint32_t> set_of, host, jobs(3 * (size_t)J);
-    const uint32_t S = ph_group_sets(H, ps, flip, set_of, host);
+    const uint32_t H = f.H, C = (uint32_t)c.n, S = f.group(ps, flip);
+    std::vector<uint32_t> jobs(3 * (size_t)J);
     hc_jobs(c.n, c.cpos, s.n, s.pos, ps, J, jobs.data());
     for (uint64_t j = J; j-- > 0;) {  // (c, ps) pairs become c, set index, ps, from the back: in place
         const uint32_t cj = jobs[2 * j], pj = jobs[2 * j + 1];
         jobs[3 * j] = cj;
-        jobs[3 * j + 1] = set_of[pj - 1u];
+        jobs[3 * j + 1] = f.set_of[pj - 1u];
         jobs[3 * j + 2] = pj;
     }
-    const size_t host_words = 2 * (size_t)S + 1u + H;
-    const uint32_t T = ph_tile_reads(n_reads, (uint64_t)H + S + C);
-    vga_dbuf<ph_rec> d_recs;
-    vga_dbuf<uint32_t> d_pos, d_tile, d_sets, d_jobs, d_rows;  // d_pos: pos, then cpos; d_tile: obs, cols, tags
-    vga_dbuf<uint8_t> d_bytes;                                 // x, y, ref, cref
-    const size_t obs_words = (size_t)H * T / 4u, cols_words = (size_t)C * T / 4u, tag_words = (size_t)S * T / 4u;
-    VGA_HIP_CHECK_OOM(ctx, d_recs.reserve(n_reads));
-    VGA_HIP_CHECK_OOM(ctx, d_pos.reserve((size_t)H + C));
-    VGA_HIP_CHECK_OOM(ctx, d_bytes.reserve((size_t)H * 3 + C));
-    VGA_HIP_CHECK_OOM(ctx, d_tile.reserve(obs_words + cols_words + tag_words));
-    VGA_HIP_CHECK_OOM(ctx, d_sets.reserve(host_words));
-    VGA_HIP_CHECK_OOM(ctx, d_jobs.reserve(3 * (size_t)J));
+    vga_dbuf<uint32_t> d_calls, d_rows;  // d_calls: cpos, the bytes of cref in whole words, then the jobs
+    VGA_HIP_CHECK_OOM(ctx, d_calls.reserve(C + (C + 3u) / 4u + 3 * (size_t)J));
     VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)J * HC_ROW));
-    uint8_t *d_x = d_bytes.p, *d_y = d_bytes.p + H, *d_ref = d_bytes.p + 2 * (size_t)H, *d_cref = d_bytes.p + 3 * (size_t)H;
-    uint32_t *d_cpos = d_pos.p + H, *d_obs = d_tile.p, *d_cols = d_tile.p + obs_words;
-    uint8_t *d_tags = (uint8_t *)(d_tile.p + obs_words + cols_words);
-    const uint32_t *d_set_start = d_sets.p, *d_order = d_sets.p + 2 * (size_t)S + 1u;
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_recs.p, recs, n_reads * sizeof(ph_rec), hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, s.pos, (size_t)H * 4, hipMemcpyHostToDevice, st));
+    uint32_t *d_cpos = d_calls.p, *d_jobs = d_cpos + C + (C + 3u) / 4u;
+    uint8_t *d_cref = (uint8_t *)(d_cpos + C);
+    int rc = f.open(C, S);  // the tile: obs, cols, tags (every tag byte that is counted is written)
+    if (rc != VGA_OK) return rc;
+    uint32_t *d_cols = f.d_tile.p + f.obs_words;
+    uint8_t *d_tags = (uint8_t *)(f.d_tile.p + f.clear_words);
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs, jobs.data(), 3 * (size_t)J * 4, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_cpos, c.cpos, (size_t)C * 4, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_x, s.x, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_y, s.y, H, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_ref, s.ref, H, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_cref, c.cref, C, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_sets.p, host.data(), host_words * 4, hipMemcpyHostToDevice, st));
-    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs.p, jobs.data(), 3 * (size_t)J * 4, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_rows.p, 0, (size_t)J * HC_ROW * 4, st));
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
-        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_tile.p, 0, (obs_words + cols_words) * 4, st));  // (every tag byte that is counted is written)
-        int t = vga_timer_begin(ctx, "k_ph_obs", 0, st);
-        hipLaunchKernelGGL(k_ph_obs, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, H, d_pos.p, d_x, d_y, d_ref, T, d_obs);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_hc_tags", (uint64_t)(H + S) * n, st);
-        hipLaunchKernelGGL(k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), 0, st, n, T, (const uint8_t *)d_obs, S, d_set_start, d_order,
-                           d_tags);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_hc_cols", 0, st);
-        hipLaunchKernelGGL(k_hc_cols, dim3(n), dim3(64), 0, st, n, d_recs.p + r0, d_words, C, (const uint32_t *)d_cpos, (const uint8_t *)d_cref, T, d_cols);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_hc_count", 2 * J * n, st);
-        hipLaunchKernelGGL(k_hc_count, dim3((uint32_t)J), dim3(HC_COUNT_BLOCK), 0, st, (uint32_t)J, T, n, (const uint32_t *)d_jobs.p, (const uint8_t *)d_tags,
-                           (const uint8_t *)d_cols, d_rows.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-    }
+    rc = f.each_tile([&](uint64_t r0, uint32_t n) {
+        int rc = ph_launch(ctx, "k_hc_tags", (uint64_t)(H + S) * n, k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), n, f.T, (const uint8_t *)f.d_tile.p, S,
+                           f.d_sets.p, f.d_sets.p + 2 * (size_t)S + 1u, d_tags);
+        if (rc == VGA_OK) rc = ph_launch(ctx, "k_hc_cols", 0, k_hc_cols, dim3(n), dim3(64), n, f.d_recs.p + r0, f.d_words, C, d_cpos, d_cref, f.T, d_cols);
+        if (rc == VGA_OK) rc = ph_launch(ctx, "k_hc_count", 2 * J * n, k_hc_count, dim3((uint32_t)J), dim3(HC_COUNT_BLOCK), J, f.T, n, d_jobs, d_tags, (const uint8_t *)d_cols, d_rows.p);
+        return rc;
+    });
+    if (rc != VGA_OK) return rc;
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(rows, d_rows.p, (size_t)J * HC_ROW * 4, hipMemcpyDeviceToHost, st));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    vga_timers_collect(ctx);
-    return VGA_OK;
+    return f.close();
 }
 
 }  // namespace
@@ -786,18 +813,12 @@ extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *p
                                uint64_t *n_reads)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ph_state *ph = ph_active(ctx);
-    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_links: the store is off (vga_phase_begin)");
-    ph_sites s = {n_sites, pos, x, y, nullptr};
-    const int rc = ph_check_sites(ctx, "vga_phase_links", s, ctx->index.seq_length, links && site_reads);
+    const ph_sites s = {n_sites, pos, x, y, nullptr};
+    const int rc = ph_check_store(ctx, "vga_phase_links", s, links && site_reads);
     if (rc != VGA_OK) return rc;
-    std::vector<uint8_t> ref(n_sites + 1);
-    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
-    s.ref = ref.data();
-    if (n_reads) *n_reads = ph->recs.size();
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    return ph_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, links, site_reads);
+    ph_frame f(ctx, s);
+    f.from_store(n_reads);
+    return ph_run(f, links, site_reads);
 }
 
 extern "C" int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
@@ -808,32 +829,22 @@ extern "C" int vga_phase_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_
     const ph_sites s = {n_sites, pos, x, y, ref};
     const int rc = ph_check_lists(ctx, "vga_phase_links_lists", n_bases, n_reads, recs, n_words, words, s, links && site_reads);
     if (rc != VGA_OK) return rc;
-    const ph_rec *rr = (const ph_rec *)recs;
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    vga_dbuf<uint32_t> d_words;
-    const int up = ph_upload_words(ctx, n_words, words, d_words);
-    if (up != VGA_OK) return up;
-    return ph_run(ctx, rr, n_reads, d_words.p, s, links, site_reads);
+    ph_frame f(ctx, s);
+    const int up = f.from_lists(n_reads, recs, n_words, words);
+    return up != VGA_OK ? up : ph_run(f, links, site_reads);
 }
 
 extern "C" int vga_phase_tags(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps, const uint8_t *flip,
                               uint64_t cap, uint32_t *rows, uint64_t *n_rows, uint64_t *n_reads)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ph_state *ph = ph_active(ctx);
-    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_tags: the store is off (vga_phase_begin)");
-    ph_sites s = {n_sites, pos, x, y, nullptr};
-    int rc = ph_check_sites(ctx, "vga_phase_tags", s, ctx->index.seq_length, true);
+    const ph_sites s = {n_sites, pos, x, y, nullptr};
+    int rc = ph_check_store(ctx, "vga_phase_tags", s, true);
     if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_phase_tags", n_sites, ps, flip, cap, rows, n_rows);
     if (rc != VGA_OK) return rc;
-    std::vector<uint8_t> ref(n_sites + 1);
-    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
-    s.ref = ref.data();
-    if (n_reads) *n_reads = ph->recs.size();
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    return ph_tag_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, ps, flip, cap, rows, n_rows);
+    ph_frame f(ctx, s);
+    f.from_store(n_reads);
+    return ph_tag_run(f, ps, flip, cap, rows, n_rows);
 }
 
 extern "C" int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
@@ -845,35 +856,26 @@ extern "C" int vga_phase_tags_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_r
     int rc = ph_check_lists(ctx, "vga_phase_tags_lists", n_bases, n_reads, recs, n_words, words, s, true);
     if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_phase_tags_lists", n_sites, ps, flip, cap, rows, n_rows);
     if (rc != VGA_OK) return rc;
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    vga_dbuf<uint32_t> d_words;
-    const int up = ph_upload_words(ctx, n_words, words, d_words);
-    if (up != VGA_OK) return up;
-    return ph_tag_run(ctx, (const ph_rec *)recs, n_reads, d_words.p, s, ps, flip, cap, rows, n_rows);
+    ph_frame f(ctx, s);
+    const int up = f.from_lists(n_reads, recs, n_words, words);
+    return up != VGA_OK ? up : ph_tag_run(f, ps, flip, cap, rows, n_rows);
 }
 
 extern "C" int vga_haplotype_counts(vga_ctx *ctx, uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
                                     const uint32_t *ps, const uint8_t *flip, uint64_t cap, uint32_t *rows, uint64_t *n_rows, uint64_t *n_reads)
 {
     if (!ctx) return VGA_ERR_ARG;
-    ph_state *ph = ph_active(ctx);
-    if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_counts: the store is off (vga_phase_begin)");
-    ph_sites s = {n_sites, pos, x, y, nullptr};
+    const ph_sites s = {n_sites, pos, x, y, nullptr};
     hc_calls c = {n_calls, cpos, nullptr};
-    int rc = ph_check_sites(ctx, "vga_haplotype_counts", s, ctx->index.seq_length, true);
+    int rc = ph_check_store(ctx, "vga_haplotype_counts", s, true);
     if (rc == VGA_OK) rc = ph_check_sets(ctx, "vga_haplotype_counts", n_sites, ps, flip, cap, rows, n_rows);
     if (rc == VGA_OK) rc = hc_check_calls(ctx, "vga_haplotype_counts", c, ctx->index.seq_length);
     if (rc != VGA_OK) return rc;
-    std::vector<uint8_t> ref(n_sites + 1), cref(n_calls + 1);
-    for (uint64_t h = 0; h < n_sites; h++) ref[h] = ph_ref_of(ctx->index.seq_fwd[pos[h]]);
-    for (uint64_t j = 0; j < n_calls; j++) cref[j] = ph_ref_of(ctx->index.seq_fwd[cpos[j]]);
-    s.ref = ref.data();
+    const std::vector<uint8_t> cref = ph_own_letters(ctx, n_calls, cpos);
     c.cref = cref.data();
-    if (n_reads) *n_reads = ph->recs.size();
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    return hc_run(ctx, ph->recs.data(), ph->recs.size(), ph->d_words, s, ps, flip, c, cap, rows, n_rows);
+    ph_frame f(ctx, s);
+    f.from_store(n_reads);
+    return hc_run(f, ps, flip, c, cap, rows, n_rows);
 }
 
 extern "C" int vga_haplotype_counts_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
@@ -889,12 +891,9 @@ extern "C" int vga_haplotype_counts_lists(vga_ctx *ctx, uint64_t n_bases, uint64
     if (rc == VGA_OK) rc = hc_check_calls(ctx, "vga_haplotype_counts_lists", c, n_bases);
     if (rc == VGA_OK && n_calls && !cref) rc = vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_counts_lists: null array with %llu calls", (unsigned long long)n_calls);
     if (rc != VGA_OK) return rc;
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    vga_dbuf<uint32_t> d_words;
-    const int up = ph_upload_words(ctx, n_words, words, d_words);
-    if (up != VGA_OK) return up;
-    return hc_run(ctx, (const ph_rec *)recs, n_reads, d_words.p, s, ps, flip, c, cap, rows, n_rows);
+    ph_frame f(ctx, s);
+    const int up = f.from_lists(n_reads, recs, n_words, words);
+    return up != VGA_OK ? up : hc_run(f, ps, flip, c, cap, rows, n_rows);
 }
 
 extern "C" int vga_haplotype_jobs(uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites, const uint32_t *pos, const uint32_t *ps, uint64_t cap, uint32_t *jobs,
@@ -904,7 +903,7 @@ extern "C" int vga_haplotype_jobs(uint64_t n_calls, const uint32_t *cpos, uint64
     for (uint64_t j = 1; j < n_calls; j++)
         if (cpos[j] <= cpos[j - 1]) return VGA_ERR_ARG;
     for (uint64_t h = 0; h < n_sites; h++)
-        if ((h && pos[h] <= pos[h - 1]) || ps[h] < 1u || ps[h] > h + 1u || ps[ps[h] - 1u] != ps[h]) return VGA_ERR_ARG;
+        if ((h && pos[h] <= pos[h - 1]) || !ph_set_named(ps, h)) return VGA_ERR_ARG;
     *n_jobs = hc_jobs(n_calls, cpos, n_sites, pos, ps, cap, jobs);
     return VGA_OK;
 }

@@ -197,6 +197,35 @@ def test_seam_nothing_to_tag(ctx):
     assert ctx.phase_tags_lists([[0, 0, 0], [0, 2, 0]], [8 << 1, (12 << 1) | 1], 20, [3, 7], [0, 1], [2, 3], [0, 3], [1, 1], [0, 0]).shape == (0, 4)
 
 
+def test_a_call_that_launches_nothing_reports_no_kernel(drb1):
+    """links, tags and counts, from lists and from the store, without sites and without reads: kernel_times() holds the kernels of the
+    last call, so none -- not those of the call that launched before it"""
+    p = pkg()
+    sites = ([3, 7], [0, 1], [2, 3])
+    lists = ([[0, 2, 0]], [0 << 1, (10 << 1) | 1], 20)
+    no_reads, no_sites = (np.zeros((0, 3), dtype=np.uint32), [], 20), ([], [], [])
+    c = p.Context(0)
+    try:
+        upload_oracle_index(c, drb1)
+        c.pileup_begin()
+        c.phase_begin()
+        c.phase_reset()
+        quiet = [lambda: c.phase_links_lists(*lists, *no_sites, []), lambda: c.phase_links_lists(*no_reads, *sites, [0, 3]),
+                 lambda: c.phase_tags_lists(*lists, *no_sites, [], [], []), lambda: c.phase_tags_lists(*no_reads, *sites, [0, 3], [1, 1], [0, 0]),
+                 lambda: c.haplotype_counts_lists(*lists, [5], [0], *no_sites, [], [], []),
+                 lambda: c.haplotype_counts_lists(*no_reads, [5], [0], *sites, [0, 3], [1, 1], [0, 0]),
+                 lambda: c.phase_links(*no_sites), lambda: c.phase_links(*sites),
+                 lambda: c.phase_tags(*no_sites, [], []), lambda: c.phase_tags(*sites, [1, 1], [0, 0]),
+                 lambda: c.haplotype_counts([5], *no_sites, [], []), lambda: c.haplotype_counts([5], *sites, [1, 1], [0, 0])]
+        for k, call in enumerate(quiet):
+            links, sr = c.phase_links_lists(*lists, *sites, [0, 3])   # one read over both sites: it launches
+            assert sr.tolist() == [[1, 0, 0], [0, 1, 0]] and {"k_ph_obs", "k_ph_link"} <= {t["name"] for t in c.kernel_times()}
+            call()
+            assert not [t["name"] for t in c.kernel_times() if t["name"].startswith("k_")], (k, c.kernel_times())
+    finally:
+        c.close()
+
+
 def test_seam_refusals_leave_the_outputs_alone(ctx):
     """everything vga_phase_links_lists refuses and what the sets add: VGA_ERR_ARG, nothing launched, rows and n_rows untouched,
     the context usable afterwards"""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import hapcall_cases as H
+import haplotag_ref
 import haplotype_calls_ref as ref
 import phase_cases as P
 import phase_ref
@@ -181,6 +182,37 @@ def test_seam_three_tiles_add_up(ctx, monkeypatch):
     assert np.array_equal(small, whole) and np.array_equal(two, whole)
     monkeypatch.setenv("VGA_PHASE_READ_TILE", "64")
     same(seam(ctx, case, cap=0), want, "tiles of 64, asked again")
+
+
+def test_seam_links_tags_and_counts_in_any_order(ctx, monkeypatch):
+    """the three calls that share the frame of a tile (the reads, the sites, the tile behind k_ph_obs) on one case and one context,
+    each of them first, in the middle and last: 129 reads in tiles of 64, 64 and 1, nine sites (the window of eight and one more), the
+    sets of the chain on the case's own links.  Every result equals its reference, so it is the same whatever ran before it."""
+    case = P.random_case("frame", 129, 9, seed=23)
+    recs, words = P.pack(case.reads)
+    obs = phase_ref.obs_lists(recs, words, case.pos, case.x, case.y, case.ref)
+    links, site_reads = phase_ref.tables(obs, 9)
+    ps, flip, _ = pkg().binding.phase_chain(links)
+    h = H.with_calls(case, 20, ps, flip, seed=23)
+    tags, rows = haplotag_ref.table(obs, ps, flip), want_rows(h)
+    # four sets, one of them inside the span of another, a flipped site; the one read of the last tile has tag rows
+    assert ps.tolist() == [1, 2, 3, 2, 2, 2, 7, 2, 2] and flip.any() and tags[-1, 0] == 128 and len(rows) > 9 and rows[:, 2:].sum() > 0
+    monkeypatch.setenv("VGA_PHASE_READ_TILE", "64")
+    sites = (case.n_bases, case.pos, case.x, case.y, case.ref)
+
+    def run(name):
+        if name == "links":
+            got = ctx.phase_links_lists(recs, words, *sites)
+            assert got[0].dtype == np.uint32 and np.array_equal(got[0], links) and np.array_equal(got[1], site_reads), order
+        elif name == "tags":
+            same(ctx.phase_tags_lists(recs, words, *sites, ps, flip), tags, (order, name))
+        else:
+            same(seam(ctx, h), rows, (order, name))
+        assert launches(ctx).get("k_ph_obs") == 3, (order, name, launches(ctx))
+
+    for order in (("links", "tags", "counts"), ("counts", "links", "tags"), ("tags", "counts", "links")):
+        for name in order:
+            run(name)
 
 
 def raw_lists(c, case, cap, rows, n_rows, recs=None, words=None, null=(), n_bases=None):
