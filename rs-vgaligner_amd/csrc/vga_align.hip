@@ -49,11 +49,7 @@ struct align_call {
     const bool on_device = !sw.sg_host;
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     vga_trace tr{"align"};
-    cov_state *const lists;  // the run lists of the problems are kept: coverage or path support is on
-    cov_state *const cov;
-    ps_state *const ps;
-    pu_state *const pu;      // the pileup is counted: event lists of its own
-    ia_state *const ia;      // the inserted letters are counted: event lists of their own
+    ps_state *const ps;  // path support is scored: it reads the run lists that coverage makes
     // ---- plan (vga_align_plan.hpp); the per-problem arrays are in launch order on the device route, in list order on the host's
     std::vector<uint64_t> prob_read, prob_chain, read_prob0;
     std::vector<uint32_t> slot_of;  // where the q-th (read, chain) pair of the selection sits among the problems
@@ -77,8 +73,7 @@ struct align_call {
     vga_result_guard<vga_align_result, vga_align_result_free> res;
 
     align_call(vga_batch *batch, const vga_map_result *chains, uint32_t best_n, const vga_poa_params *p)
-        : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), lists(cov_lists_active(batch->ctx)), cov(cov_active(batch->ctx)),
-          ps(ps_active(batch->ctx)), pu(pu_active(batch->ctx)), ia(ia_active(batch->ctx)) {}
+        : ctx(batch->ctx), b(batch), m(chains), align_best_n(best_n), params(p), R(batch->n_reads), ps(ps_active(batch->ctx)) {}
 
     uint32_t qlen(uint64_t r) const { return (uint32_t)(b->read_off[r + 1] - b->read_off[r]); }
     // VGA_STRANDS_BOTH: a read whose chains came from its reverse complement is aligned as that sequence
@@ -120,9 +115,12 @@ int align_call::reverse_complements()
 int align_call::plan()
 {
     // the list makers read the subgraph store's handles on the device
-    const char *refused = on_device ? nullptr : cov ? "read coverage is not counted" : ps ? "path support is not scored" : pu ? "the pileup is not counted" : ia ? "the inserted letters are not counted" : nullptr;
-    if (refused)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_align_batch: %s under VGA_SUBGRAPH=host (the subgraph handles are then on the host only)", refused);
+    const char *refused = nullptr;
+    for (const oplist_maker *mk : oplist_makers()) {
+        if (on_device || refused) break;
+        refused = mk->counting(ctx) ? mk->text.refusal : mk == &cov_maker() && ps ? OPLIST_REFUSAL_PATHS : nullptr;
+    }
+    if (refused) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, OPLIST_ERR_REFUSED, refused);
     align_select(m, align_best_n, prob_read, prob_chain, read_prob0);
     n = prob_read.size();
     proxy.resize(n);
@@ -272,35 +270,32 @@ void align_call::pick_winners()
     });
 }
 
-// coverage, path support, the pileup and the insertion table count the reported record of every read and nothing else
+// The list makers, in the table's order, and path support count the reported record of every read and nothing else.  Per maker:
+// the winners' lists are staged, and added while its counters are on; path support scores from the run lists coverage staged.
 int align_call::count_winners()
 {
+    if (std::none_of(oplist_makers().begin(), oplist_makers().end(), [&](const oplist_maker *mk) { return mk->making(ctx) != nullptr; })) return VGA_OK;
     std::vector<uint32_t> winners, reads;
     for (uint64_t r = 0; r < R; r++)
         if (pick[r] >= 0) { winners.push_back((uint32_t)pick[r]); reads.push_back((uint32_t)r); }
     int rc = VGA_OK;
-    cov_win_view v;
-    if (lists && (rc = cov_stage_winners(ctx, lists, winners, v)) != VGA_OK) return rc;
-    if (cov) {
-        if ((rc = cov_add_winners(ctx, cov, winners.size())) != VGA_OK) return rc;
-        tr.mark("coverage");
-    }
-    if (ps) {
-        std::vector<uint64_t> off;
-        std::vector<uint32_t> len;
-        if (ps->pe)  // the edit distance is on: where each winner's query sits in the batch on the device
-            for (uint32_t r : reads) { off.push_back(q_off(r)); len.push_back(qlen(r)); }
-        const pe_queries q = {b->d_reads, off.data(), len.data()};
-        if ((rc = ps_score_winners(ctx, ps, v, reads, R, &q)) != VGA_OK) return rc;
-        tr.mark("path support");
-    }
-    if (pu) {  // from lists of its own
-        if ((rc = pu_add_winners(ctx, pu, winners)) != VGA_OK) return rc;
-        tr.mark("pileup");
-    }
-    if (ia) {
-        if ((rc = ia_add_winners(ctx, ia, winners)) != VGA_OK) return rc;
-        tr.mark("insertions");
+    for (const oplist_maker *mk : oplist_makers()) {
+        oplist_state *s = mk->making(ctx);
+        if (!s) continue;
+        if (!winners.empty() && (rc = s->lists.stage_winners(ctx, winners, mk->text)) != VGA_OK) return rc;
+        if (mk->counting(ctx)) {
+            if (!winners.empty() && (rc = mk->add(ctx, s, winners.size())) != VGA_OK) return rc;
+            tr.mark(mk->text.mark);
+        }
+        if (mk == &cov_maker() && ps) {
+            std::vector<uint64_t> off;
+            std::vector<uint32_t> len;
+            if (ps->pe)  // the edit distance is on: where each winner's query sits in the batch on the device
+                for (uint32_t r : reads) { off.push_back(q_off(r)); len.push_back(qlen(r)); }
+            const pe_queries q = {b->d_reads, off.data(), len.data()};
+            if ((rc = ps_score_winners(ctx, ps, cov_staged_winners(cov_lists_active(ctx), winners.size()), reads, R, &q)) != VGA_OK) return rc;
+            tr.mark("path support");
+        }
     }
     return VGA_OK;
 }
@@ -388,7 +383,7 @@ static int vga_align_batch_impl(vga_batch *b, const vga_map_result *m, uint32_t 
     if ((rc = c.run_poa()) != VGA_OK) return rc;
     if ((rc = c.begin_result()) != VGA_OK) return rc;
     c.pick_winners();
-    if ((c.lists || c.pu || c.ia) && (rc = c.count_winners()) != VGA_OK) return rc;
+    if ((rc = c.count_winners()) != VGA_OK) return rc;
     if ((rc = c.fill_result()) != VGA_OK) return rc;
     *out = c.res.release();
     return VGA_OK;

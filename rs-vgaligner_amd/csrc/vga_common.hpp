@@ -344,3 +344,20 @@ int vga_timer_begin(vga_ctx *ctx, const char *name, uint64_t bytes, hipStream_t 
 void vga_timer_end(vga_ctx *ctx, int idx);
 void vga_timers_collect(vga_ctx *ctx);  // requires the stream to be synchronised
 float vga_timer_sum(const vga_ctx *ctx, const char *prefix);
+
+// The one timed launch: `kernel` on `stream` under a timer of the kernel's name; what hipGetLastError says afterwards
+template <typename... P, typename... A>
+hipError_t vga_launch_on(vga_ctx *ctx, hipStream_t stream, const char *name, uint64_t bytes, void (*kernel)(P...), dim3 grid, dim3 block, A... args)
+{
+    const int t = vga_timer_begin(ctx, name, bytes, stream);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<P>(args)...);
+    vga_timer_end(ctx, t);
+    return hipGetLastError();
+}
+// ... on the context's stream: VGA_OK, or the error that was set
+template <typename... P, typename... A>
+int vga_launch(vga_ctx *ctx, const char *name, uint64_t bytes, void (*kernel)(P...), dim3 grid, dim3 block, A... args)
+{
+    VGA_HIP_CHECK(ctx, vga_launch_on(ctx, ctx->stream, name, bytes, kernel, grid, block, args...));
+    return VGA_OK;
+}

@@ -96,12 +96,10 @@ __global__ __launch_bounds__(1024) void k_cov_depth(const uint32_t *__restrict__
 }  // namespace
 
 // The counters of a context's index while counting is on (vga_dev_index::cov: released with the index), and the lists
-struct cov_state {
+struct cov_state : oplist_state {
     uint32_t users = 0;  // COV_USER_*: who reads the lists (the counters below exist while COV_USER_COVERAGE is among them)
-    uint32_t seq_length = 0, n_nodes = 0, n_edges = 0;
+    uint32_t n_nodes = 0, n_edges = 0;
     vga_dbuf<uint32_t> d_diff, d_node, d_edge, d_depth;
-    uint64_t n_alignments = 0;
-    oplist_call lists;  // of the vga_align_batch call in progress
 };
 
 cov_state *cov_lists_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.cov.get() : nullptr; }
@@ -113,9 +111,9 @@ cov_state *cov_active(vga_ctx *ctx)
 
 int cov_lists_acquire(vga_ctx *ctx, uint32_t user, const char *who)
 {
-    if (!ctx->index.cov && !(ctx->index.cov = vga_make_owned<cov_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "%s: out of host memory", who);
-    ctx->index.cov->users |= user;
-    return VGA_OK;
+    const int rc = oplist_make(ctx, ctx->index.cov, who);
+    if (rc == VGA_OK) ctx->index.cov->users |= user;
+    return rc;
 }
 
 void cov_lists_release(vga_ctx *ctx, uint32_t user)
@@ -127,19 +125,12 @@ void cov_lists_release(vga_ctx *ctx, uint32_t user)
     if (user == COV_USER_COVERAGE) { cv->d_diff.release(); cv->d_node.release(); cv->d_edge.release(); cv->d_depth.release(); }
 }
 
-oplist_call &cov_lists(cov_state *cv) { return cv->lists; }
-
-hipError_t cov_enqueue_runs(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                            const uint32_t *ids, const sg_store &store)
+cov_win_view cov_staged_winners(const cov_state *cv, size_t nw)
 {
-    return lists.enqueue(ctx, st, slot, oset, nb, "k_cov_runs", [&](cov_rec *d_recs) {
-        hipLaunchKernelGGL(k_cov_runs, dim3(nb), dim3(64), 0, st, nb, b.probs, b.outs, b.ops, b.orow, b.rows, b.ntab, ids, store.d_off,
-                           (uint32_t)store.split, store.part[0].d_handles, store.part[1].d_handles, ctx->index.d_node_start,
-                           (uint32_t)ctx->index.n_nodes, lists.d_lists.p, lists.list_words, lists.d_cur.p, d_recs);
-    });
+    return nw ? cov_win_view{cv->lists.d_win.p, cv->lists.d_lists.p, cv->lists.d_host_lists.p} : cov_win_view{nullptr, nullptr, nullptr};
 }
 
-void cov_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
+static void cov_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
 {
     std::vector<uint32_t> nodes;
     oplist_runs_host runs;
@@ -151,90 +142,53 @@ void cov_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
     lists.keep_host(p, nodes, runs.ev, 0u);
 }
 
-int cov_stage_winners(vga_ctx *ctx, cov_state *cv, const std::vector<uint32_t> &winners, cov_win_view &v)
+static int cov_add(vga_ctx *ctx, oplist_state *s, size_t nw)
 {
-    v = cov_win_view{nullptr, nullptr, nullptr};
-    if (winners.empty()) return VGA_OK;
-    const int rc = cv->lists.stage_winners(ctx, winners, "coverage", "run");
-    if (rc == VGA_OK) v = cov_win_view{cv->lists.d_win.p, cv->lists.d_lists.p, cv->lists.d_host_lists.p};
-    return rc;
+    cov_state *cv = static_cast<cov_state *>(s);
+    const vga_dev_index &ix = ctx->index;
+    return oplist_add_staged(ctx, cv, nw, "k_cov_add", k_cov_add, [] { return VGA_OK; }, ix.d_edge_idx, ix.d_edges_to, ix.d_edges, cv->n_nodes, cv->seq_length, cv->d_diff.p,
+                             cv->d_node.p, cv->d_edge.p);
 }
 
-int cov_add_winners(vga_ctx *ctx, cov_state *cv, size_t nw)
+static std::vector<oplist_counter> cov_counters(const vga_dev_index &ix, oplist_state *s)
 {
-    if (nw == 0) return VGA_OK;
-    hipStream_t st = ctx->stream;
-    const vga_dev_index &ix = ctx->index;
-    const int t = vga_timer_begin(ctx, "k_cov_add", 0, st);
-    hipLaunchKernelGGL(k_cov_add, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, cv->lists.d_win.p, cv->lists.d_lists.p, cv->lists.d_host_lists.p, ix.d_edge_idx,
-                       ix.d_edges_to, ix.d_edges, cv->n_nodes, cv->seq_length, cv->d_diff.p, cv->d_node.p, cv->d_edge.p);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    cv->n_alignments += nw;
-    vga_timers_collect(ctx);  // (poa_run collected before this launch: once more, with it)
-    return VGA_OK;
+    cov_state *cv = static_cast<cov_state *>(s);
+    cv->n_nodes = (uint32_t)ix.n_nodes; cv->n_edges = (uint32_t)ix.n_edges;
+    return {{&cv->d_diff, (size_t)cv->seq_length + 1, true}, {&cv->d_node, (size_t)cv->n_nodes + 1, true}, {&cv->d_edge, (size_t)cv->n_edges + 1, true},
+            {&cv->d_depth, (size_t)cv->seq_length + 1, false}};
+}
+
+// The lists are made while any reader is on (path support holds them too: the users mask), the counters while coverage is
+const oplist_maker &cov_maker()
+{
+    static const oplist_maker m = {
+        OPLIST_TEXT_COV,
+        [](vga_ctx *ctx) -> oplist_state * { return cov_lists_active(ctx); },
+        [](vga_ctx *ctx) -> oplist_state * { return cov_active(ctx); },
+        &poa_switches::has_cov_words, &poa_switches::cov_words,
+        [](vga_ctx *ctx, oplist_call &lists, const oplist_launch &L) { return oplist_enqueue<false>(ctx, lists, L, "k_cov_runs", k_cov_runs); },
+        cov_keep_from_ops,
+        cov_add,
+        [](const vga_dev_index &ix) { return ix.seq_length < (1ull << 31) && ix.n_nodes < (1ull << 31) && ix.n_edges < (1ull << 32); },
+        [](vga_ctx *ctx, const char *fn) { return cov_lists_acquire(ctx, COV_USER_COVERAGE, fn); },
+        [](vga_ctx *ctx) { cov_lists_release(ctx, COV_USER_COVERAGE); },
+        cov_counters,
+        nullptr,
+    };
+    return m;
 }
 
 // ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
-static int cov_zero(vga_ctx *ctx, cov_state *cv)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(cv->d_diff.p, 0, ((size_t)cv->seq_length + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(cv->d_node.p, 0, ((size_t)cv->n_nodes + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(cv->d_edge.p, 0, ((size_t)cv->n_edges + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    cv->n_alignments = 0;
-    return VGA_OK;
-}
-
-extern "C" int vga_coverage_begin(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_coverage_begin: no index uploaded");
-    const vga_dev_index &ix = ctx->index;
-    if (ix.seq_length >= (1ull << 31) || ix.n_nodes >= (1ull << 31) || ix.n_edges >= (1ull << 32))
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_coverage_begin: graph too large for 32-bit positions");
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    int rc = cov_lists_acquire(ctx, COV_USER_COVERAGE, "vga_coverage_begin");
-    if (rc != VGA_OK) return rc;
-    cov_state *cv = ctx->index.cov.get();
-    cv->seq_length = (uint32_t)ix.seq_length; cv->n_nodes = (uint32_t)ix.n_nodes; cv->n_edges = (uint32_t)ix.n_edges;
-    hipError_t e = cv->d_diff.reserve((size_t)cv->seq_length + 1);
-    if (e == hipSuccess) e = cv->d_node.reserve((size_t)cv->n_nodes + 1);
-    if (e == hipSuccess) e = cv->d_edge.reserve((size_t)cv->n_edges + 1);
-    if (e == hipSuccess) e = cv->d_depth.reserve((size_t)cv->seq_length + 1);
-    rc = e == hipSuccess ? cov_zero(ctx, cv) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_coverage_begin: %s", hipGetErrorString(e));
-    if (rc != VGA_OK) cov_lists_release(ctx, COV_USER_COVERAGE);
-    return rc;
-}
-
-extern "C" int vga_coverage_reset(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    cov_state *cv = cov_active(ctx);
-    if (!cv) return vga_set_error(ctx, VGA_ERR_ARG, "vga_coverage_reset: counting is off (vga_coverage_begin)");
-    (void)hipSetDevice(ctx->device);
-    return cov_zero(ctx, cv);
-}
-
-extern "C" int vga_coverage_end(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    cov_lists_release(ctx, COV_USER_COVERAGE);
-    return VGA_OK;
-}
+extern "C" int vga_coverage_begin(vga_ctx *ctx) { return oplist_begin(ctx, cov_maker(), __func__); }
+extern "C" int vga_coverage_reset(vga_ctx *ctx) { return oplist_reset(ctx, cov_maker(), __func__); }
+extern "C" int vga_coverage_end(vga_ctx *ctx) { return oplist_end(ctx, cov_maker()); }
 
 extern "C" int vga_coverage_read(vga_ctx *ctx, uint32_t *base_depth, uint32_t *node_reads, uint32_t *edge_reads, uint64_t *n_alignments)
 {
-    if (!ctx) return VGA_ERR_ARG;
-    cov_state *cv = cov_active(ctx);
-    if (!cv) return vga_set_error(ctx, VGA_ERR_ARG, "vga_coverage_read: counting is off (vga_coverage_begin)");
-    if (cv->n_alignments >= 0xFFFFFFFFull)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_coverage_read: %llu alignments counted: a 32-bit counter may have wrapped",
-                             (unsigned long long)cv->n_alignments);
+    cov_state *cv = static_cast<cov_state *>(oplist_on(ctx, cov_maker(), __func__));
+    if (!cv) return VGA_ERR_ARG;
+    const int rc = oplist_wrapped(ctx, cv, __func__);
+    if (rc != VGA_OK) return rc;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     if (base_depth && cv->seq_length) {

@@ -7,6 +7,9 @@
 // k_poa_text on the slot's stream, condenses every finished problem into a short list (the ids of the nodes its path enters, then
 // the +1 / -1 events of its runs of matched bases on the linearised graph), and k_cov_add, once the host has picked the winners,
 // adds the winners' lists to the counters: a difference array over the bases, a word per node, a word per edge slot.
+//
+// poa_run and vga_align_batch reach all of that through cov_maker() (vga_oplist.hpp: the frame of a list maker); what is declared
+// beside it is the second reader of the run lists, path support.
 #pragma once
 
 #include "vga_oplist.hpp"
@@ -15,6 +18,7 @@
 using cov_rec = oplist_rec;
 
 struct cov_state;
+const oplist_maker &cov_maker();
 // The lists have two readers: the coverage counters (k_cov_add) and path support (vga_path_support.hip: k_ps_score).  The state
 // exists, and poa_run makes lists, while either is on.
 enum : uint32_t { COV_USER_COVERAGE = 1u, COV_USER_PATHS = 2u };
@@ -25,20 +29,11 @@ cov_state *cov_lists_active(vga_ctx *ctx);
 // a reader turns itself on (creates the state if it is the first) / off (the last one out releases it)
 int cov_lists_acquire(vga_ctx *ctx, uint32_t user, const char *who);
 void cov_lists_release(vga_ctx *ctx, uint32_t user);
-// the lists of the call in progress
-oplist_call &cov_lists(cov_state *cv);
-// k_cov_runs for the nb problems staged on a slot, and the copy of their records into the slot's result set `oset`
-hipError_t cov_enqueue_runs(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                            const uint32_t *ids, const sg_store &store);
-// the host route for a problem whose list found no room: the same list from the operations as they came back
-void cov_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o);
-// the records of the winners (problem indices of the call that just ended) and the lists the host built go to the device, on the
-// context's stream; `v` is what a kernel launched on that stream afterwards reads (all null for no winners)
+// what a kernel launched on the context's stream reads once the nw winners of a call are staged (oplist_call::stage_winners): all null
+// for no winners
 struct cov_win_view {
     const cov_rec *recs;          // one per winner
     const uint32_t *lists;        // records with flags 1 index this buffer,
     const uint32_t *host_lists;   // records with flags 3 this one
 };
-int cov_stage_winners(vga_ctx *ctx, cov_state *cv, const std::vector<uint32_t> &winners, cov_win_view &v);
-// k_cov_add over the nw staged winners, on the context's stream; waits for it
-int cov_add_winners(vga_ctx *ctx, cov_state *cv, size_t nw);
+cov_win_view cov_staged_winners(const cov_state *cv, size_t nw);

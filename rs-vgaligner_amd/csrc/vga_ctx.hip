@@ -207,10 +207,12 @@ static hipEvent_t vga_event_get(vga_ctx *ctx)
     return ctx->event_pool[ctx->events_used++];
 }
 
+// a timed call starts from "nothing launched": one that returns before its collect reports no kernel, not those of the call before it
 void vga_timers_reset(vga_ctx *ctx)
 {
     ctx->timers.clear();
     ctx->events_used = 0;
+    ctx->last_times.clear();
 }
 
 int vga_timer_begin(vga_ctx *ctx, const char *name, uint64_t bytes, hipStream_t stream)

@@ -178,29 +178,15 @@ __global__ __launch_bounds__(IA_BLOCK) void k_ia_call(const T *__restrict__ tabl
 }  // namespace
 
 // The counters of a context's index while counting is on (vga_dev_index::ia: released with the index), and the lists
-struct ia_state {
-    uint32_t seq_length = 0;
+struct ia_state : oplist_state {
     vga_dbuf<uint32_t> d_counts;
-    uint64_t n_alignments = 0, n_events = 0, n_leading = 0;
-    oplist_call lists;  // of the vga_align_batch call in progress
+    uint64_t n_events = 0, n_leading = 0;
 };
 
-ia_state *ia_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.ia.get() : nullptr; }
-
-oplist_call &ia_lists(ia_state *ia) { return ia->lists; }
-
-hipError_t ia_enqueue_events(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                             const uint32_t *ids, const sg_store &store)
-{
-    return lists.enqueue(ctx, st, slot, oset, nb, "k_ia_events", [&](ia_rec *d_recs) {
-        hipLaunchKernelGGL(k_ia_events, dim3(nb), dim3(64), 0, st, nb, b.probs, b.outs, b.ops, b.orow, b.rows, b.ntab, (const char *)b.seq32, b.q, ids,
-                           store.d_off, (uint32_t)store.split, store.part[0].d_handles, store.part[1].d_handles, ctx->index.d_node_start,
-                           (uint32_t)ctx->index.n_nodes, lists.d_lists.p, lists.list_words, lists.d_cur.p, d_recs);
-    });
-}
+static ia_state *ia_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.ia.get() : nullptr; }
 
 // (the walk hands out the read base of an M only: the lambda counts the query bases itself, operations 0 and 1 consume one)
-void ia_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
+static void ia_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
 {
     std::vector<uint32_t> ev;
     bool has = false, leading = false, in_run = false;
@@ -224,90 +210,48 @@ void ia_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
     lists.keep_host(p, ev, std::vector<uint32_t>(), leading ? PU_LEADING : 0u);
 }
 
-int ia_add_winners(vga_ctx *ctx, ia_state *ia, const std::vector<uint32_t> &winners)
+static int ia_add(vga_ctx *ctx, oplist_state *s, size_t nw)
 {
-    const size_t nw = winners.size();
-    if (nw == 0) return VGA_OK;
-    const int rc = ia->lists.stage_winners(ctx, winners, "insertions", "insertion");
-    if (rc != VGA_OK) return rc;
+    ia_state *ia = static_cast<ia_state *>(s);
     uint64_t leading = 0, events = 0;
     for (size_t i = 0; i < nw; i++) {
         leading += (ia->lists.h_win.p[i].flags & PU_LEADING) ? 1u : 0u;
         events += ia->lists.h_win.p[i].n_a / IA_EVENT_WORDS;
     }
-    hipStream_t st = ctx->stream;
-    const int t = vga_timer_begin(ctx, "k_ia_add", 0, st);
-    hipLaunchKernelGGL(k_ia_add, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, ia->lists.d_win.p, ia->lists.d_lists.p, ia->lists.d_host_lists.p, ia->seq_length,
-                       ia->d_counts.p);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    ia->n_alignments += nw;
-    ia->n_events += events;
-    ia->n_leading += leading;
-    vga_timers_collect(ctx);  // (poa_run collected before this launch: once more, with it)
-    return VGA_OK;
-}
-
-// ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
-static int ia_zero(vga_ctx *ctx, ia_state *ia)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(ia->d_counts.p, 0, ((size_t)ia->seq_length * IA_COLS + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    ia->n_alignments = 0;
-    ia->n_events = 0;
-    ia->n_leading = 0;
-    return VGA_OK;
-}
-
-extern "C" int vga_insertion_begin(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_insertion_begin: no index uploaded");
-    const vga_dev_index &ix = ctx->index;
-    if (ix.seq_length >= IA_MAX_SEQ || ix.n_nodes >= (1ull << 31))
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_insertion_begin: graph too large for 26-bit positions");
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    if (!ctx->index.ia && !(ctx->index.ia = vga_make_owned<ia_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_insertion_begin: out of host memory");
-    ia_state *ia = ctx->index.ia.get();
-    ia->seq_length = (uint32_t)ix.seq_length;
-    const hipError_t e = ia->d_counts.reserve((size_t)ia->seq_length * IA_COLS + 1);
-    const int rc = e == hipSuccess ? ia_zero(ctx, ia) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_insertion_begin: %s", hipGetErrorString(e));
-    if (rc != VGA_OK) ctx->index.ia.reset();
+    const int rc = oplist_add_staged(ctx, ia, nw, "k_ia_add", k_ia_add, [] { return VGA_OK; }, ia->seq_length, ia->d_counts.p);
+    if (rc == VGA_OK) { ia->n_events += events; ia->n_leading += leading; }
     return rc;
 }
 
-extern "C" int vga_insertion_reset(vga_ctx *ctx)
+const oplist_maker &ia_maker()
 {
-    if (!ctx) return VGA_ERR_ARG;
-    ia_state *ia = ia_active(ctx);
-    if (!ia) return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_reset: counting is off (vga_insertion_begin)");
-    (void)hipSetDevice(ctx->device);
-    return ia_zero(ctx, ia);
+    static const oplist_maker m = {
+        OPLIST_TEXT_IA,
+        [](vga_ctx *ctx) -> oplist_state * { return ia_active(ctx); },
+        [](vga_ctx *ctx) -> oplist_state * { return ia_active(ctx); },
+        &poa_switches::has_ins_words, &poa_switches::ins_words,
+        [](vga_ctx *ctx, oplist_call &lists, const oplist_launch &L) { return oplist_enqueue<true>(ctx, lists, L, "k_ia_events", k_ia_events); },
+        ia_keep_from_ops,
+        ia_add,
+        [](const vga_dev_index &ix) { return ix.seq_length < IA_MAX_SEQ && ix.n_nodes < (1ull << 31); },
+        [](vga_ctx *ctx, const char *fn) { return oplist_make(ctx, ctx->index.ia, fn); },
+        [](vga_ctx *ctx) { ctx->index.ia.reset(); },
+        [](const vga_dev_index &, oplist_state *s) { return std::vector<oplist_counter>{{&static_cast<ia_state *>(s)->d_counts, (size_t)s->seq_length * IA_COLS + 1, true}}; },
+        [](oplist_state *s) { static_cast<ia_state *>(s)->n_events = static_cast<ia_state *>(s)->n_leading = 0; },
+    };
+    return m;
 }
 
-extern "C" int vga_insertion_end(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->index.ia.reset();
-    return VGA_OK;
-}
-
-static int ia_wrapped(vga_ctx *ctx, const ia_state *ia, const char *who)
-{
-    if (ia->n_alignments < 0xFFFFFFFFull) return VGA_OK;
-    return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu alignments counted: a 32-bit counter may have wrapped", who, (unsigned long long)ia->n_alignments);
-}
+// ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
+extern "C" int vga_insertion_begin(vga_ctx *ctx) { return oplist_begin(ctx, ia_maker(), __func__); }
+extern "C" int vga_insertion_reset(vga_ctx *ctx) { return oplist_reset(ctx, ia_maker(), __func__); }
+extern "C" int vga_insertion_end(vga_ctx *ctx) { return oplist_end(ctx, ia_maker()); }
 
 extern "C" int vga_insertion_read(vga_ctx *ctx, uint32_t *counts, uint64_t *n_alignments, uint64_t *n_events, uint64_t *n_leading)
 {
-    if (!ctx) return VGA_ERR_ARG;
-    ia_state *ia = ia_active(ctx);
-    if (!ia) return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_read: counting is off (vga_insertion_begin)");
-    const int rc = ia_wrapped(ctx, ia, "vga_insertion_read");
+    ia_state *ia = static_cast<ia_state *>(oplist_on(ctx, ia_maker(), __func__));
+    if (!ia) return VGA_ERR_ARG;
+    const int rc = oplist_wrapped(ctx, ia, __func__);
     if (rc != VGA_OK) return rc;
     (void)hipSetDevice(ctx->device);
     if (counts && ia->seq_length) {
@@ -345,16 +289,14 @@ int ia_run(vga_ctx *ctx, const char *who, const T *d_table, const uint32_t *d_po
     uint8_t *d_len = d_bytes.p, *d_seq = d_bytes.p + n;
     unsigned long long *d_lr = d_wide.p, *d_sr = d_wide.p + n, *d_rows = o.rows ? d_wide.p + n * (1 + IA_MAX_LEN) : nullptr;
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_flags.p, 0, 4, st));
-    const int t = vga_timer_begin(ctx, "k_ia_call", n * (IA_COLS * sizeof(T) + 9 + 8 * 9), st);
-    hipLaunchKernelGGL(k_ia_call<T>, dim3((unsigned)((n + IA_BLOCK - 1u) / IA_BLOCK)), dim3(IA_BLOCK), 0, st, d_table, d_pos, (uint32_t)n, d_len, d_lr, d_seq, d_sr, d_rows,
-                       d_flags.p);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = vga_launch(ctx, "k_ia_call", n * (IA_COLS * sizeof(T) + 9 + 8 * 9), k_ia_call<T>, dim3((unsigned)((n + IA_BLOCK - 1u) / IA_BLOCK)), dim3(IA_BLOCK), d_table, d_pos,
+                              (uint32_t)n, d_len, d_lr, d_seq, d_sr, d_rows, d_flags.p);
+    if (rc != VGA_OK) return rc;
     uint32_t h_flags = 0;
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(&h_flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
     VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     vga_timers_collect(ctx);
-    if (h_flags & 1u) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: a counter of 2^40 or more", who);
+    if (h_flags & 1u) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, OPLIST_ERR_WIDE, who);
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.length, d_len, n, hipMemcpyDeviceToHost, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.length_reads, d_lr, n * 8, hipMemcpyDeviceToHost, st));
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.seq, d_seq, n * IA_MAX_LEN, hipMemcpyDeviceToHost, st));
@@ -378,23 +320,20 @@ extern "C" int vga_insertion_call(vga_ctx *ctx, uint64_t n, const uint32_t *pos,
 {
     if (!ctx) return VGA_ERR_ARG;
     const ia_out o = {length, length_reads, seq, seq_reads, rows};
-    int rc = ia_check(ctx, "vga_insertion_call", n, o);
+    int rc = ia_check(ctx, __func__, n, o);
     if (rc != VGA_OK) return rc;
-    ia_state *ia = ia_active(ctx);
-    if (!ia) return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_call: counting is off (vga_insertion_begin)");
-    if ((rc = ia_wrapped(ctx, ia, "vga_insertion_call")) != VGA_OK) return rc;
-    if (n && !pos) return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_call: null positions");
+    ia_state *ia = static_cast<ia_state *>(oplist_on(ctx, ia_maker(), __func__));
+    if (!ia) return VGA_ERR_ARG;
+    if ((rc = oplist_wrapped(ctx, ia, __func__)) != VGA_OK) return rc;
+    if (n && !pos) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null positions", __func__);
     for (uint64_t s = 0; s < n; s++)
         if (pos[s] >= ia->seq_length)
-            return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_call: position %u of site %llu, the graph has %u bases", pos[s], (unsigned long long)s, ia->seq_length);
+            return vga_set_error(ctx, VGA_ERR_ARG, "%s: position %u of site %llu, the graph has %u bases", __func__, pos[s], (unsigned long long)s, ia->seq_length);
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
     vga_dbuf<uint32_t> d_pos;
-    if (n) {
-        VGA_HIP_CHECK_OOM(ctx, d_pos.reserve((size_t)n));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.p, pos, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return ia_run<uint32_t>(ctx, "vga_insertion_call", ia->d_counts.p, d_pos.p, n, o);
+    if ((rc = table_upload(ctx, d_pos, pos, (size_t)n)) != VGA_OK) return rc;
+    return ia_run<uint32_t>(ctx, __func__, ia->d_counts.p, d_pos.p, n, o);
 }
 
 extern "C" int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *rows_in, uint8_t *length, uint64_t *length_reads, uint8_t *seq,
@@ -402,17 +341,13 @@ extern "C" int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t
 {
     if (!ctx) return VGA_ERR_ARG;
     const ia_out o = {length, length_reads, seq, seq_reads, rows};
-    const int rc = ia_check(ctx, "vga_insertion_call_table", n, o);
+    int rc = ia_check(ctx, __func__, n, o);
     if (rc != VGA_OK) return rc;
-    if (n && !rows_in) return vga_set_error(ctx, VGA_ERR_ARG, "vga_insertion_call_table: null rows");
+    if (n && !rows_in) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null rows", __func__);
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
-    hipStream_t st = ctx->stream;
-    if (st) (void)hipStreamSynchronize(st);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     vga_dbuf<unsigned long long> d_rows;
-    if (n) {
-        VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)n * IA_COLS));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_rows.p, rows_in, (size_t)n * IA_COLS * 8, hipMemcpyHostToDevice, st));
-    }
-    return ia_run<unsigned long long>(ctx, "vga_insertion_call_table", d_rows.p, nullptr, n, o);
+    if ((rc = table_upload(ctx, d_rows, rows_in, (size_t)n * IA_COLS)) != VGA_OK) return rc;
+    return ia_run<unsigned long long>(ctx, __func__, d_rows.p, nullptr, n, o);
 }

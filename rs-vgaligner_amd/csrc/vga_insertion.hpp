@@ -37,16 +37,6 @@ static_assert(IA_MAX_LEN * 3u <= 32u && IA_MAX_SEQ * 16ull <= (1ull << 32) && IA
 // PU_LEADING for a run of insertions with no base before it
 using ia_rec = oplist_rec;
 
-struct ia_state;
-// the context's insertion state while counting is on (vga_insertion_begin), else null
-ia_state *ia_active(vga_ctx *ctx);
-// the lists of the call in progress
-oplist_call &ia_lists(ia_state *ia);
-// k_ia_events for the nb problems staged on a slot, and the copy of their records into the slot's result set `oset`
-hipError_t ia_enqueue_events(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                             const uint32_t *ids, const sg_store &store);
-// the host route for a problem whose list found no room: the same list from the operations as they came back and the query
-void ia_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o);
-// k_ia_add over the lists of the winners (problem indices of the call that just ended), on the context's stream; waits for it
-int ia_add_winners(vga_ctx *ctx, ia_state *ia, const std::vector<uint32_t> &winners);
+// all that poa_run and vga_align_batch see of it (vga_oplist.hpp: the frame of a list maker)
+const oplist_maker &ia_maker();
 #endif

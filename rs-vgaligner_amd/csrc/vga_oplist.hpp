@@ -1,8 +1,11 @@
 // vga_oplist.hpp -- what the three list makers share: coverage's k_cov_runs (vga_coverage.hip), the pileup's k_pu_events
-// (vga_pileup.hip) and the insertion table's k_ia_events (vga_insertion.hip) condense the traceback of every finished problem into a short list, and the winners' lists are counted once the
-// host has picked them.  Here is the one copy of the walk over the operations (device, and host for a list that found no room), of
-// the record of a list and of the per-call store of lists.  Each maker keeps what is its own: what counts as "in a run", what else
-// it lists, and its counters.
+// (vga_pileup.hip) and the insertion table's k_ia_events (vga_insertion.hip) condense the traceback of every finished problem into
+// a short list, and the winners' lists are counted once the host has picked them.  Here is the one copy of the walk over the
+// operations (device, and host for a list that found no room), of the record of a list, of the per-call store of lists and of the
+// host frame of a maker: the base of its state, the enqueue of its list kernel, the add of the staged winners, its begin / reset /
+// end, and the descriptor (oplist_maker) through which poa_run and vga_align_batch reach it.  Each maker keeps what is its own:
+// what counts as "in a run", what else it lists, its kernels, its counters and what it reads out.  A new maker is a .hip with
+// those, an oplist_text and an oplist_maker, and one entry of oplist_makers.
 //
 // There is a fourth reader of the same operation stream: k_poa_text (vga_poa_text.hpp, compiled into vga_poa.hip).  It is on the
 // path of every alignment, carries other state from block to block (the text's run lengths) and keeps its own copy of the
@@ -11,8 +14,10 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 
 #include "vga_common.hpp"
+#include "vga_oplist_text.hpp"
 #include "vga_poa_launch.hpp"
 #include "vga_subgraph.hpp"
 
@@ -237,20 +242,6 @@ struct oplist_call {
         host_lists.clear();
         return VGA_OK;
     }
-    // the maker's kernel for the nb problems staged on a slot (launch(recs) enqueues it on st, timed as `timer`), and the copy of
-    // their records into the slot's result set `oset`
-    template <class Launch>
-    hipError_t enqueue(vga_ctx *ctx, hipStream_t st, int slot, int oset, uint32_t nb, const char *timer, Launch &&launch)
-    {
-        hipError_t e;
-        if ((e = d_recs[slot].reserve(nb)) != hipSuccess) return e;
-        if ((e = h_recs[slot][oset].reserve(nb)) != hipSuccess) return e;
-        const int t = vga_timer_begin(ctx, timer, 0, st);
-        launch(d_recs[slot].p);
-        vga_timer_end(ctx, t);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        return hipMemcpyAsync(h_recs[slot][oset].p, d_recs[slot].p, nb * sizeof(oplist_rec), hipMemcpyDeviceToHost, st);
-    }
     // the records of a finished launch (valid once its stream is synchronised)
     const oplist_rec *launch_recs(int slot, int oset) const { return h_recs[slot][oset].p; }
     // keeps the record of problem p (a later run of the same problem replaces it)
@@ -263,16 +254,15 @@ struct oplist_call {
         host_lists.insert(host_lists.end(), b.begin(), b.end());
     }
     // the records of the winners (problem indices of the call that just ended; at least one) and the lists the host built go to
-    // the device, on the context's stream.  who / what name the maker and its list in the error for a winner without a list.
-    int stage_winners(vga_ctx *ctx, const std::vector<uint32_t> &winners, const char *who, const char *what)
+    // the device, on the context's stream.  `t` names the maker and its list in the error for a winner without a list.
+    int stage_winners(vga_ctx *ctx, const std::vector<uint32_t> &winners, const oplist_text &t)
     {
         const size_t nw = winners.size();
         VGA_HIP_CHECK(ctx, h_win.reserve(nw));
         VGA_HIP_CHECK(ctx, d_win.reserve(nw));
         for (size_t i = 0; i < nw; i++) {
             const oplist_rec &r = recs[winners[i]];
-            if ((r.flags & 3u) != 1u && (r.flags & 3u) != 3u)
-                return vga_set_error(ctx, VGA_ERR_HIP, "%s: reported alignment %zu has no %s list (flags %u)", who, i, what, r.flags);
+            if ((r.flags & 3u) != 1u && (r.flags & 3u) != 3u) return vga_set_error(ctx, VGA_ERR_HIP, OPLIST_ERR_NO_LIST, t.who, i, t.what, r.flags);
             h_win.p[i] = r;
         }
         hipStream_t st = ctx->stream;
@@ -341,3 +331,106 @@ struct oplist_runs_host {
         pg = g;
     }
 };
+
+// ------------------------------------------------------------------------------------------------ host: the frame of a maker
+// What the three states share; a maker derives its own from it and adds its counters.
+struct oplist_state {
+    uint32_t seq_length = 0;
+    uint64_t n_alignments = 0;  // counted since begin / reset
+    oplist_call lists;          // of the vga_align_batch call in progress
+};
+
+// what poa_run hands a maker's enqueue: the nb problems staged on a slot, whose records go into the slot's result set `oset`
+struct oplist_launch {
+    hipStream_t st; int slot, oset; uint32_t nb;
+    const poa_launch_bufs &b;
+    const uint32_t *ids;
+    const sg_store &store;
+};
+
+// a buffer of a maker's 32-bit counters: begin reserves `words`, begin and reset zero them unless the buffer is scratch of its read
+struct oplist_counter { vga_dbuf<uint32_t> *buf; size_t words; bool zeroed; };
+
+// One per maker, handed out by a function of its .hip (cov_maker(), pu_maker(), ia_maker(): a constant at namespace scope would be
+// emitted for the device too, where its hooks do not exist); oplist_makers() (vga_oplist.hip) is the table poa_run and
+// vga_align_batch walk, in the order in which the winners are counted.  The frame below calls the hooks.
+struct oplist_maker {
+    const oplist_text &text;
+    oplist_state *(*making)(vga_ctx *ctx);    // the state while poa_run makes its lists, else null
+    oplist_state *(*counting)(vga_ctx *ctx);  // ... while its counters are on (between its begin and end), else null
+    bool poa_switches::*has_cap; uint64_t poa_switches::*cap_words;  // its VGA_*_LIST_WORDS
+    hipError_t (*enqueue)(vga_ctx *ctx, oplist_call &lists, const oplist_launch &L);  // its list kernel behind k_poa_text: oplist_enqueue
+    void (*keep_from_ops)(oplist_call &lists, uint32_t p, const oplist_ops &o);       // the host route for a list that found no room
+    int (*add)(vga_ctx *ctx, oplist_state *s, size_t nw);                             // its add kernel over the nw staged winners: oplist_add_staged
+    bool (*fits)(const vga_dev_index &ix);                        // the graph is within oplist_text::limit
+    int (*acquire)(vga_ctx *ctx, const char *fn);                 // the state exists and counts (oplist_make), for the entry point fn
+    void (*release)(vga_ctx *ctx);
+    std::vector<oplist_counter> (*counters)(const vga_dev_index &ix, oplist_state *s);  // its device counters for this index (seq_length is set)
+    void (*zero_own)(oplist_state *s);                            // its own host counters start again (null: it has none)
+};
+const std::array<const oplist_maker *, 3> &oplist_makers();
+
+// vga_<name>_begin / _reset / _end for the entry point fn (its __func__)
+int oplist_begin(vga_ctx *ctx, const oplist_maker &m, const char *fn);
+int oplist_reset(vga_ctx *ctx, const oplist_maker &m, const char *fn);
+int oplist_end(vga_ctx *ctx, const oplist_maker &m);
+// the state while the maker counts; else (and for a null context) null, and the error of fn is set: the caller returns VGA_ERR_ARG
+oplist_state *oplist_on(vga_ctx *ctx, const oplist_maker &m, const char *fn);
+// VGA_ERR_UNSUPPORTED once a 32-bit counter may have wrapped
+int oplist_wrapped(vga_ctx *ctx, const oplist_state *s, const char *fn);
+
+// oplist_maker::acquire of a maker that owns its slot of the index alone
+template <class S>
+int oplist_make(vga_ctx *ctx, vga_owned<S> &slot, const char *fn)
+{
+    if (!slot && !(slot = vga_make_owned<S>())) return vga_set_error(ctx, VGA_ERR_NOMEM, OPLIST_ERR_NO_MEMORY, fn);
+    return VGA_OK;
+}
+
+// oplist_maker::enqueue: `kernel` over the problems of L on its stream, timed as `timer`, and the copy of their records to the host.
+// The argument pack is the one every list kernel takes; QUERY: the gathered node sequences and the queries go in (opl_open<true>)
+template <bool QUERY, typename... P>
+hipError_t oplist_enqueue(vga_ctx *ctx, oplist_call &lists, const oplist_launch &L, const char *timer, void (*kernel)(P...))
+{
+    vga_dbuf<oplist_rec> &d_recs = lists.d_recs[L.slot];
+    vga_hbuf<oplist_rec> &h_recs = lists.h_recs[L.slot][L.oset];
+    hipError_t e;
+    if ((e = d_recs.reserve(L.nb)) != hipSuccess) return e;
+    if ((e = h_recs.reserve(L.nb)) != hipSuccess) return e;
+    auto launch = [&](auto... query_side) {
+        return vga_launch_on(ctx, L.st, timer, 0, kernel, dim3(L.nb), dim3(64), L.nb, L.b.probs, L.b.outs, L.b.ops, L.b.orow, L.b.rows, L.b.ntab, query_side..., L.ids,
+                             L.store.d_off, (uint32_t)L.store.split, L.store.part[0].d_handles, L.store.part[1].d_handles, ctx->index.d_node_start,
+                             (uint32_t)ctx->index.n_nodes, lists.d_lists.p, lists.list_words, lists.d_cur.p, d_recs.p);
+    };
+    if constexpr (QUERY) e = launch((const char *)L.b.seq32, L.b.q);
+    else e = launch();
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(h_recs.p, d_recs.p, L.nb * sizeof(oplist_rec), hipMemcpyDeviceToHost, L.st);
+}
+
+// oplist_maker::add: `kernel` (n, records, lists, host lists, own ...) over the nw staged winners on the context's stream, then
+// before_wait() on the same stream (a failing one still drains it), the wait, and the call's timers once more with this launch
+template <class Step, typename... P, typename... A>
+int oplist_add_staged(vga_ctx *ctx, oplist_state *s, size_t nw, const char *name, void (*kernel)(P...), Step &&before_wait, A... own)
+{
+    int rc = vga_launch(ctx, name, 0, kernel, dim3((unsigned)nw), dim3(64), (uint32_t)nw, s->lists.d_win.p, s->lists.d_lists.p, s->lists.d_host_lists.p, own...);
+    if (rc != VGA_OK) return rc;
+    if ((rc = before_wait()) != VGA_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    s->n_alignments += nw;
+    vga_timers_collect(ctx);  // (poa_run collected before this launch: once more, with it)
+    return VGA_OK;
+}
+
+// ------------------------------------------------------------------------------------ host: the calls over a finished table
+// What vga_variant.hip and vga_insertion.hip share beyond vga_launch and OPLIST_ERR_WIDE: n items of a table of the caller's
+// go to the device on the context's stream (nothing for n == 0)
+template <typename T, typename H>
+int table_upload(vga_ctx *ctx, vga_dbuf<T> &d, const H *host, size_t n)
+{
+    static_assert(sizeof(T) == sizeof(H), "a copy, not a conversion");
+    if (n == 0) return VGA_OK;
+    VGA_HIP_CHECK_OOM(ctx, d.reserve(n));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(d.p, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return VGA_OK;
+}

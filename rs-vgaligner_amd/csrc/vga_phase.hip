@@ -325,17 +325,6 @@ __global__ __launch_bounds__(HC_COUNT_BLOCK) void k_hc_count(uint32_t n_jobs, ui
     }
 }
 
-// A launch on the context's stream under a timer of the kernel's name: VGA_OK, or the error that was set
-template <typename... P, typename... A>
-int ph_launch(vga_ctx *ctx, const char *name, uint64_t bytes, void (*kernel)(P...), dim3 grid, dim3 block, A... args)
-{
-    const int t = vga_timer_begin(ctx, name, bytes, ctx->stream);
-    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, static_cast<P>(args)...);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
-    return VGA_OK;
-}
-
 }  // namespace
 
 // The store of a context's index while it is on (vga_dev_index::ph: released with the index): the words on the device, the
@@ -393,7 +382,7 @@ int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t
         ph->cap = cap;
     }
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(ph->d_dst.p, ph->h_dst.p, nw * 4, hipMemcpyHostToDevice, st));
-    const int rc = ph_launch(ctx, "k_ph_keep", (at - ph->n_words) * 8, k_ph_keep, dim3((unsigned)nw), dim3(64), nw, lists.d_win.p, lists.d_lists.p, lists.d_host_lists.p,
+    const int rc = vga_launch(ctx, "k_ph_keep", (at - ph->n_words) * 8, k_ph_keep, dim3((unsigned)nw), dim3(64), nw, lists.d_win.p, lists.d_lists.p, lists.d_host_lists.p,
                              ph->d_dst.p, ph->d_words);
     if (rc != VGA_OK) return rc;
     for (size_t i = 0; i < nw; i++) ph->recs.push_back(ph_rec{ph->h_dst.p[i], lists.h_win.p[i].n_a, lists.h_win.p[i].n_b});
@@ -586,8 +575,7 @@ struct ph_frame {
     ph_frame(vga_ctx *c, const ph_sites &sites) : ctx(c), scope(c), s(sites), H((uint32_t)sites.n)
     {
         (void)hipSetDevice(ctx->device);
-        vga_timers_reset(ctx);
-        vga_timers_collect(ctx);  // (a call that launches nothing reports no kernel)
+        vga_timers_reset(ctx);  // (a call that launches nothing reports no kernel)
     }
 
     // the reads of the context's store (checked: it is on, the sites lie in its index), the sites' own letters from the index
@@ -662,7 +650,7 @@ struct ph_frame {
         for (uint64_t r0 = 0; r0 < n_reads; r0 += T) {
             const uint32_t n = (uint32_t)std::min<uint64_t>(T, n_reads - r0);
             VGA_HIP_CHECK(ctx, hipMemsetAsync(d_tile.p, 0, clear_words * 4, ctx->stream));
-            int rc = ph_launch(ctx, "k_ph_obs", 0, k_ph_obs, dim3(n), dim3(64), n, d_recs.p + r0, d_words, H, d_pos.p, d_bytes.p, d_bytes.p + H, d_bytes.p + 2 * (size_t)H,
+            int rc = vga_launch(ctx, "k_ph_obs", 0, k_ph_obs, dim3(n), dim3(64), n, d_recs.p + r0, d_words, H, d_pos.p, d_bytes.p, d_bytes.p + H, d_bytes.p + 2 * (size_t)H,
                                T, d_tile.p);
             if (rc == VGA_OK) rc = per_tile(r0, n);
             if (rc != VGA_OK) return rc;
@@ -698,7 +686,7 @@ int ph_run(ph_frame &f, uint32_t *links, uint32_t *site_reads)
     if (rc != VGA_OK) return rc;
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_out.p, 0, out_words * 4, ctx->stream));
     rc = f.each_tile([&](uint64_t, uint32_t n) {
-        return ph_launch(ctx, "k_ph_link", (uint64_t)H * n, k_ph_link, dim3(H), dim3(PH_LINK_BLOCK), H, f.T, n, (const uint8_t *)f.d_tile.p, d_links, d_sr);
+        return vga_launch(ctx, "k_ph_link", (uint64_t)H * n, k_ph_link, dim3(H), dim3(PH_LINK_BLOCK), H, f.T, n, (const uint8_t *)f.d_tile.p, d_links, d_sr);
     });
     if (rc != VGA_OK) return rc;
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(links, d_links, (size_t)H * PH_LINK_ROW * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -726,12 +714,12 @@ int ph_tag_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, uint64_t ca
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_run.p, 0, 16, st));
     const uint32_t *d_sets = f.d_sets.p;  // set_start, set_ps, order
     const auto tag = [&](auto kernel, uint64_t r0, uint32_t n) {
-        return ph_launch(ctx, "k_ph_tag", (uint64_t)H * n, kernel, dim3((n + PH_TAG_BLOCK - 1u) / PH_TAG_BLOCK), dim3(PH_TAG_BLOCK), n, f.T, r0, (const uint8_t *)f.d_tile.p,
+        return vga_launch(ctx, "k_ph_tag", (uint64_t)H * n, kernel, dim3((n + PH_TAG_BLOCK - 1u) / PH_TAG_BLOCK), dim3(PH_TAG_BLOCK), n, f.T, r0, (const uint8_t *)f.d_tile.p,
                          S, d_sets, d_sets + S + 1u, d_sets + 2 * (size_t)S + 1u, d_rows_of.p, d_run.p, room, d_rows.p);
     };
     rc = f.each_tile([&](uint64_t r0, uint32_t n) {
         int rc = tag(k_ph_tag<false>, r0, n);
-        if (rc == VGA_OK) rc = ph_launch(ctx, "k_ph_tag_scan", (uint64_t)n * 8, k_ph_tag_scan, dim3(1), dim3(PH_SCAN_BLOCK), n, d_rows_of.p, d_run.p);
+        if (rc == VGA_OK) rc = vga_launch(ctx, "k_ph_tag_scan", (uint64_t)n * 8, k_ph_tag_scan, dim3(1), dim3(PH_SCAN_BLOCK), n, d_rows_of.p, d_run.p);
         if (rc == VGA_OK) rc = tag(k_ph_tag<true>, r0, n);
         return rc;
     });
@@ -796,10 +784,10 @@ int hc_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, const hc_calls 
     VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_cref, c.cref, C, hipMemcpyHostToDevice, st));
     VGA_HIP_CHECK(ctx, hipMemsetAsync(d_rows.p, 0, (size_t)J * HC_ROW * 4, st));
     rc = f.each_tile([&](uint64_t r0, uint32_t n) {
-        int rc = ph_launch(ctx, "k_hc_tags", (uint64_t)(H + S) * n, k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), n, f.T, (const uint8_t *)f.d_tile.p, S,
+        int rc = vga_launch(ctx, "k_hc_tags", (uint64_t)(H + S) * n, k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), n, f.T, (const uint8_t *)f.d_tile.p, S,
                            f.d_sets.p, f.d_sets.p + 2 * (size_t)S + 1u, d_tags);
-        if (rc == VGA_OK) rc = ph_launch(ctx, "k_hc_cols", 0, k_hc_cols, dim3(n), dim3(64), n, f.d_recs.p + r0, f.d_words, C, d_cpos, d_cref, f.T, d_cols);
-        if (rc == VGA_OK) rc = ph_launch(ctx, "k_hc_count", 2 * J * n, k_hc_count, dim3((uint32_t)J), dim3(HC_COUNT_BLOCK), J, f.T, n, d_jobs, d_tags, (const uint8_t *)d_cols, d_rows.p);
+        if (rc == VGA_OK) rc = vga_launch(ctx, "k_hc_cols", 0, k_hc_cols, dim3(n), dim3(64), n, f.d_recs.p + r0, f.d_words, C, d_cpos, d_cref, f.T, d_cols);
+        if (rc == VGA_OK) rc = vga_launch(ctx, "k_hc_count", 2 * J * n, k_hc_count, dim3((uint32_t)J), dim3(HC_COUNT_BLOCK), J, f.T, n, d_jobs, d_tags, (const uint8_t *)d_cols, d_rows.p);
         return rc;
     });
     if (rc != VGA_OK) return rc;

@@ -97,7 +97,7 @@ static_assert(PH_LINK_ROW == PH_WINDOW * PH_LINK_COLS, "the links of a site");
 struct ph_state;
 // the context's phase store while it is on (vga_phase_begin, with the pileup counted), else null
 ph_state *ph_active(vga_ctx *ctx);
-// k_ph_keep: the lists of the nw winners that pu_add_winners has just staged (lists.d_win / h_win, the device lists and the
+// k_ph_keep: the lists of the nw winners that the pileup's add step (pu_add) has just staged (lists.d_win / h_win, the device lists and the
 // host-built ones) join the store, on the context's stream; not waited for.  VGA_ERR_NOMEM when the store cannot grow.
 int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t nw);
 #endif

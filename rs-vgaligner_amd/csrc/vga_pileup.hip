@@ -128,28 +128,14 @@ __global__ __launch_bounds__(1024) void k_pu_finish(const uint32_t *__restrict__
 }  // namespace
 
 // The counters of a context's index while counting is on (vga_dev_index::pu: released with the index), and the lists
-struct pu_state {
-    uint32_t seq_length = 0;
+struct pu_state : oplist_state {
     vga_dbuf<uint32_t> d_mdiff, d_counts, d_out;
-    uint64_t n_alignments = 0, leading_ins = 0;
-    oplist_call lists;  // of the vga_align_batch call in progress
+    uint64_t leading_ins = 0;
 };
 
 pu_state *pu_active(vga_ctx *ctx) { return ctx && ctx->index.loaded ? ctx->index.pu.get() : nullptr; }
 
-oplist_call &pu_lists(pu_state *pu) { return pu->lists; }
-
-hipError_t pu_enqueue_events(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                             const uint32_t *ids, const sg_store &store)
-{
-    return lists.enqueue(ctx, st, slot, oset, nb, "k_pu_events", [&](pu_rec *d_recs) {
-        hipLaunchKernelGGL(k_pu_events, dim3(nb), dim3(64), 0, st, nb, b.probs, b.outs, b.ops, b.orow, b.rows, b.ntab, (const char *)b.seq32, b.q, ids,
-                           store.d_off, (uint32_t)store.split, store.part[0].d_handles, store.part[1].d_handles, ctx->index.d_node_start,
-                           (uint32_t)ctx->index.n_nodes, lists.d_lists.p, lists.list_words, lists.d_cur.p, d_recs);
-    });
-}
-
-void pu_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
+static void pu_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
 {
     std::vector<uint32_t> sp;
     oplist_runs_host runs;
@@ -174,86 +160,53 @@ void pu_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o)
     lists.keep_host(p, runs.ev, sp, leading ? PU_LEADING : 0u);
 }
 
-int pu_add_winners(vga_ctx *ctx, pu_state *pu, const std::vector<uint32_t> &winners)
+static int pu_add(vga_ctx *ctx, oplist_state *s, size_t nw)
 {
-    const size_t nw = winners.size();
-    if (nw == 0) return VGA_OK;
-    const int rc = pu->lists.stage_winners(ctx, winners, "pileup", "event");
-    if (rc != VGA_OK) return rc;
+    pu_state *pu = static_cast<pu_state *>(s);
     uint64_t leading = 0;
     for (size_t i = 0; i < nw; i++) leading += (pu->lists.h_win.p[i].flags & PU_LEADING) ? 1u : 0u;
-    hipStream_t st = ctx->stream;
-    const int t = vga_timer_begin(ctx, "k_pu_add", 0, st);
-    hipLaunchKernelGGL(k_pu_add, dim3((unsigned)nw), dim3(64), 0, st, (uint32_t)nw, pu->lists.d_win.p, pu->lists.d_lists.p, pu->lists.d_host_lists.p, pu->seq_length,
-                       pu->d_mdiff.p, pu->d_counts.p);
-    vga_timer_end(ctx, t);
-    VGA_HIP_CHECK(ctx, hipGetLastError());
-    if (ph_state *ph = ph_active(ctx)) {  // the phase store keeps the lists that were just staged (vga_phase.hpp)
-        const int kept = ph_keep_winners(ctx, ph, pu->lists, nw);
-        if (kept != VGA_OK) { (void)hipStreamSynchronize(st); return kept; }
-    }
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    pu->n_alignments += nw;
-    pu->leading_ins += leading;
-    vga_timers_collect(ctx);  // (poa_run collected before this launch: once more, with it)
-    return VGA_OK;
-}
-
-// ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
-static int pu_zero(vga_ctx *ctx, pu_state *pu)
-{
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(pu->d_mdiff.p, 0, ((size_t)pu->seq_length + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipMemsetAsync(pu->d_counts.p, 0, ((size_t)pu->seq_length * PU_COLS + 1) * 4, ctx->stream));
-    VGA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    pu->n_alignments = 0;
-    pu->leading_ins = 0;
-    return VGA_OK;
-}
-
-extern "C" int vga_pileup_begin(vga_ctx *ctx)
-{
-    if (!ctx) return VGA_ERR_ARG;
-    if (!ctx->index.loaded) return vga_set_error(ctx, VGA_ERR_NO_INDEX, "vga_pileup_begin: no index uploaded");
-    const vga_dev_index &ix = ctx->index;
-    if (ix.seq_length >= PU_MAX_SEQ || ix.n_nodes >= (1ull << 31))
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_pileup_begin: graph too large for 29-bit positions");
-    (void)hipSetDevice(ctx->device);
-    vga_ctx_scope scope(ctx);
-    if (!ctx->index.pu && !(ctx->index.pu = vga_make_owned<pu_state>())) return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_pileup_begin: out of host memory");
-    pu_state *pu = ctx->index.pu.get();
-    pu->seq_length = (uint32_t)ix.seq_length;
-    hipError_t e = pu->d_mdiff.reserve((size_t)pu->seq_length + 1);
-    if (e == hipSuccess) e = pu->d_counts.reserve((size_t)pu->seq_length * PU_COLS + 1);
-    if (e == hipSuccess) e = pu->d_out.reserve((size_t)pu->seq_length * PU_COLS + 1);
-    const int rc = e == hipSuccess ? pu_zero(ctx, pu) : vga_set_error(ctx, VGA_ERR_NOMEM, "vga_pileup_begin: %s", hipGetErrorString(e));
-    if (rc != VGA_OK) ctx->index.pu.reset();
+    // the phase store keeps the lists that were just staged (vga_phase.hpp), behind k_pu_add on the same stream
+    const auto keep = [&]() { ph_state *ph = ph_active(ctx); return ph ? ph_keep_winners(ctx, ph, pu->lists, nw) : VGA_OK; };
+    const int rc = oplist_add_staged(ctx, pu, nw, "k_pu_add", k_pu_add, keep, pu->seq_length, pu->d_mdiff.p, pu->d_counts.p);
+    if (rc == VGA_OK) pu->leading_ins += leading;
     return rc;
 }
 
-extern "C" int vga_pileup_reset(vga_ctx *ctx)
+static std::vector<oplist_counter> pu_counters(const vga_dev_index &, oplist_state *s)
 {
-    if (!ctx) return VGA_ERR_ARG;
-    pu_state *pu = pu_active(ctx);
-    if (!pu) return vga_set_error(ctx, VGA_ERR_ARG, "vga_pileup_reset: counting is off (vga_pileup_begin)");
-    (void)hipSetDevice(ctx->device);
-    return pu_zero(ctx, pu);
+    pu_state *pu = static_cast<pu_state *>(s);
+    const size_t cells = (size_t)pu->seq_length * PU_COLS + 1;
+    return {{&pu->d_mdiff, (size_t)pu->seq_length + 1, true}, {&pu->d_counts, cells, true}, {&pu->d_out, cells, false}};
 }
 
-extern "C" int vga_pileup_end(vga_ctx *ctx)
+const oplist_maker &pu_maker()
 {
-    if (!ctx) return VGA_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->index.ph.reset();  // (the phase store keeps the pileup's lists: it ends with it)
-    ctx->index.pu.reset();
-    return VGA_OK;
+    static const oplist_maker m = {
+        OPLIST_TEXT_PU,
+        [](vga_ctx *ctx) -> oplist_state * { return pu_active(ctx); },
+        [](vga_ctx *ctx) -> oplist_state * { return pu_active(ctx); },
+        &poa_switches::has_pileup_words, &poa_switches::pileup_words,
+        [](vga_ctx *ctx, oplist_call &lists, const oplist_launch &L) { return oplist_enqueue<true>(ctx, lists, L, "k_pu_events", k_pu_events); },
+        pu_keep_from_ops,
+        pu_add,
+        [](const vga_dev_index &ix) { return ix.seq_length < PU_MAX_SEQ && ix.n_nodes < (1ull << 31); },
+        [](vga_ctx *ctx, const char *fn) { return oplist_make(ctx, ctx->index.pu, fn); },
+        [](vga_ctx *ctx) { ctx->index.ph.reset(); ctx->index.pu.reset(); },  // (the phase store keeps the pileup's lists: it ends with it)
+        pu_counters,
+        [](oplist_state *s) { static_cast<pu_state *>(s)->leading_ins = 0; },
+    };
+    return m;
 }
+
+// ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
+extern "C" int vga_pileup_begin(vga_ctx *ctx) { return oplist_begin(ctx, pu_maker(), __func__); }
+extern "C" int vga_pileup_reset(vga_ctx *ctx) { return oplist_reset(ctx, pu_maker(), __func__); }
+extern "C" int vga_pileup_end(vga_ctx *ctx) { return oplist_end(ctx, pu_maker()); }
 
 int pu_finish_device(vga_ctx *ctx, pu_state *pu, const char *who, const uint32_t **table, uint32_t *seq_length)
 {
-    if (pu->n_alignments >= 0xFFFFFFFFull)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu alignments counted: a 32-bit counter may have wrapped", who,
-                             (unsigned long long)pu->n_alignments);
+    const int rc = oplist_wrapped(ctx, pu, who);
+    if (rc != VGA_OK) return rc;
     if (pu->seq_length) {
         hipLaunchKernelGGL(k_pu_finish, dim3(1), dim3(1024), 0, ctx->stream, pu->d_mdiff.p, pu->d_counts.p, ctx->index.d_seq_fwd, pu->d_out.p, pu->seq_length);
         VGA_HIP_CHECK(ctx, hipGetLastError());
@@ -265,19 +218,16 @@ int pu_finish_device(vga_ctx *ctx, pu_state *pu, const char *who, const uint32_t
 
 extern "C" int vga_pileup_read(vga_ctx *ctx, uint32_t *counts, uint64_t *n_alignments, uint64_t *leading_ins)
 {
-    if (!ctx) return VGA_ERR_ARG;
-    pu_state *pu = pu_active(ctx);
-    if (!pu) return vga_set_error(ctx, VGA_ERR_ARG, "vga_pileup_read: counting is off (vga_pileup_begin)");
-    if (pu->n_alignments >= 0xFFFFFFFFull)
-        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_pileup_read: %llu alignments counted: a 32-bit counter may have wrapped",
-                             (unsigned long long)pu->n_alignments);
+    pu_state *pu = static_cast<pu_state *>(oplist_on(ctx, pu_maker(), __func__));
+    if (!pu) return VGA_ERR_ARG;
+    int rc = oplist_wrapped(ctx, pu, __func__);  // (also without a table to read)
+    if (rc != VGA_OK) return rc;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     if (counts && pu->seq_length) {
         const uint32_t *table = nullptr;
         uint32_t n = 0;
-        const int rc = pu_finish_device(ctx, pu, "vga_pileup_read", &table, &n);
-        if (rc != VGA_OK) return rc;
+        if ((rc = pu_finish_device(ctx, pu, __func__, &table, &n)) != VGA_OK) return rc;
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(counts, table, (size_t)n * PU_COLS * 4, hipMemcpyDeviceToHost, st));
         VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }

@@ -11,7 +11,8 @@
 // the column of every base's own letter.
 //
 // What the pileup shares with coverage -- the walk over the operations on the device and on the host, the record of a list and
-// the per-call store of lists -- has one copy, in vga_oplist.hpp; here is what is the pileup's own.
+// the per-call store of lists -- has one copy, in vga_oplist.hpp, and so has the host frame of a maker: poa_run and
+// vga_align_batch reach the pileup through pu_maker().  Here is what is the pileup's own.
 #pragma once
 
 #include "vga_oplist.hpp"
@@ -26,18 +27,9 @@ enum : uint32_t { PU_COL_N = 4u, PU_COL_DEL = 5u, PU_COL_INS = 6u, PU_COLS = 7u 
 using pu_rec = oplist_rec;
 
 struct pu_state;
+const oplist_maker &pu_maker();
 // the context's pileup state while counting is on (vga_pileup_begin), else null
 pu_state *pu_active(vga_ctx *ctx);
-// the lists of the call in progress
-oplist_call &pu_lists(pu_state *pu);
-// k_pu_events for the nb problems staged on a slot, and the copy of their records into the slot's result set `oset`
-hipError_t pu_enqueue_events(vga_ctx *ctx, oplist_call &lists, hipStream_t st, int slot, int oset, uint32_t nb, const poa_launch_bufs &b,
-                             const uint32_t *ids, const sg_store &store);
-// the host route for a problem whose list found no room: the same list from the operations as they came back, with the bases of
-// both sides
-void pu_keep_from_ops(oplist_call &lists, uint32_t p, const oplist_ops &o);
-// k_pu_add over the lists of the winners (problem indices of the call that just ended), on the context's stream; waits for it
-int pu_add_winners(vga_ctx *ctx, pu_state *pu, const std::vector<uint32_t> &winners);
 // k_pu_finish on the context's stream, not waited for: the table vga_pileup_read copies out (seq_length x PU_COLS), left on the
 // device for vga_variant.hip.  VGA_ERR_UNSUPPORTED once a 32-bit counter may have wrapped.
 int pu_finish_device(vga_ctx *ctx, pu_state *pu, const char *who, const uint32_t **table, uint32_t *seq_length);

@@ -3,9 +3,7 @@
 // (vga_align_prepare, vga_poa_batch).  No kernel is visible here: launches go through vga_poa_launch.hpp, the launch shape comes
 // from vga_poa_shape.hpp, the traceback pool is vga_poa_pool.hip.  The engine itself is described at the top of vga_poa.hip.
 #include "vga_common.hpp"
-#include "vga_coverage.hpp"
-#include "vga_pileup.hpp"
-#include "vga_insertion.hpp"
+#include "vga_oplist.hpp"
 #include "vga_poa_internal.hpp"
 #include "vga_poa_pool.hpp"
 
@@ -271,16 +269,11 @@ struct poa_call {
     vga_trace tr{"poa"};
     poa_ws &W;
     poa_pool pool;
-    // A list maker that is on while the graphs are in the device store (vga_oplist.hpp): its kernel runs behind k_poa_text.
-    // Coverage's k_cov_runs while coverage or path support is on (cov_lists_active), the pileup's k_pu_events and the insertion
-    // table's k_ia_events while they are counted
+    // The list makers (oplist_makers()) that are on while the graphs are in the device store, with the lists of this call: the list
+    // kernel of each runs behind k_poa_text
     struct list_maker {
+        const oplist_maker *maker;
         oplist_call *lists;
-        const char *what;  // as the trace calls its list
-        bool has_cap;      // VGA_COV_LIST_WORDS / VGA_PILEUP_LIST_WORDS / VGA_INS_LIST_WORDS
-        uint64_t cap_words;
-        decltype(&cov_enqueue_runs) enqueue;
-        decltype(&cov_keep_from_ops) keep_from_ops;
     };
     std::vector<list_maker> makers;
     uint32_t max_q = 0;
@@ -325,9 +318,8 @@ struct poa_call {
           family(poa_choose_family(*p, sw)), W(poa_ws_of(c)), pool(c, W, sw, tr, n)
     {
         if (!f.dev) return;
-        if (cov_state *cv = cov_lists_active(c)) makers.push_back({&cov_lists(cv), "run list", sw.has_cov_words, sw.cov_words, cov_enqueue_runs, cov_keep_from_ops});
-        if (pu_state *pu = pu_active(c)) makers.push_back({&pu_lists(pu), "pileup list", sw.has_pileup_words, sw.pileup_words, pu_enqueue_events, pu_keep_from_ops});
-        if (ia_state *ia = ia_active(c)) makers.push_back({&ia_lists(ia), "insertion list", sw.has_ins_words, sw.ins_words, ia_enqueue_events, ia_keep_from_ops});
+        for (const oplist_maker *m : oplist_makers())
+            if (oplist_state *s = m->making(c)) makers.push_back({m, &s->lists});
     }
 
     double ms_since_start() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
@@ -767,7 +759,7 @@ void poa_call::enqueue_results(const launch_t &L)
     }
     // coverage's run list and the pileup's list of every problem, while its operations are in the slot (the refill recycles them)
     for (const list_maker &m : makers)
-        if (launch_err == hipSuccess) chk(m.enqueue(ctx, *m.lists, st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev));
+        if (launch_err == hipSuccess) chk(m.maker->enqueue(ctx, *m.lists, {st, L.slot, L.oset, nb, bufs_of(S), S.d_ids.p, *feed.dev}));
 }
 
 // stage, upload and enqueue DP + traceback + result copies of a sub-batch that starts at launch position i0 and ends
@@ -949,8 +941,8 @@ void poa_call::collect_lists(const list_maker &m, const sub_t &cur, const poa_sl
         if (ho.status != POA_ST_OK) continue;
         const oplist_rec &r = recs[i - cur.i0];
         if ((r.flags & 3u) != 2u) { m.lists->keep(p, r); continue; }
-        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its %s, built from the operations\n", p, m.what);
-        m.keep_from_ops(*m.lists, p, {S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1, probs[p].N,
+        if (tr.on) fprintf(stderr, "[vga-trace] poa:   problem %u: no room for its %s, built from the operations\n", p, m.maker->text.list);
+        m.maker->keep_from_ops(*m.lists, p, {S.h_ops.p + probs[p].ops0, S.h_orow.p + probs[p].ops0, ho.nops, G[p].first_row_p, G[p].n_ntab - 1, probs[p].N,
                                       feed.dev->of(p).h_handles + feed.dev->off[p].node0, ctx->index.node_start.data(), S.h_seq.p + probs[p].seq0,
                                       views[p].query});
     }
@@ -1148,7 +1140,7 @@ int poa_run(vga_ctx *ctx, poa_feed &feed, const vga_poa_params *params, std::vec
         uint64_t total_q = 0;
         for (const poa_view &v : c.views) total_q += v.qlen;
         for (const auto &m : c.makers)
-            if ((rc = m.lists->begin(ctx, c.n, total_q, m.has_cap, m.cap_words)) != VGA_OK) return rc;
+            if ((rc = m.lists->begin(ctx, c.n, total_q, c.sw.*m.maker->has_cap, c.sw.*m.maker->cap_words)) != VGA_OK) return rc;
     }
     if ((rc = c.order_problems()) != VGA_OK) return rc;
     if ((rc = c.size_pool()) != VGA_OK) return rc;

@@ -202,19 +202,14 @@ int vc_run(vga_ctx *ctx, const char *who, const T *d_counts, const char *d_lette
         VGA_HIP_CHECK_OOM(ctx, d_totals.reserve(2));
         uint32_t *wg_calls = d_wg.p, *wg_tested = d_wg.p + n_wg, *wg_off = d_wg.p + 2 * (size_t)n_wg, *flags = d_wg.p + 3 * (size_t)n_wg + 1;
         VGA_HIP_CHECK(ctx, hipMemsetAsync(flags, 0, 4, st));
-        int t = vga_timer_begin(ctx, "k_vc_count", (uint64_t)n * (PU_COLS * sizeof(T) + 1), st);
-        hipLaunchKernelGGL(k_vc_count<T>, dim3(n_wg), dim3(VC_BLOCK), 0, st, d_counts, d_letters, n, P, wg_calls, wg_tested, flags);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
-        t = vga_timer_begin(ctx, "k_vc_scan", (uint64_t)n_wg * 12, st);
-        hipLaunchKernelGGL(k_vc_scan, dim3(1), dim3(VC_SCAN_BLOCK), 0, st, wg_calls, wg_tested, n_wg, wg_off, d_totals.p);
-        vga_timer_end(ctx, t);
-        VGA_HIP_CHECK(ctx, hipGetLastError());
+        int rc = vga_launch(ctx, "k_vc_count", (uint64_t)n * (PU_COLS * sizeof(T) + 1), k_vc_count<T>, dim3(n_wg), dim3(VC_BLOCK), d_counts, d_letters, n, P, wg_calls, wg_tested, flags);
+        if (rc == VGA_OK) rc = vga_launch(ctx, "k_vc_scan", (uint64_t)n_wg * 12, k_vc_scan, dim3(1), dim3(VC_SCAN_BLOCK), wg_calls, wg_tested, n_wg, wg_off, d_totals.p);
+        if (rc != VGA_OK) return rc;
         uint32_t h_flags = 0;
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(totals, d_totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
         VGA_HIP_CHECK(ctx, hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, st));
         VGA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        if (h_flags & 1u) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: a counter of 2^40 or more", who);
+        if (h_flags & 1u) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, OPLIST_ERR_WIDE, who);
         const uint64_t m = std::min<uint64_t>(totals[1], o.cap);
         if (m) {
             vga_dbuf<uint32_t> d_pos, d_qual;
@@ -225,11 +220,9 @@ int vc_run(vga_ctx *ctx, const char *who, const T *d_counts, const char *d_lette
             VGA_HIP_CHECK_OOM(ctx, d_gt.reserve(m));
             VGA_HIP_CHECK_OOM(ctx, d_wide.reserve((size_t)m * (2 + PU_COLS)));
             unsigned long long *d_insq = d_wide.p, *d_depth = d_wide.p + m, *d_rows = d_wide.p + 2 * m;
-            t = vga_timer_begin(ctx, "k_vc_emit", m * (13 + 8 * (2 + PU_COLS)), st);
-            hipLaunchKernelGGL(k_vc_emit<T>, dim3(n_wg), dim3(VC_BLOCK), 0, st, d_counts, d_letters, n, P, wg_off, (uint32_t)m, d_pos.p, d_gt.p, d_qual.p,
-                               d_insq, d_depth, d_rows);
-            vga_timer_end(ctx, t);
-            VGA_HIP_CHECK(ctx, hipGetLastError());
+            rc = vga_launch(ctx, "k_vc_emit", m * (13 + 8 * (2 + PU_COLS)), k_vc_emit<T>, dim3(n_wg), dim3(VC_BLOCK), d_counts, d_letters, n, P, wg_off, (uint32_t)m, d_pos.p, d_gt.p,
+                            d_qual.p, d_insq, d_depth, d_rows);
+            if (rc != VGA_OK) return rc;
             VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.pos, d_pos.p, m * 4, hipMemcpyDeviceToHost, st));
             VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.gt, d_gt.p, m, hipMemcpyDeviceToHost, st));
             VGA_HIP_CHECK(ctx, hipMemcpyAsync(o.qual, d_qual.p, m * 4, hipMemcpyDeviceToHost, st));
@@ -260,17 +253,17 @@ extern "C" int vga_variant_call(vga_ctx *ctx, uint32_t E, uint64_t min_depth, ui
 {
     if (!ctx) return VGA_ERR_ARG;
     const vc_out o = {cap, pos, gt, qual, ins_qual, depth, counts, n_tested, n_calls};
-    int rc = vc_check(ctx, "vga_variant_call", E, min_depth, o);
+    int rc = vc_check(ctx, __func__, E, min_depth, o);
     if (rc != VGA_OK) return rc;
+    if (!oplist_on(ctx, pu_maker(), __func__)) return VGA_ERR_ARG;
     pu_state *pu = pu_active(ctx);
-    if (!pu) return vga_set_error(ctx, VGA_ERR_ARG, "vga_variant_call: counting is off (vga_pileup_begin)");
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
     const uint32_t *table = nullptr;
     uint32_t n = 0;
-    if ((rc = pu_finish_device(ctx, pu, "vga_variant_call", &table, &n)) != VGA_OK) return rc;
+    if ((rc = pu_finish_device(ctx, pu, __func__, &table, &n)) != VGA_OK) return rc;
     const vc_params P = {E, min_depth, min_qual};
-    return vc_run<uint32_t>(ctx, "vga_variant_call", table, ctx->index.d_seq_fwd, n, P, o);
+    return vc_run<uint32_t>(ctx, __func__, table, ctx->index.d_seq_fwd, n, P, o);
 }
 
 extern "C" int vga_variant_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *counts_in, const char *letters, uint32_t E, uint64_t min_depth, uint64_t min_qual,
@@ -279,22 +272,17 @@ extern "C" int vga_variant_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *
 {
     if (!ctx) return VGA_ERR_ARG;
     const vc_out o = {cap, pos, gt, qual, ins_qual, depth, counts, n_tested, n_calls};
-    const int rc = vc_check(ctx, "vga_variant_call_table", E, min_depth, o);
+    int rc = vc_check(ctx, __func__, E, min_depth, o);
     if (rc != VGA_OK) return rc;
-    if (n && (!counts_in || !letters)) return vga_set_error(ctx, VGA_ERR_ARG, "vga_variant_call_table: null table");
-    if (n >= VC_MAX_BASES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "vga_variant_call_table: %llu bases, positions are 31-bit", (unsigned long long)n);
+    if (n && (!counts_in || !letters)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null table", __func__);
+    if (n >= VC_MAX_BASES) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu bases, positions are 31-bit", __func__, (unsigned long long)n);
     (void)hipSetDevice(ctx->device);
     vga_ctx_scope scope(ctx);
-    hipStream_t st = ctx->stream;
-    if (st) (void)hipStreamSynchronize(st);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     vga_dbuf<unsigned long long> d_counts;
     vga_dbuf<char> d_letters;
-    if (n) {
-        VGA_HIP_CHECK_OOM(ctx, d_counts.reserve((size_t)n * PU_COLS));
-        VGA_HIP_CHECK_OOM(ctx, d_letters.reserve((size_t)n));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_counts.p, counts_in, (size_t)n * PU_COLS * 8, hipMemcpyHostToDevice, st));
-        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_letters.p, letters, (size_t)n, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = table_upload(ctx, d_counts, counts_in, (size_t)n * PU_COLS)) != VGA_OK) return rc;
+    if ((rc = table_upload(ctx, d_letters, letters, (size_t)n)) != VGA_OK) return rc;
     const vc_params P = {E, min_depth, min_qual};
-    return vc_run<unsigned long long>(ctx, "vga_variant_call_table", d_counts.p, d_letters.p, (uint32_t)n, P, o);
+    return vc_run<unsigned long long>(ctx, __func__, d_counts.p, d_letters.p, (uint32_t)n, P, o);
 }

@@ -1,13 +1,16 @@
-"""diagnostic: the list makers before and after their walk moved into vga_oplist.hpp (DESIGN.md sections 13 and 16).  One JSON
-object on stdout (profiles/oplist_shared_ab.json).  Every measurement runs in a child process of its own, under a time limit of
+"""diagnostic: the list makers before and after a change to what they share in vga_oplist.hpp -- their walk (DESIGN.md sections 13
+and 16, profiles/oplist_shared_ab.json) and their host frame (section 27, profiles/oplist_stage_ab.json).  One JSON object on
+stdout.  Every measurement runs in a child process of its own, under a time limit of
 its own, and the sides alternate, so that both sides of the comparison see the same box in the same minutes; the script stops
 at the first child that fails.  `--parent-lib` names a libvga_hip.so built from the parent commit (the binding's VGA_LIB).
 
   step   config 3 and config 5 steps (10 000 x 10 kbp reads, seed 77: map + align, the step bench.py times) with coverage, the
-         pileup and path support all counting, with the parent's library (parent_on) and with this one (branch_on), alternating.
-         Per run: aligned reads/s, from vga_last_kernel_times the busy time per step of k_cov_runs, k_pu_events, k_cov_add,
-         k_pu_add and poa_text (k_poa_text), and a SHA-256 over the bytes of every table read back.  The digests of the two
-         sides must be equal; for each of the two walk kernels the branch's median must not exceed the parent's slowest run.
+         pileup, the insertion table and path support all counting, with the parent's library (parent_on) and with this one
+         (branch_on), alternating.  Per run: aligned reads/s, the wall time of a step, from vga_last_kernel_times the busy time
+         per step of the makers' list and add kernels and of poa_text (k_poa_text), and a SHA-256 over the bytes of every table
+         read back.  The digests of the two sides must be equal; for each of the walk kernels the branch's median must not exceed
+         the parent's slowest run; `in_parent_range` says for every kernel and for the step whether the branch's median lies
+         inside the parent's own fastest-to-slowest range.
 
     python tests/prof_oplist_ab.py --parent-lib PATH [--repeats 3] [--reads 10000] [--steps 3] [--configs config3,config5]
 """
@@ -23,8 +26,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DRB1 = os.path.join(ROOT, "tests", "golden", "data", "DRB1-3123.gfa")
-BUSY = ("k_cov_runs", "k_pu_events", "k_cov_add", "k_pu_add", "poa_text")
-WALK = ("k_cov_runs", "k_pu_events")
+BUSY = ("k_cov_runs", "k_pu_events", "k_ia_events", "k_cov_add", "k_pu_add", "k_ia_add", "poa_text")
+WALK = ("k_cov_runs", "k_pu_events", "k_ia_events")
 ACC = ("sum_bases", "sum_edges", "top", "top_alone")
 
 
@@ -42,12 +45,14 @@ def child_step(gfa, n_reads, steps, warmup):
     g = p.hostlib.gfa_paths(gfa)
     ctx.coverage_begin()
     ctx.pileup_begin()
+    ctx.insertion_begin()
     ctx.path_support_begin(g["step_off"], g["steps"])
     for _ in range(warmup):
         b.map_align_raw()
     ctx.synchronize()
     ctx.coverage_reset()
     ctx.pileup_reset()
+    ctx.insertion_reset()
     ctx.path_support_reset()
     busy = {n: 0.0 for n in BUSY}
     aligned = 0
@@ -62,13 +67,14 @@ def child_step(gfa, n_reads, steps, warmup):
     dt = time.perf_counter() - t0
     base, node, edge, n_cov = ctx.coverage()
     counts, n_pu, leading = ctx.pileup()
+    ins, n_ia, n_events, n_leading = ctx.insertions()
     acc = ctx.path_support()
     h = hashlib.sha256()
-    for a in (base, node, edge, counts, np.array([n_pu, leading], dtype=np.uint64)) + tuple(acc[k] for k in ACC):
+    for a in (base, node, edge, counts, np.array([n_pu, leading], dtype=np.uint64), ins, np.array([n_ia, n_events, n_leading], dtype=np.uint64)) + tuple(acc[k] for k in ACC):
         h.update(np.ascontiguousarray(a).tobytes())
     print(json.dumps({"aligned_reads_per_s": round(aligned / dt, 1), "ms_per_step": round(dt / steps * 1e3, 1),
                       "busy_ms_per_step": {n: round(v / steps, 3) for n, v in busy.items()}, "tables_sha256": h.hexdigest(),
-                      "counted": {"coverage": n_cov, "pileup": n_pu, "leading_ins": leading, "path_support": acc["n_alignments"]}}), flush=True)
+                      "counted": {"coverage": n_cov, "pileup": n_pu, "leading_ins": leading, "insertions": n_ia, "insertion_events": n_events, "path_support": acc["n_alignments"]}}), flush=True)
 
 
 def run_json(cmd, env, timeout):
@@ -106,8 +112,11 @@ def step(parent_lib, gfa, n_reads, steps, warmup, repeats, timeout):
     walk = {n: {"parent_slowest": max(busy["parent_on"][n]), "branch_median": median(busy["branch_on"][n])} for n in WALK}
     for n in WALK:
         walk[n]["branch_median_not_above_parent_slowest"] = bool(walk[n]["branch_median"] <= walk[n]["parent_slowest"])
-    return {"reads": n_reads, "steps": steps, "aligned_reads_per_s": {s: [r["aligned_reads_per_s"] for r in runs[s]] for s in runs},
-            "busy_ms_per_step": busy, "walk_kernels": walk, "tables_sha256": digests,
+    wall = {s: [r["ms_per_step"] for r in runs[s]] for s in runs}
+    in_range = {n: bool(min(v["parent_on"]) <= median(v["branch_on"]) <= max(v["parent_on"]))
+                for n, v in [(n, {s: busy[s][n] for s in runs}) for n in BUSY] + [("ms_per_step", wall)]}
+    return {"reads": n_reads, "steps": steps, "aligned_reads_per_s": {s: [r["aligned_reads_per_s"] for r in runs[s]] for s in runs}, "ms_per_step": wall,
+            "busy_ms_per_step": busy, "walk_kernels": walk, "in_parent_range": in_range, "tables_sha256": digests,
             "tables_equal": bool(digests["parent_on"] == digests["branch_on"] and len(digests["branch_on"]) == 1),
             "counted": runs["branch_on"][-1]["counted"]}
 

@@ -384,6 +384,103 @@ def test_life_cycle(oracle, drb1_graph, drb1, monkeypatch):
         c.close()
 
 
+def _tables(c, which):
+    """the tables of the makers named in `which`, each flattened to a tuple of arrays and totals"""
+    read = {"cov": c.coverage, "pu": c.pileup, "ia": c.insertions}
+    return {m: read[m]() for m in which}
+
+
+def _same_tables(got, want, what):
+    for m, w in want.items():
+        assert len(got[m]) == len(w), (what, m)
+        for k, (g, x) in enumerate(zip(got[m], w)):
+            assert np.array_equal(g, x), (what, m, k)
+
+
+def test_three_makers_on_one_context(drb1, monkeypatch, capfd):
+    """coverage, the pileup and the insertion table counting together: each table equals the one the same reads give with that
+    maker alone -- with every list on the device, with one maker on the host walk between two that are not, and with all three on
+    it.  Ending them in another order than they began (one of them twice) leaves the others counting, and no kernel of an ended
+    maker runs."""
+    p = pkg()
+    seqs = [r.seq for r in p.readsim.simulate_reads(DRB1, 8, 1800, 0.03, 0.03, 0.04, seed=81)]
+    begin = {"cov": lambda c: c.coverage_begin(), "pu": lambda c: c.pileup_begin(), "ia": lambda c: c.insertion_begin()}
+    end = {"cov": lambda c: c.coverage_end(), "pu": lambda c: c.pileup_end(), "ia": lambda c: c.insertion_end()}
+    reset = {"cov": lambda c: c.coverage_reset(), "pu": lambda c: c.pileup_reset(), "ia": lambda c: c.insertion_reset()}
+    prefix = {"cov": "k_cov", "pu": "k_pu", "ia": "k_ia"}
+    list_name = {"cov": "run list", "pu": "pileup list", "ia": "insertion list"}
+    c = p.Context(0)
+    try:
+        upload_oracle_index(c, drb1)
+        alone = {}
+        for m in ("cov", "pu", "ia"):
+            begin[m](c)
+            al, _ = count(c, seqs)
+            assert int(al.aligned.sum()) == len(seqs) == al.poa_problems   # (one list per read and maker)
+            alone.update(_tables(c, [m]))
+            end[m](c)
+        assert alone["cov"][3] == alone["pu"][1] == alone["ia"][1] == len(seqs) and alone["ia"][2] > 100
+        for m in ("cov", "pu", "ia"):
+            begin[m](c)
+        monkeypatch.setenv("VGA_TRACE", "1")
+        for env, on_host in (({}, ()), ({"VGA_PILEUP_LIST_WORDS": "0"}, ("pu",)),
+                             ({"VGA_COV_LIST_WORDS": "0", "VGA_PILEUP_LIST_WORDS": "0", "VGA_INS_LIST_WORDS": "0"}, ("cov", "pu", "ia"))):
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            capfd.readouterr()
+            count(c, seqs)
+            trace = capfd.readouterr().err
+            names = [t["name"] for t in c.kernel_times()]
+            _same_tables(_tables(c, alone), alone, str(env))
+            for m in alone:
+                by_host = len(re.findall("no room for its " + list_name[m], trace))
+                assert by_host == (len(seqs) if m in on_host else 0), (env, m, by_host)
+            adds = [names.index(k) for k in ("k_cov_add", "k_pu_add", "k_ia_add")]
+            assert adds == sorted(adds), names   # the order of the launches
+            for k in env:
+                monkeypatch.delenv(k)
+            for m in alone:
+                reset[m](c)
+        monkeypatch.delenv("VGA_TRACE")
+        # begun as coverage, pileup, insertions: the pileup ends first (twice), then the insertions, then coverage
+        left = ["cov", "pu", "ia"]
+        for gone in ("pu", "ia", "cov"):
+            end[gone](c)
+            if gone == "pu":
+                end[gone](c)
+            left.remove(gone)
+            count(c, seqs)
+            names = [t["name"] for t in c.kernel_times()]
+            for m in alone:
+                assert any(n.startswith(prefix[m]) for n in names) == (m in left), (gone, names)
+            _same_tables(_tables(c, left), {m: alone[m] for m in left}, "after the end of " + gone)
+            for m in left:
+                reset[m](c)
+    finally:
+        c.close()
+
+
+def test_a_table_call_that_launches_nothing_reports_no_kernel(drb1):
+    """the calls over a table, without sites and without bases: kernel_times() holds the kernels of the last call, so none -- not
+    those of the call that launched before it"""
+    p = pkg()
+    rows = random_rows(3, seed=9)
+    c = p.Context(0)
+    try:
+        upload_oracle_index(c, drb1)
+        c.pileup_begin()
+        c.insertion_begin()
+        quiet = [lambda: c.insertion_call([]), lambda: c.insertion_call_table(np.zeros((0, COLS), dtype=np.uint64)),
+                 lambda: c.variant_call_table(np.zeros((0, 7), dtype=np.uint64), "")]
+        for k, call in enumerate(quiet):
+            c.insertion_call_table(rows)   # three rows: it launches
+            assert "k_ia_call" in [t["name"] for t in c.kernel_times()]
+            call()
+            assert not [t["name"] for t in c.kernel_times() if t["name"].startswith("k_")], (k, c.kernel_times())
+    finally:
+        c.close()
+
+
 # ---- 5. the seam
 def random_rows(n, seed):
     """rows with ties, zeros, rows that `more` dominates, and counters of 2^32 - 1 and just below 2^40"""
