@@ -754,6 +754,51 @@ int vga_haplotype_jobs(uint64_t n_calls, const uint32_t *cpos, uint64_t n_sites,
                        uint32_t *jobs /* cap * 2 */, uint64_t *n_jobs);
 int vga_haplotype_call(const uint32_t *counts /* 7 */, char *text /* 3 */);
 
+/* ---- phase join: which phase sets of the chain the reads hold together ---------------------------------------
+ * Stands in for nothing in the reference.  The chain links sites at most eight apart in site order and joins nothing again; a long
+ * read is tagged in several sets at once, which is direct evidence about how the sets' haplotypes go together.  Integers only;
+ * defined on the alignments GAF, the rows of <out>-variants.tsv and the chain's ps and flip alone (tests/phase_join_ref.py
+ * recomputes it).
+ *   sets         the S sets of ps in ascending ps (a set is named by the site that opens it), numbered 0 .. S - 1.
+ *   tag          as for the haplotype counts: a for votes_a > votes_b of the haplotag row (r, s), b for votes_b > votes_a, none on a
+ *                tie or without a row.  The rule of vga_phase_tags, on the same observation tile (k_ph_obs, k_hc_tags).
+ *   table        for s <= t four uint32 n[2 i + j], i, j in 0 = a, 1 = b: the kept reads with tag(r, s) = i and tag(r, t) = j.  The
+ *                S (S + 1) / 2 rows lie in the upper triangle, row-major: row s S - s (s - 1) / 2 + (t - s), the order of the
+ *                genotype tables.  On the diagonal n[0] and n[3] are the reads tagged a and b in the set, n[1] = n[2] = 0.
+ *   join rule    for s < t: cis = n[0] + n[3], trans = n[1] + n[2], diff = |cis - trans|; a link when diff >= min_reads (1 ..
+ *                65 535; cis = trans is never one).  Links are taken by diff descending, then s, then t ascending.  A link whose
+ *                sets are in different components at its turn joins them, the haplotypes related trans when trans > cis, else
+ *                cis; a link inside one component joins nothing and is counted as agreeing or conflicting with the orientation the
+ *                component already implies.  The smallest set of a component names it and keeps its orientation.
+ *   vga_phase_set_links        the table from the context's own store; *n_reads the stored records (may be NULL).  *n_sets = S is
+ *                              always written (0 without a site or with an empty store: zero rows); with cap_rows < S (S + 1) / 2
+ *                              nothing is launched and no row is written, and the caller asks again.  Per tile of reads k_ph_obs,
+ *                              k_hc_tags, k_sj_bits (two bit rows per set, 64 reads to a word) and k_sj_pairs (a workgroup per tile
+ *                              of 32 x 32 set pairs); the table stays on the device across the tiles.  The tile's read count is a
+ *                              multiple of 64 sized from 64 MiB, VGA_PHASE_READ_TILE overrides it, and the table does not depend on
+ *                              it.  VGA_ERR_ARG for everything vga_phase_tags refuses; VGA_ERR_UNSUPPORTED for more than 4096 sets
+ *                              (the table is 134 MB there), before anything is launched.  A refusal leaves the outputs as they
+ *                              were.  Does not reset the store.
+ *   vga_phase_set_links_lists  the kernel seam, and the route of several contexts: the same from explicit records and words on a
+ *                              graph of n_bases bases, with every check of vga_phase_tags_lists (the same code).  Needs a context
+ *                              only.
+ *   vga_phase_join             no context, on the host: the one definition of the join rule (csrc/vga_phase_join.hpp).  set_root[s]:
+ *                              the set that names the component of s; set_flip[s]: the parity of s against it; joins: the accepted
+ *                              links in order as s, t, cis, trans (at most S - 1 of them; room for S - 1); *n_agree and *n_conflict:
+ *                              the links inside a component.  Per site ps'[h] is the name of set_root of the set of h and flip'[h]
+ *                              = flip[h] xor set_flip of it: what vga_phase_tags and vga_haplotype_counts take in the place of ps
+ *                              and flip.  VGA_ERR_ARG for min_reads outside 1 .. 65 535, more than 4096 sets or a NULL array it needs.
+ * Without these calls nothing changes: no k_sj_* launch, no extra allocation. */
+int vga_phase_set_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps,
+                        const uint8_t *flip, uint64_t cap_rows, uint32_t *table /* cap_rows * 4 */, uint64_t *n_sets, uint64_t *n_reads);
+int vga_phase_set_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs /* n_reads * 3 */, uint64_t n_words,
+                              const uint32_t *words, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
+                              const uint8_t *ref, const uint32_t *ps, const uint8_t *flip, uint64_t cap_rows,
+                              uint32_t *table /* cap_rows * 4 */, uint64_t *n_sets);
+int vga_phase_join(uint64_t n_sets, const uint32_t *table /* n_sets (n_sets + 1) / 2 * 4 */, uint32_t min_reads, uint32_t *set_root /* n_sets */,
+                   uint8_t *set_flip /* n_sets */, uint32_t *joins /* (n_sets - 1) * 4 */, uint64_t *n_joins, uint64_t *n_agree,
+                   uint64_t *n_conflict);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "vga_phase_begin", "vga_phase_read", "vga_phase_reset", "vga_phase_end", "vga_phase_links", "vga_phase_links_lists", "vga_phase_chain",
     "vga_phase_tags", "vga_phase_tags_lists",
     "vga_haplotype_counts", "vga_haplotype_counts_lists", "vga_haplotype_jobs", "vga_haplotype_call",
+    "vga_phase_set_links", "vga_phase_set_links_lists", "vga_phase_join",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -114,6 +115,13 @@ PHASE_TAG_COLS = 4
 HAPLOTYPE_ROW = 16
 HAPLOTYPE_MAX_CALLS = 1 << 24
 HAPLOTYPE_MAX_JOBS = 1 << 24
+# the set links (csrc/vga_phase_join.hpp): a row of the table is (a, a), (a, b), (b, a), (b, b); the sets of one call at most; the
+# side of k_sj_pairs' tile of set pairs; --phase-join-min-reads
+PHASE_JOIN_COLS = 4
+PHASE_JOIN_MAX_SETS = 4096
+PHASE_JOIN_TILE = 32
+PHASE_JOIN_MIN_READS = 2
+PHASE_JOIN_MAX_MIN_READS = 65535
 
 
 class VgaError(RuntimeError):
@@ -331,6 +339,10 @@ def load_library():
             L.vga_haplotype_counts_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
             L.vga_haplotype_jobs.argtypes = [u64, u32p, u64, u32p, u32p, u64, u32p, u64p]
             L.vga_haplotype_call.argtypes = [u32p, C.c_char_p]
+        if hasattr(L, "vga_phase_set_links"):  # (the set links came later than the haplotype counts)
+            L.vga_phase_set_links.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u8p, u64, u32p, u64p, u64p]
+            L.vga_phase_set_links_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
+            L.vga_phase_join.argtypes = [u64, u32p, C.c_uint32, u32p, u8p, u32p, u64p, u64p, u64p]
         for name in ABI_SYMBOLS:
             if name.startswith(("vga_phase_", "vga_haplotype_")) and hasattr(L, name):
                 getattr(L, name).restype = C.c_int
@@ -424,6 +436,25 @@ def phase_chain(links, min_links: int = PHASE_MIN_LINKS):
     if rc != VGA_OK:
         raise VgaError(rc, "phase_chain: min_links %r is 1 to %d" % (min_links, PHASE_MAX_MIN_LINKS))
     return ps[:n], flip[:n], link_d[:n]
+
+
+def phase_join(table, n_sets: int, min_reads: int = PHASE_JOIN_MIN_READS):
+    """vga_phase_join -> (set_root uint32[S], set_flip uint8[S], joins[J, 4] uint32 (s, t, cis, trans), n_agree, n_conflict) from the
+    table[S (S + 1) / 2, 4] of Context.phase_set_links: the library's one definition of the join rule (csrc/vga_phase_join.hpp);
+    needs no context and no device"""
+    n = int(n_sets)
+    tb = np.ascontiguousarray(table, dtype=np.uint32).reshape(-1, PHASE_JOIN_COLS)
+    if n < 0 or len(tb) != n * (n + 1) // 2:
+        raise VgaError(-1, "phase_join: %d sets and %d rows" % (n, len(tb)))
+    if not 0 <= int(min_reads) < 1 << 32:
+        raise VgaError(-1, "phase_join: min_reads %r" % (min_reads,))
+    root, flip, joins = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint8), np.zeros((max(1, n), PHASE_JOIN_COLS), dtype=np.uint32)
+    n_joins, n_agree, n_conflict = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = load_library().vga_phase_join(n, _u32p(tb if n else np.zeros(4, dtype=np.uint32)), int(min_reads), _u32p(root), flip.ctypes.data_as(_P(C.c_uint8)),
+                                       _u32p(joins), C.byref(n_joins), C.byref(n_agree), C.byref(n_conflict))
+    if rc != VGA_OK:
+        raise VgaError(rc, "phase_join: min_reads %r is 1 to %d, %d sets at most" % (min_reads, PHASE_JOIN_MAX_MIN_READS, PHASE_JOIN_MAX_SETS))
+    return root[:n], flip[:n], joins[:n_joins.value], int(n_agree.value), int(n_conflict.value)
 
 
 def haplotype_jobs(cpos, pos, ps):
@@ -1079,6 +1110,47 @@ class Context:
         return self._haplotype_counts(lambda sets, fl, cap, rows, n_rows: self.L.vga_haplotype_counts_lists(
             self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), len(cp), _u32p(pad(cp)), u8(pad(cr)), n, _u32p(at), u8(xs), u8(ys), u8(rf), sets,
             fl, cap, rows, n_rows), n, ps, flip, 4 * len(cp) + 64 if cap is None else cap)
+
+    def _phase_set_links(self, call, n, ps, flip):
+        """`call(ps, flip, cap_rows, table, n_sets)` is one of the two C calls with everything else bound: asked again with room for
+        the whole table when the first answer names more sets than it had room for (nothing was counted then)"""
+        sets = np.ascontiguousarray(ps, dtype=np.uint32).reshape(-1)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8).reshape(-1)
+        if len(sets) != n or len(fl) != n:
+            raise VgaError(-1, "phase set links: %d sites, %d ps and %d flip" % (n, len(sets), len(fl)))
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        cap = int((sets == np.arange(1, n + 1, dtype=np.uint32)).sum())
+        cap = cap * (cap + 1) // 2
+        while True:
+            table, n_sets = np.zeros((max(1, cap), PHASE_JOIN_COLS), dtype=np.uint32), C.c_uint64(0)
+            self._check(call(_u32p(pad(sets)), pad(fl).ctypes.data_as(_P(C.c_uint8)), cap, _u32p(table), C.byref(n_sets)))
+            rows = n_sets.value * (n_sets.value + 1) // 2
+            if rows <= cap:
+                return table[:rows], int(n_sets.value)
+            cap = rows
+
+    def phase_set_links(self, pos, x, y, ps, flip):
+        """vga_phase_set_links: for every pair of phase sets s <= t (ascending ps) the stored reads of this context tagged a or b in
+        both, at the sites pos, x, y of phase_links under the ps and flip of phase_chain -> (table[S (S + 1) / 2, 4] uint32: (a, a),
+        (a, b), (b, a), (b, b), rows in pair_index(S, s, t) order; n_sets; n_reads).  Does not reset."""
+        n, at, (xs, ys) = self._phase_sites(pos, x, y)
+        n_reads = C.c_uint64(0)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        table, n_sets = self._phase_set_links(lambda sets, fl, cap, table, n_sets: self.L.vga_phase_set_links(self.h, n, _u32p(at), u8(xs), u8(ys), sets, fl, cap, table,
+                                                                                                             n_sets, C.byref(n_reads)), n, ps, flip)
+        return table, n_sets, int(n_reads.value)
+
+    def phase_set_links_lists(self, recs, words, n_bases, pos, x, y, ref, ps, flip):
+        """vga_phase_set_links_lists, the kernel seam: the same from explicit records and words (phase_links_lists) -> (table, n_sets,
+        n_reads).  Needs a context only."""
+        rc = np.ascontiguousarray(recs, dtype=np.uint32).reshape(-1, 3)
+        wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        n, at, (xs, ys, rf) = self._phase_sites(pos, x, y, ref)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=np.uint32)
+        table, n_sets = self._phase_set_links(lambda sets, fl, cap, table, n_sets: self.L.vga_phase_set_links_lists(
+            self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), n, _u32p(at), u8(xs), u8(ys), u8(rf), sets, fl, cap, table, n_sets), n, ps, flip)
+        return table, n_sets, len(rc)
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

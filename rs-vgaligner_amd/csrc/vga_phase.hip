@@ -1,7 +1,9 @@
 // vga_phase.hip -- the read-backed linkage of heterozygous sites and the reads' haplotype tags: k_ph_keep, k_ph_obs, k_ph_link,
 // k_ph_tag, k_ph_tag_scan and the C entry points vga_phase_begin / _read / _reset / _end / _links / _links_lists / _chain / _tags /
 // _tags_lists; and what the tagged reads of each haplotype show at the calls: k_hc_tags, k_hc_cols, k_hc_count and vga_haplotype_counts /
-// _counts_lists / _jobs / _call.  See vga_phase.hpp and vga_hapcall.hpp for the shape.  Links, tags and counts run on one ph_frame.
+// _counts_lists / _jobs / _call; and which sets the reads tagged in two of them hold together: k_sj_bits, k_sj_pairs and
+// vga_phase_set_links / _set_links_lists / vga_phase_join.  See vga_phase.hpp, vga_hapcall.hpp and vga_phase_join.hpp for the shape.
+// Links, tags, counts and set links run on one ph_frame.
 //
 // Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
 // read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
@@ -10,6 +12,8 @@
 // b] counts the reads with obs a at site h and b at site h + d.  ORs and sums of integers: the tables are exact and repeatable.
 #include "vga_phase.hpp"
 #include "vga_hapcall.hpp"
+#include "vga_phase_join.hpp"
+#include "vga_pair_tile.hpp"
 #include "vga_pileup.hpp"
 
 // the store keeps k_pu_events' words as they are
@@ -18,6 +22,9 @@ static_assert(PH_COL_OTHER == PU_COL_N && PH_COL_DEL == PU_COL_DEL && PH_COL_INS
 // a column of a sparse word is a bit of a byte of k_hc_cols and a counter of a row
 static_assert(HC_COLS == PH_COLS && HC_COL_DEL == PH_COL_DEL && HC_COL_INS == PH_COL_INS && HC_ROW == 2u + 2u * HC_COLS && HC_MAX_CALLS == PH_MAX_SITES,
               "the columns of the haplotype counts");
+// k_sj_pairs stages a chunk of both ranges with whole rounds of its threads, and a thread owns whole squares of the pair frame
+static_assert(PJ_TILE % 16u == 0 && (PJ_CHUNK_ROWS * PJ_TILE) % PAIR_TILE_THREADS == 0 && PJ_CHUNK_ROWS % 2u == 0 && PJ_BITS_SETS == 64u,
+              "the tile of the set links");
 
 namespace {
 
@@ -323,6 +330,101 @@ __global__ __launch_bounds__(HC_COUNT_BLOCK) void k_hc_count(uint32_t n_jobs, ui
         for (uint32_t w = 0; w < HC_COUNT_BLOCK / 64u; w++) s += part[w][tid - 2u];
         row[tid] += s;
     }
+}
+
+// ---- the set links (vga_phase_join.hpp), behind the unchanged k_ph_obs and k_hc_tags
+
+// One wave per word of 64 reads and PJ_BITS_SETS sets.  Per set a ballot over the 64 tag bytes of the word (one line), "tagged a" and
+// "tagged b"; lane k keeps the two words of the k-th set, and the wave stores 64 sets of a bit row at once.  Bit row 2 w is "tagged
+// a" of word w for every set, row 2 w + 1 "tagged b": S words each.  No load is under a lane mask: a lane behind the tile's last read
+// takes that read and is masked out of both ballots.
+__global__ __launch_bounds__(64) void k_sj_bits(uint32_t n, uint32_t tile_reads, uint32_t n_sets, const uint8_t *__restrict__ tags, uint64_t *__restrict__ bits)
+{
+    const uint32_t w = blockIdx.x, s0 = blockIdx.y * PJ_BITS_SETS, lane = threadIdx.x;
+    if (w * 64u >= n || s0 >= n_sets) return;
+    const uint32_t r = w * 64u + lane < n ? w * 64u + lane : n - 1u;
+    const uint64_t live = __builtin_amdgcn_ballot_w64(w * 64u + lane < n);
+    const uint32_t sets = n_sets - s0 < PJ_BITS_SETS ? n_sets - s0 : PJ_BITS_SETS;
+    const uint8_t *col = tags + (size_t)s0 * tile_reads + r;
+    uint64_t mine_a = 0, mine_b = 0;
+    for (uint32_t k = 0; k < sets; k++) {
+        const uint32_t tag = col[(size_t)k * tile_reads];
+        const uint64_t is_a = __builtin_amdgcn_ballot_w64(tag == 1u) & live, is_b = __builtin_amdgcn_ballot_w64(tag == 2u) & live;
+        if (lane == k) { mine_a = is_a; mine_b = is_b; }
+    }
+    if (lane < sets) {
+        bits[(size_t)(2u * w) * n_sets + s0 + lane] = mine_a;
+        bits[(size_t)(2u * w + 1u) * n_sets + s0 + lane] = mine_b;
+    }
+}
+
+// One workgroup per PJ_TILE x PJ_TILE tile of pairs of sets s <= t (the frame of vga_pair_tile.hpp with the bit rows in the place
+// of the reads, one group of them), thread (ty, tx) owning the pairs s = s0 + ty + 16 i, t = t0 + tx + 16 j.  Per chunk of
+// PJ_CHUNK_ROWS bit rows the words of the s range and of the t range are staged in LDS row-major (row, then set: the sixteen tx of
+// a half wave read sixteen neighbouring 64-bit words, the two ty of it two more: no two on one bank); per pair and word four ANDs
+// and popcounts into four counters in registers.  A row or a set past the end is staged as zero and counts nothing.  The workgroup
+// owns its rows of the table and the tiles of reads run one after another on the stream: plain loads and stores add its sums.
+__global__ __launch_bounds__(PAIR_TILE_THREADS) void k_sj_pairs(uint32_t n_rows, uint32_t n_sets, uint32_t n_side, const uint64_t *__restrict__ bits,
+                                                                 uint32_t *__restrict__ table)
+{
+    constexpr uint32_t SUB = PJ_TILE / 16u, ROUNDS = PJ_CHUNK_ROWS * PJ_TILE / PAIR_TILE_THREADS;
+    __shared__ uint64_t sh[2][PJ_CHUNK_ROWS][PJ_TILE];
+    const pair_tile T = pair_tile_open<PJ_TILE>(n_rows, n_sets, n_side, n_rows);
+    const uint32_t tid = threadIdx.x;
+    uint32_t cnt[SUB][SUB][PJ_COLS];
+#pragma unroll
+    for (uint32_t i = 0; i < SUB; i++)
+#pragma unroll
+        for (uint32_t j = 0; j < SUB; j++)
+#pragma unroll
+            for (uint32_t k = 0; k < PJ_COLS; k++) cnt[i][j][k] = 0;
+    for (uint32_t r0 = T.r_begin; r0 < T.r_end; r0 += PJ_CHUNK_ROWS) {
+        uint64_t v[2][ROUNDS];  // (the loads of both ranges are in flight together)
+#pragma unroll
+        for (uint32_t side = 0; side < 2u; side++)
+#pragma unroll
+            for (uint32_t k = 0; k < ROUNDS; k++) {
+                const pair_slot e = pair_tile_slot<PJ_TILE>(T, n_sets, k, tid, r0, side);
+                const uint64_t got = bits[e.have ? (size_t)e.read * n_sets + e.path : 0];
+                v[side][k] = e.have ? got : 0ull;
+            }
+        __syncthreads();  // (the chunk before has been counted)
+#pragma unroll
+        for (uint32_t side = 0; side < 2u; side++)
+#pragma unroll
+            for (uint32_t k = 0; k < ROUNDS; k++) {
+                const pair_slot e = pair_tile_slot<PJ_TILE>(T, n_sets, k, tid, r0, side);
+                sh[side][e.row][e.col] = v[side][k];
+            }
+        __syncthreads();
+#pragma unroll 4
+        for (uint32_t w = 0; w < PJ_CHUNK_ROWS; w += 2u) {
+            uint64_t sa[SUB], sb[SUB], ta[SUB], tb[SUB];
+#pragma unroll
+            for (uint32_t i = 0; i < SUB; i++) {
+                sa[i] = sh[0][w][T.ty + 16u * i];
+                sb[i] = sh[0][w + 1u][T.ty + 16u * i];
+                ta[i] = sh[1][w][T.tx + 16u * i];
+                tb[i] = sh[1][w + 1u][T.tx + 16u * i];
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < SUB; i++)
+#pragma unroll
+                for (uint32_t j = 0; j < SUB; j++) {
+                    cnt[i][j][0] += (uint32_t)__builtin_popcountll(sa[i] & ta[j]);
+                    cnt[i][j][1] += (uint32_t)__builtin_popcountll(sa[i] & tb[j]);
+                    cnt[i][j][2] += (uint32_t)__builtin_popcountll(sb[i] & ta[j]);
+                    cnt[i][j][3] += (uint32_t)__builtin_popcountll(sb[i] & tb[j]);
+                }
+        }
+    }
+    if (!T.live) return;
+    uint4 *rows = reinterpret_cast<uint4 *>(table);
+    pair_tile_each<SUB>(T, n_sets, [&](uint32_t i, uint32_t j, uint64_t at) {
+        uint4 n = rows[at];
+        n.x += cnt[i][j][0]; n.y += cnt[i][j][1]; n.z += cnt[i][j][2]; n.w += cnt[i][j][3];
+        rows[at] = n;
+    });
 }
 
 }  // namespace
@@ -795,6 +897,63 @@ int hc_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, const hc_calls 
     return f.close();
 }
 
+// the sets of a checked ps: the sites that open one
+uint64_t sj_count_sets(uint64_t n_sites, const uint32_t *ps)
+{
+    uint64_t sets = 0;
+    for (uint64_t h = 0; h < n_sites; h++) sets += ps[h] == h + 1u ? 1u : 0u;
+    return sets;
+}
+
+// The sets of the set links: somewhere for their number, and for the table when it has room; everything ph_check_sets asks of ps
+// and flip; PJ_MAX_SETS sets at most.  Before the frame is made: a refusal uploads and launches nothing.
+int sj_check_sets(vga_ctx *ctx, const char *who, uint64_t n_sites, const uint32_t *ps, const uint8_t *flip, uint64_t cap_rows, const uint32_t *table,
+                  const uint64_t *n_sets)
+{
+    if (!n_sets || (cap_rows && !table)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null output (n_sets always, table with cap_rows above 0)", who);
+    const int rc = ph_check_sets(ctx, who, n_sites, ps, flip, cap_rows, table, n_sets);
+    if (rc != VGA_OK) return rc;
+    const uint64_t sets = sj_count_sets(n_sites, ps);
+    if (sets > PJ_MAX_SETS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu phase sets, %u at most", who, (unsigned long long)sets, PJ_MAX_SETS);
+    return VGA_OK;
+}
+
+// Per tile of reads k_hc_tags, k_sj_bits and k_sj_pairs behind k_ph_obs over the frame's reads; the table stays on the device across
+// the tiles and comes back once.  *n_sets = S always (0 without a site or a read); the S (S + 1) / 2 rows when cap_rows has room for
+// them, nothing launched otherwise.  Everything was checked by the caller (sj_check_sets).
+int sj_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, uint64_t cap_rows, uint32_t *table, uint64_t *n_sets)
+{
+    vga_ctx *ctx = f.ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t sets = f.n_reads ? sj_count_sets(f.s.n, ps) : 0;
+    *n_sets = sets;
+    const uint64_t n_pairs = vga_pair_count(sets);
+    if (sets == 0 || cap_rows < n_pairs) return VGA_OK;
+    const uint32_t H = f.H, S = f.group(ps, flip), side = (S + PJ_TILE - 1u) / PJ_TILE;
+    vga_dbuf<uint32_t> d_table;
+    int rc = pair_exact_alloc(ctx, d_table, (size_t)n_pairs * PJ_COLS);
+    if (rc == VGA_OK) rc = f.open(0, S + (S + 3u) / 4u);  // the tile: obs, tags, and two bits per tag byte
+    if (rc != VGA_OK) return rc;
+    uint8_t *d_tags = (uint8_t *)(f.d_tile.p + f.clear_words);
+    uint64_t *d_bits = (uint64_t *)(d_tags + (size_t)S * f.T);
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_table.p, 0, (size_t)n_pairs * PJ_COLS * 4, st));
+    rc = f.each_tile([&](uint64_t, uint32_t n) {
+        const uint32_t words = (n + 63u) / 64u;
+        int rc = vga_launch(ctx, "k_hc_tags", (uint64_t)(H + S) * n, k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), n, f.T, (const uint8_t *)f.d_tile.p, S,
+                           f.d_sets.p, f.d_sets.p + 2 * (size_t)S + 1u, d_tags);
+        if (rc == VGA_OK)
+            rc = vga_launch(ctx, "k_sj_bits", (uint64_t)S * n + (uint64_t)S * words * 16u, k_sj_bits, dim3(words, (S + PJ_BITS_SETS - 1u) / PJ_BITS_SETS), dim3(64), n, f.T, S,
+                            (const uint8_t *)d_tags, d_bits);
+        if (rc == VGA_OK)
+            rc = vga_launch(ctx, "k_sj_pairs", (uint64_t)side * S * words * 16u + 2 * n_pairs * PJ_COLS * 4u, k_sj_pairs, dim3((uint32_t)vga_pair_count(side)), dim3(PAIR_TILE_THREADS),
+                            2u * words, S, side, (const uint64_t *)d_bits, d_table.p);
+        return rc;
+    });
+    if (rc != VGA_OK) return rc;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(table, d_table.p, (size_t)n_pairs * PJ_COLS * 4, hipMemcpyDeviceToHost, st));
+    return f.close();
+}
+
 }  // namespace
 
 extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, uint32_t *links, uint32_t *site_reads,
@@ -900,6 +1059,42 @@ extern "C" int vga_haplotype_call(const uint32_t *counts, char *text)
 {
     if (!counts || !text) return VGA_ERR_ARG;
     hc_call_text(hc_call(counts), text);
+    return VGA_OK;
+}
+
+extern "C" int vga_phase_set_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps, const uint8_t *flip,
+                                   uint64_t cap_rows, uint32_t *table, uint64_t *n_sets, uint64_t *n_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const ph_sites s = {n_sites, pos, x, y, nullptr};
+    int rc = ph_check_store(ctx, "vga_phase_set_links", s, true);
+    if (rc == VGA_OK) rc = sj_check_sets(ctx, "vga_phase_set_links", n_sites, ps, flip, cap_rows, table, n_sets);
+    if (rc != VGA_OK) return rc;
+    ph_frame f(ctx, s);
+    f.from_store(n_reads);
+    return sj_run(f, ps, flip, cap_rows, table, n_sets);
+}
+
+extern "C" int vga_phase_set_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words,
+                                         uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint8_t *ref, const uint32_t *ps,
+                                         const uint8_t *flip, uint64_t cap_rows, uint32_t *table, uint64_t *n_sets)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const ph_sites s = {n_sites, pos, x, y, ref};
+    int rc = ph_check_lists(ctx, "vga_phase_set_links_lists", n_bases, n_reads, recs, n_words, words, s, true);
+    if (rc == VGA_OK) rc = sj_check_sets(ctx, "vga_phase_set_links_lists", n_sites, ps, flip, cap_rows, table, n_sets);
+    if (rc != VGA_OK) return rc;
+    ph_frame f(ctx, s);
+    const int up = f.from_lists(n_reads, recs, n_words, words);
+    return up != VGA_OK ? up : sj_run(f, ps, flip, cap_rows, table, n_sets);
+}
+
+extern "C" int vga_phase_join(uint64_t n_sets, const uint32_t *table, uint32_t min_reads, uint32_t *set_root, uint8_t *set_flip, uint32_t *joins, uint64_t *n_joins,
+                              uint64_t *n_agree, uint64_t *n_conflict)
+{
+    if (min_reads < 1u || min_reads > PJ_MIN_READS_MAX || n_sets > PJ_MAX_SETS) return VGA_ERR_ARG;
+    if (!n_joins || !n_agree || !n_conflict || (n_sets && (!table || !set_root || !set_flip)) || (n_sets > 1 && !joins)) return VGA_ERR_ARG;
+    pj_join(n_sets, table, min_reads, set_root, set_flip, joins, n_joins, n_agree, n_conflict);
     return VGA_OK;
 }
 

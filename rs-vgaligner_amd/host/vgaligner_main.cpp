@@ -76,7 +76,11 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           {"", "--haplotag", false, "haplotag"},
                           // not in the reference: what the reads tagged a and the reads tagged b of each phase set show at every
                           // reported call inside the set's span, counted on the GPU, and a haploid call on each (one TSV file)
-                          {"", "--haplotype-calls", false, "haplotype-calls"}};
+                          {"", "--haplotype-calls", false, "haplotype-calls"},
+                          // not in the reference: the phase sets of --phase joined by the reads that are tagged in two of them,
+                          // counted on the GPU (three TSV files; --haplotag and --haplotype-calls then work on the joined sets);
+                          // --phase-join-min-reads N: the reads by which cis and trans must differ for a link (2, 1..65535)
+                          {"", "--phase-join", false, "phase-join"}, {"", "--phase-join-min-reads", true, "phase-join-min-reads"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -233,6 +237,15 @@ int map_main(int argc, char **argv)
     if (o.haplotag && !o.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
     o.haplotype_calls = m.count("haplotype-calls") > 0;
     if (o.haplotype_calls && !o.haplotag) throw Error("--haplotype-calls counts what the reads tagged by --haplotag show: it needs --haplotag");
+    o.phase_join = m.count("phase-join") > 0;
+    if (o.phase_join && !o.phase) throw Error("--phase-join joins the phase sets of --phase: it needs --phase");
+    if (m.count("phase-join-min-reads")) {
+        const std::string v = m["phase-join-min-reads"];
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoul(v) < 1 || std::stoul(v) > 65535)
+            throw Error("--phase-join-min-reads takes a number from 1 to 65535: not " + v);
+        if (!o.phase_join) throw Error("--phase-join-min-reads has no meaning without --phase-join");
+        o.phase_join_min_reads = (uint32_t)std::stoul(v);
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -314,6 +327,10 @@ int map_main(int argc, char **argv)
     if (o.phase)
         fprintf(stderr, "[vgaligner] phase: %llu heterozygous sites, %llu phase sets, %llu reads kept\n", (unsigned long long)out.n_phase_sites,
                 (unsigned long long)out.n_phase_sets, (unsigned long long)out.n_phase_reads);
+    if (o.phase_join)
+        fprintf(stderr, "[vgaligner] phase-join: %llu sets, %llu joins, %llu sets left, %llu agreeing, %llu conflicting links\n", (unsigned long long)out.n_join_sets,
+                (unsigned long long)out.n_joins, (unsigned long long)(out.n_join_sets - out.n_joins), (unsigned long long)out.n_join_agree,
+                (unsigned long long)out.n_join_conflict);
     if (o.haplotag)
         fprintf(stderr, "[vgaligner] haplotag: %llu rows of %llu reads: %llu a, %llu b, %llu undecided\n", (unsigned long long)out.n_haplotag_rows,
                 (unsigned long long)out.n_phase_reads, (unsigned long long)out.n_haplotag_a, (unsigned long long)out.n_haplotag_b,
@@ -368,7 +385,8 @@ int main(int argc, char **argv)
                         "                [--path-edit]\n"
                         "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
                         "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n"
-                        "                                 (with --haplotag: [--haplotype-calls])\n");
+                        "                                 (with --haplotag: [--haplotype-calls])\n"
+                        "                                 (with --phase: [--phase-join [--phase-join-min-reads 2]])\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

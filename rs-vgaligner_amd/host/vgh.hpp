@@ -219,6 +219,13 @@ struct MapOptions {
     // (vga_haplotype_counts; several contexts: vga_haplotype_counts_lists on the first, from the concatenated stores), a haploid
     // call on each (vga_hapcall.hpp: hc_call), and write <out>-haplotype-calls.tsv
     bool haplotype_calls = false;
+    // --phase-join (not in the reference; needs phase): join the phase sets of the chain by the reads that are tagged in two of
+    // them, counted on the GPU from the same store behind the chain (vga_phase_set_links; several contexts:
+    // vga_phase_set_links_lists on the first, from the concatenated stores), the join rule of vga_phase_join.hpp with links of at
+    // least phase_join_min_reads reads (1 .. 65535), and write <out>-phase-joined.tsv, <out>-phase-sets.tsv and
+    // <out>-phase-joins.tsv; haplotag and haplotype_calls then work on the joined sets.  <out>-phase.tsv stays the chain's.
+    bool phase_join = false;
+    uint32_t phase_join_min_reads = 2;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -237,6 +244,7 @@ struct MapOutput {
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
     uint64_t n_phase_sites = 0, n_phase_sets = 0, n_phase_reads = 0;  // heterozygous sites, phase sets and reads kept (MapOptions::phase)
     uint64_t n_haplotag_rows = 0, n_haplotag_a = 0, n_haplotag_b = 0, n_haplotag_tied = 0;  // rows and their haplotypes (MapOptions::haplotag)
+    uint64_t n_join_sets = 0, n_joins = 0, n_join_agree = 0, n_join_conflict = 0;  // chain sets, accepted links, links inside a component (MapOptions::phase_join)
     uint64_t n_hapcall_jobs = 0, n_hapcall_rows = 0, n_hapcall_differ = 0;  // jobs, lines written, lines whose two decided calls differ (MapOptions::haplotype_calls)
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)

@@ -5,6 +5,7 @@
 #include "../csrc/vga_pair_index.hpp"
 #include "../csrc/vga_phase.hpp"
 #include "../csrc/vga_hapcall.hpp"
+#include "../csrc/vga_phase_join.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -115,6 +116,27 @@ void hap_counts_fetch(vga_ctx *ctx, HaplotypeCounts &h, uint64_t n_calls, F call
     h.rows.resize(h.n_rows * HC_ROW);
 }
 
+// `call(cap_rows, table, &n_sets)` is one of the two library calls with everything before cap_rows bound, asked with room for the
+// table of the chain's sets (more than PJ_MAX_SETS: refused with the count).  Then the join rule on the table, and per site the
+// joined ps and flip.
+template <typename F>
+void join_fetch(vga_ctx *ctx, PhaseJoin &j, const PhaseLinks &p, uint32_t min_reads, F call)
+{
+    const size_t n = p.pos.size();
+    j.set_ps.clear();
+    for (size_t h = 0; h < n; h++)
+        if (p.ps[h] == h + 1u) j.set_ps.push_back((uint32_t)(h + 1u));
+    const uint64_t S = j.n_sets = j.set_ps.size(), rows = vga_pair_count(S);
+    j.table.assign(rows * PJ_COLS + PJ_COLS, 0);  // (an empty store leaves it so)
+    uint64_t counted = 0;
+    check(ctx, call(rows, j.table.data(), &counted));
+    if (counted != S && counted != 0) throw Error("--phase-join: the chain has " + std::to_string(S) + " sets, and " + std::to_string(counted) + " were counted");
+    j.set_root.assign(S + 1, 0); j.set_flip.assign(S + 1, 0); j.joins.assign((S + 1) * PJ_JOIN_COLS, 0);
+    pj_join(S, j.table.data(), min_reads, j.set_root.data(), j.set_flip.data(), j.joins.data(), &j.n_joins, &j.n_agree, &j.n_conflict);
+    j.ps.assign(n + 1, 0); j.flip.assign(n + 1, 0);
+    pj_sites(n, p.ps.data(), p.flip.data(), j.set_root.data(), j.set_flip.data(), j.ps.data(), j.flip.data());
+}
+
 // ---- the writers.  Each gets its table padded to the sizes it indexes.
 
 void coverage_write(const Index &ix, const Counters &s, const std::string &out_prefix)
@@ -202,20 +224,17 @@ void insertion_write(const Index &ix, const VariantCalls &v, const InsertionCall
 
 // one line per heterozygous site: where it is, the genotype with haplotype a first, the set, the link that joined it (how many
 // sites back, 0 for none) with the reads for and against it, and what the reads show at the site
-void phase_write(const Index &ix, PhaseLinks &p, uint32_t min_links, MapOutput &out, const std::string &out_prefix)
+// (the lines under the sets ps and flip: the chain's own, or the joined ones of --phase-join; the link columns are the chain's)
+std::string phase_text(const Index &ix, const PhaseLinks &p, const std::vector<uint32_t> &ps, const std::vector<uint8_t> &flip)
 {
     static const char ALLELES[] = "ACGT-";
     const size_t n = p.pos.size();
-    p.chain(min_links);
-    const std::vector<uint32_t> &ps = p.ps;
-    const std::vector<uint8_t> &flip = p.flip, &link_d = p.link_d;
+    const std::vector<uint8_t> &link_d = p.link_d;
     std::string t = "node\toffset\tgt\tps\tlink\tcis\ttrans\tx_reads\ty_reads\tother_reads\n";
     uint64_t id = 1;  // the sites come in base order: the node moves forward only
-    out.n_phase_sites = n; out.n_phase_sets = 0; out.n_phase_reads = p.n_reads;
     for (size_t h = 0; h < n; h++) {
         const uint64_t at = p.pos[h];
         while (id < ix.n_nodes && ix.node_ref[id].seq_idx <= at) id++;
-        out.n_phase_sets += link_d[h] == 0 ? 1u : 0u;
         uint64_t cis = 0, trans = 0;
         if (link_d[h]) {
             const uint32_t *l = p.links.data() + ((h - link_d[h]) * PH_WINDOW + (link_d[h] - 1u)) * PH_LINK_COLS;
@@ -227,7 +246,43 @@ void phase_write(const Index &ix, PhaseLinks &p, uint32_t min_links, MapOutput &
         for (uint32_t c = 0; c < PH_SITE_COLS; c++) { t += '\t'; put_u64(t, p.site_reads[h * PH_SITE_COLS + c]); }
         t += '\n';
     }
+    return t;
+}
+
+void phase_write(const Index &ix, PhaseLinks &p, uint32_t min_links, MapOutput &out, const std::string &out_prefix)
+{
+    p.chain(min_links);
+    out.n_phase_sites = p.pos.size(); out.n_phase_sets = 0; out.n_phase_reads = p.n_reads;
+    for (size_t h = 0; h < p.pos.size(); h++) out.n_phase_sets += p.link_d[h] == 0 ? 1u : 0u;
+    const std::string t = phase_text(ix, p, p.ps, p.flip);
     if (!out_prefix.empty()) write_file(out_prefix + "-phase.tsv", t);
+}
+
+// <out>-phase-joined.tsv: the lines of <out>-phase.tsv under the joined sets; <out>-phase-sets.tsv: one line per chain set, its
+// sites, the reads tagged a and b in it (the diagonal of the table), the set that names its component and its parity against it;
+// <out>-phase-joins.tsv: one line per accepted link, in the order of the join
+void phase_join_write(const Index &ix, const PhaseLinks &p, const PhaseJoin &j, MapOutput &out, const std::string &out_prefix)
+{
+    const uint64_t S = j.n_sets;
+    out.n_join_sets = S; out.n_joins = j.n_joins; out.n_join_agree = j.n_agree; out.n_join_conflict = j.n_conflict;
+    if (out_prefix.empty()) return;
+    write_file(out_prefix + "-phase-joined.tsv", phase_text(ix, p, j.ps, j.flip));
+    std::vector<uint64_t> sites(S + 1, 0);
+    for (size_t h = 0; h < p.pos.size(); h++) sites[(size_t)(std::lower_bound(j.set_ps.begin(), j.set_ps.end(), p.ps[h]) - j.set_ps.begin())]++;
+    std::string t = "ps\tsites\treads_a\treads_b\tjoined_ps\tflip\n";
+    for (uint64_t s = 0; s < S; s++) {
+        const uint32_t *n = j.table.data() + vga_pair_index(S, s, s) * PJ_COLS;
+        put_u64(t, j.set_ps[s]); t += '\t'; put_u64(t, sites[s]); t += '\t'; put_u64(t, n[0]); t += '\t'; put_u64(t, n[3]); t += '\t';
+        put_u64(t, j.set_ps[j.set_root[s]]); t += '\t'; put_u64(t, j.set_flip[s]); t += '\n';
+    }
+    write_file(out_prefix + "-phase-sets.tsv", t);
+    t = "ps_a\tps_b\tcis\ttrans\trel\n";
+    for (uint64_t k = 0; k < j.n_joins; k++) {
+        const uint32_t *l = j.joins.data() + k * PJ_JOIN_COLS;
+        put_u64(t, j.set_ps[l[0]]); t += '\t'; put_u64(t, j.set_ps[l[1]]); t += '\t'; put_u64(t, l[2]); t += '\t'; put_u64(t, l[3]); t += '\t';
+        t += l[3] > l[2] ? "trans" : "cis"; t += '\n';
+    }
+    write_file(out_prefix + "-phase-joins.tsv", t);
 }
 
 // one line per (kept read, phase set) in which a site votes: the read as the input file numbers it, the set as <out>-phase.tsv
@@ -399,6 +454,8 @@ void check_aligner(const MapOptions &opt)
     if (opt.phase && (opt.phase_min_links < 1 || opt.phase_min_links > PH_MIN_LINKS_MAX)) throw Error("--phase-min-links is 1 to 65535");
     if (opt.haplotag && !opt.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
     if (opt.haplotype_calls && !opt.haplotag) throw Error("--haplotype-calls counts what the reads tagged by --haplotag show: it needs --haplotag");
+    if (opt.phase_join && !opt.phase) throw Error("--phase-join joins the phase sets of --phase: it needs --phase");
+    if (opt.phase_join && (opt.phase_join_min_reads < 1 || opt.phase_join_min_reads > PJ_MIN_READS_MAX)) throw Error("--phase-join-min-reads is 1 to 65535");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -516,16 +573,19 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         phase_sites();
         PhaseLinks &p = phase_;
         check(ctx, vga_phase_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.links.data(), p.site_reads.data(), &p.n_reads));
-        if (tagging()) {
-            p.chain(opt_.phase_min_links);
-            tags_fetch(ctx, tags_, p.n_reads, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
-                return vga_phase_tags(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(), p.flip.data(), cap, rows, n_rows, nullptr);
+        if (tagging() || joining()) p.chain(opt_.phase_min_links);
+        if (joining())  // the sets of the chain just made; what follows works on the joined ones
+            join_fetch(ctx, join_, p, opt_.phase_join_min_reads, [&](uint64_t cap_rows, uint32_t *table, uint64_t *n_sets) {
+                return vga_phase_set_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(), p.flip.data(), cap_rows, table, n_sets, nullptr);
             });
-        }
-        if (hap_calling())  // every call just made, under the chain just made
+        if (tagging())
+            tags_fetch(ctx, tags_, p.n_reads, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
+                return vga_phase_tags(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), sets_ps().data(), sets_flip().data(), cap, rows, n_rows, nullptr);
+            });
+        if (hap_calling())  // every call just made, under the sets just made
             hap_counts_fetch(ctx, hap_counts_, variants_.n_calls, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
-                return vga_haplotype_counts(ctx, variants_.n_calls, variants_.pos.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(),
-                                            p.flip.data(), cap, rows, n_rows, nullptr);
+                return vga_haplotype_counts(ctx, variants_.n_calls, variants_.pos.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), sets_ps().data(),
+                                            sets_flip().data(), cap, rows, n_rows, nullptr);
             });
     } else if (phasing()) {  // the whole store: the context may be gone before the summed call
         PhaseStore s;
@@ -611,11 +671,18 @@ void Tables::call(vga_ctx *ctx)
         check(ctx, vga_phase_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
                                          p.y.data(), ref.data(), p.links.data(), p.site_reads.data()));
         trace_mark("phase links counted");
+        if (tagging() || joining()) p.chain(opt_.phase_min_links);
+        if (joining()) {
+            join_fetch(ctx, join_, p, opt_.phase_join_min_reads, [&](uint64_t cap_rows, uint32_t *table, uint64_t *n_sets) {
+                return vga_phase_set_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
+                                                 p.y.data(), ref.data(), p.ps.data(), p.flip.data(), cap_rows, table, n_sets);
+            });
+            trace_mark("phase sets joined");
+        }
         if (tagging()) {
-            p.chain(opt_.phase_min_links);
             tags_fetch(ctx, tags_, p.n_reads, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
                 return vga_phase_tags_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
-                                            p.y.data(), ref.data(), p.ps.data(), p.flip.data(), cap, rows, n_rows);
+                                            p.y.data(), ref.data(), sets_ps().data(), sets_flip().data(), cap, rows, n_rows);
             });
             trace_mark("reads tagged");
         }
@@ -624,8 +691,8 @@ void Tables::call(vga_ctx *ctx)
             for (uint64_t j = 0; j < variants_.n_calls; j++) cref[j] = ph_ref_of(ix_.seq_fwd[variants_.pos[j]]);
             hap_counts_fetch(ctx, hap_counts_, variants_.n_calls, [&](uint64_t cap, uint32_t *rows, uint64_t *n_rows) {
                 return vga_haplotype_counts_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), variants_.n_calls,
-                                                  variants_.pos.data(), cref.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), ref.data(), p.ps.data(),
-                                                  p.flip.data(), cap, rows, n_rows);
+                                                  variants_.pos.data(), cref.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), ref.data(), sets_ps().data(),
+                                                  sets_flip().data(), cap, rows, n_rows);
             });
             trace_mark("haplotypes counted");
         }
@@ -685,6 +752,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
     if (phasing()) {
         phase_write(ix_, phase_, opt_.phase_min_links, out, out_prefix);
         trace_mark("phase written");
+        if (joining()) {
+            phase_join_write(ix_, phase_, join_, out, out_prefix);
+            trace_mark("phase join written");
+        }
         if (tagging()) {
             haplotag_write(tags_, out, out_prefix);
             trace_mark("haplotags written");

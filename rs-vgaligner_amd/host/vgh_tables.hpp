@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -74,6 +74,17 @@ struct HaplotypeCounts {
     uint64_t n_rows = 0;
 };
 
+// The set links of the chain's sets and what the join rule makes of them (MapOptions::phase_join): the table of four counters per
+// pair of sets, per chain set its name, the set that names its component and its parity against it, the accepted links (s, t, cis,
+// trans), and per site the joined ps and flip that the tags and the haplotype counts take in the place of the chain's
+struct PhaseJoin {
+    std::vector<uint32_t> table, set_ps, set_root, joins;
+    std::vector<uint8_t> set_flip;
+    uint64_t n_sets = 0, n_joins = 0, n_agree = 0, n_conflict = 0;
+    std::vector<uint32_t> ps;
+    std::vector<uint8_t> flip;
+};
+
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
 struct ReadRows {
     std::string path, edit;
@@ -98,6 +109,7 @@ public:
     bool phasing() const { return opt_.phase; }
     bool tagging() const { return opt_.haplotag; }
     bool hap_calling() const { return opt_.haplotype_calls; }
+    bool joining() const { return opt_.phase_join; }
     bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
     // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
     bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
@@ -137,6 +149,10 @@ private:
     PhaseLinks phase_;
     PhaseTags tags_;  // (read_ids: of this context's store, then of the concatenated stores)
     HaplotypeCounts hap_counts_;
+    PhaseJoin join_;
+    // the sets the tags and the haplotype counts work on: the joined ones under --phase-join, else the chain's
+    const std::vector<uint32_t> &sets_ps() const { return joining() ? join_.ps : phase_.ps; }
+    const std::vector<uint8_t> &sets_flip() const { return joining() ? join_.flip : phase_.flip; }
     // the heterozygous variant calls as sites; sizes the tables of phase_
     void phase_sites();
     // the positions of the variant calls whose insertion state is het or hom; fills ins_calls_.site and sizes its arrays
