@@ -799,6 +799,62 @@ int vga_phase_join(uint64_t n_sets, const uint32_t *table /* n_sets (n_sets + 1)
                    uint8_t *set_flip /* n_sets */, uint32_t *joins /* (n_sets - 1) * 4 */, uint64_t *n_joins, uint64_t *n_agree,
                    uint64_t *n_conflict);
 
+/* ---- haplotype paths: which P line each haplotype of each phase set looks like -----------------------------
+ * Stands in for nothing in the reference.  The path stages rank pairs of P lines from all reads at once; the phase stages separate
+ * the reads of the two haplotypes without knowing a path.  Here each haplotype of each phase set gets a haploid ranking of the P
+ * lines from its own reads.  Integers only; defined on the alignments GAF, the GFA's S and P lines, the rows of
+ * <out>-variants.tsv and ps and flip alone (tests/haplotype_paths_ref.py recomputes it).
+ *   kept reads   the records of the phase store, in store order (vga_phase_read).
+ *   score        s[r][p], a 64-bit sum: bases[r][p] + edges[r][p] of the read's path-support row (source 0, support), or m - e of
+ *                the edit distance, 0 for NONE (source 1, edit: the matrices the likelihood takes from it).
+ *   deficit      d[r][p] = min(max_p' s[r][p'] - s[r][p], cap), one byte (the rule of the likelihood's deficits); cap 1 .. 255.
+ *                Read r is scored when max_p' s[r][p'] > 0; an unscored read has an all-zero row and is in no group.
+ *   sets, tag    as for the set links: the S sets in ascending ps; tag(r, s) the byte of k_hc_tags.
+ *   groups       g = 2 s + h, h: 0 = a, 1 = b: the scored kept reads with tag(r, s) = h.  reads[g] their number; table[g][p] =
+ *                (cost, best): cost = sum d[r][p], best = #{r : d[r][p] = 0}, uint64.  Exact; independent of read order, tile size
+ *                and the store's row pitch.
+ *   rank rule    a group is ranked when reads[g] > 0: its paths by cost ascending, then in P-line order; margin: the cost above
+ *                rank 1; tied: the paths that attain the minimum.
+ *   vga_haplotype_paths_begin  turns the deficit store on: from now on every vga_align_batch keeps a row of n_paths bytes (at a
+ *                              pitch of whole 32-bit words) and a scored byte per kept read, beside the phase store (k_hp_keep, a
+ *                              wave per winner).  After vga_path_support_begin and vga_phase_begin, and vga_path_edit_begin for
+ *                              source 1: VGA_ERR_ARG otherwise, and for cap outside 1 .. 255.  The store grows by doubling
+ *                              (VGA_HAP_PATHS_STORE_ROWS: its first size in rows); VGA_ERR_NOMEM from vga_align_batch, with the
+ *                              reads kept, when it cannot.  vga_phase_begin / _reset empty it; vga_phase_end, vga_pileup_end,
+ *                              vga_path_support_end and a new index drop it.
+ *   vga_haplotype_paths_end    frees it and stops keeping.
+ *   vga_haplotype_paths_store  deficits[n_reads * n_paths] dense and scored[n_reads]; the counts are always written, so a call
+ *                              with NULL arrays sizes the next.
+ *   vga_haplotype_paths        from the context's own stores and the letters of its index.  *n_sets = S is always written (0
+ *                              without a site or with an empty store); with cap_groups < 2 S nothing is launched or written, and
+ *                              the caller asks again.  Per tile of reads k_ph_obs, k_hc_tags and k_hp_sums (a workgroup per set
+ *                              and 256 paths); reads and table stay on the device across the tiles.  VGA_ERR_UNSUPPORTED, with
+ *                              *n_sets, before anything is launched, for more than 4096 sets or 2 S n_paths above 2^23 entries
+ *                              (the table is 134 MB there).  VGA_ERR_ARG for everything vga_phase_tags refuses, and when the
+ *                              store's rows are not the phase store's reads (it was turned on behind kept reads): every reader
+ *                              refuses then.  A refusal leaves reads and table as they were.  Does not reset the stores.
+ *   vga_haplotype_paths_lists  the kernel seam, and the route of several contexts: the same from explicit records, words, dense
+ *                              deficits and scored bytes, with every check of vga_phase_tags_lists (the same code), n_paths
+ *                              1 .. 4096 and scored <= 1.  Needs a context only.
+ *   vga_haplotype_paths_rank   no context, on the host: the one definition of the rank rule (csrc/vga_hap_paths.hpp) on the
+ *                              n_paths entries (cost, best) of one group.  VGA_ERR_ARG for n_paths outside 1 .. 4096 or a NULL.
+ * Without vga_haplotype_paths_begin nothing changes: no k_hp_* launch, no extra allocation. */
+#define VGA_HP_FROM_SUPPORT 0u
+#define VGA_HP_FROM_EDIT 1u
+int vga_haplotype_paths_begin(vga_ctx *ctx, uint32_t cap, uint32_t source);
+int vga_haplotype_paths_end(vga_ctx *ctx);
+int vga_haplotype_paths_store(vga_ctx *ctx, uint8_t *deficits /* n_reads * n_paths */, uint8_t *scored /* n_reads */, uint64_t *n_reads,
+                              uint32_t *n_paths);
+int vga_haplotype_paths(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps,
+                        const uint8_t *flip, uint64_t cap_groups, uint64_t *reads /* cap_groups */,
+                        uint64_t *table /* cap_groups * n_paths * 2 */, uint64_t *n_sets, uint64_t *n_reads);
+int vga_haplotype_paths_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs /* n_reads * 3 */, uint64_t n_words,
+                              const uint32_t *words, uint32_t n_paths, const uint8_t *deficits /* n_reads * n_paths */,
+                              const uint8_t *scored /* n_reads */, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
+                              const uint8_t *ref, const uint32_t *ps, const uint8_t *flip, uint64_t cap_groups, uint64_t *reads,
+                              uint64_t *table, uint64_t *n_sets);
+int vga_haplotype_paths_rank(uint32_t n_paths, const uint64_t *cost_best /* n_paths * 2 */, uint32_t *order /* n_paths */, uint32_t *tied);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "vga_phase_tags", "vga_phase_tags_lists",
     "vga_haplotype_counts", "vga_haplotype_counts_lists", "vga_haplotype_jobs", "vga_haplotype_call",
     "vga_phase_set_links", "vga_phase_set_links_lists", "vga_phase_join",
+    "vga_haplotype_paths_begin", "vga_haplotype_paths_end", "vga_haplotype_paths_store", "vga_haplotype_paths", "vga_haplotype_paths_lists",
+    "vga_haplotype_paths_rank",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -122,6 +124,16 @@ PHASE_JOIN_MAX_SETS = 4096
 PHASE_JOIN_TILE = 32
 PHASE_JOIN_MIN_READS = 2
 PHASE_JOIN_MAX_MIN_READS = 65535
+# the haplotype paths (csrc/vga_hap_paths.hpp): an entry of the table is (cost, best); the cap of a deficit and its default; the
+# paths, sets and table entries of one call at most; the paths of k_hp_sums' workgroup; the matrices a score is summed from
+HAPLOTYPE_PATHS_COLS = 2
+HAPLOTYPE_PATHS_CAP = 64
+HAPLOTYPE_PATHS_MAX_CAP = 255
+HAPLOTYPE_PATHS_MAX_PATHS = 4096
+HAPLOTYPE_PATHS_MAX_SETS = 4096
+HAPLOTYPE_PATHS_MAX_ENTRIES = 1 << 23
+HAPLOTYPE_PATHS_CHUNK = 256
+HAPLOTYPE_PATHS_SOURCES = {"support": 0, "edit": 1}
 
 
 class VgaError(RuntimeError):
@@ -343,6 +355,13 @@ def load_library():
             L.vga_phase_set_links.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u8p, u64, u32p, u64p, u64p]
             L.vga_phase_set_links_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u32p, u64p]
             L.vga_phase_join.argtypes = [u64, u32p, C.c_uint32, u32p, u8p, u32p, u64p, u64p, u64p]
+        if hasattr(L, "vga_haplotype_paths"):  # (the haplotype paths came later than the set links)
+            L.vga_haplotype_paths_begin.argtypes = [vp, C.c_uint32, C.c_uint32]
+            L.vga_haplotype_paths_end.argtypes = [vp]
+            L.vga_haplotype_paths_store.argtypes = [vp, u8p, u8p, u64p, u32p]
+            L.vga_haplotype_paths.argtypes = [vp, u64, u32p, u8p, u8p, u32p, u8p, u64, u64p, u64p, u64p, u64p]
+            L.vga_haplotype_paths_lists.argtypes = [vp, u64, u64, u32p, u64, u32p, C.c_uint32, u8p, u8p, u64, u32p, u8p, u8p, u8p, u32p, u8p, u64, u64p, u64p, u64p]
+            L.vga_haplotype_paths_rank.argtypes = [C.c_uint32, u64p, u32p, u32p]
         for name in ABI_SYMBOLS:
             if name.startswith(("vga_phase_", "vga_haplotype_")) and hasattr(L, name):
                 getattr(L, name).restype = C.c_int
@@ -455,6 +474,19 @@ def phase_join(table, n_sets: int, min_reads: int = PHASE_JOIN_MIN_READS):
     if rc != VGA_OK:
         raise VgaError(rc, "phase_join: min_reads %r is 1 to %d, %d sets at most" % (min_reads, PHASE_JOIN_MAX_MIN_READS, PHASE_JOIN_MAX_SETS))
     return root[:n], flip[:n], joins[:n_joins.value], int(n_agree.value), int(n_conflict.value)
+
+
+def haplotype_paths_rank(cost_best):
+    """vga_haplotype_paths_rank -> (order uint32[n_paths], tied) from the entries cost_best[n_paths, 2] (cost, best) of one group of
+    Context.haplotype_paths: the paths by cost ascending, then in P-line order, and the number that attain the minimum; the library's
+    one definition of the rank rule (csrc/vga_hap_paths.hpp); needs no context and no device"""
+    cb = np.ascontiguousarray(cost_best, dtype=np.uint64).reshape(-1, HAPLOTYPE_PATHS_COLS)
+    n = len(cb)
+    order, tied = np.zeros(max(1, n), dtype=np.uint32), C.c_uint32(0)
+    rc = load_library().vga_haplotype_paths_rank(n, _u64p(cb if n else np.zeros(2, dtype=np.uint64)), _u32p(order), C.byref(tied))
+    if rc != VGA_OK:
+        raise VgaError(rc, "haplotype_paths_rank: %d paths (1 to %d)" % (n, HAPLOTYPE_PATHS_MAX_PATHS))
+    return order[:n], int(tied.value)
 
 
 def haplotype_jobs(cpos, pos, ps):
@@ -1151,6 +1183,76 @@ class Context:
         table, n_sets = self._phase_set_links(lambda sets, fl, cap, table, n_sets: self.L.vga_phase_set_links_lists(
             self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), n, _u32p(at), u8(xs), u8(ys), u8(rf), sets, fl, cap, table, n_sets), n, ps, flip)
         return table, n_sets, len(rc)
+
+    def haplotype_paths_begin(self, cap: int = HAPLOTYPE_PATHS_CAP, source: str = "support") -> None:
+        """vga_haplotype_paths_begin: from now on every align() of this context keeps, beside the phase store, a row of deficit bytes
+        per kept read against every path (needs path_support_begin and phase_begin; source "edit" reads the edit distance and needs
+        path_edit_begin).  cap: 1 .. 255."""
+        if source not in HAPLOTYPE_PATHS_SOURCES:
+            raise VgaError(-1, "haplotype_paths_begin: source %r (support or edit)" % (source,))
+        if not 0 <= int(cap) < 1 << 32:
+            raise VgaError(-1, "haplotype_paths_begin: cap %r" % (cap,))
+        self._check(self.L.vga_haplotype_paths_begin(self.h, int(cap), HAPLOTYPE_PATHS_SOURCES[source]))
+
+    def haplotype_paths_end(self) -> None:
+        """vga_haplotype_paths_end: free the deficit store, stop keeping"""
+        self._check(self.L.vga_haplotype_paths_end(self.h))
+
+    def haplotype_paths_store(self):
+        """vga_haplotype_paths_store -> (deficits uint8[n_reads, n_paths], scored uint8[n_reads]): the rows of the kept reads in the
+        order of phase_reads; does not reset"""
+        n, np_ = C.c_uint64(0), C.c_uint32(0)
+        self._check(self.L.vga_haplotype_paths_store(self.h, None, None, C.byref(n), C.byref(np_)))
+        d, sc = np.zeros((max(1, n.value), max(1, np_.value)), dtype=np.uint8), np.zeros(max(1, n.value), dtype=np.uint8)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        self._check(self.L.vga_haplotype_paths_store(self.h, u8(d), u8(sc), C.byref(n), C.byref(np_)))
+        return d[:n.value], sc[:n.value]
+
+    def _haplotype_paths(self, call, n, ps, flip, n_paths):
+        """`call(ps, flip, cap_groups, reads, table, n_sets)` is one of the two C calls with everything else bound: asked again with
+        room for every group when the first answer names more sets than it had room for (nothing was summed then)"""
+        sets = np.ascontiguousarray(ps, dtype=np.uint32).reshape(-1)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8).reshape(-1)
+        if len(sets) != n or len(fl) != n:
+            raise VgaError(-1, "haplotype paths: %d sites, %d ps and %d flip" % (n, len(sets), len(fl)))
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        cap = 2 * int((sets == np.arange(1, n + 1, dtype=np.uint32)).sum())
+        while True:
+            reads, n_sets = np.zeros(max(1, cap), dtype=np.uint64), C.c_uint64(0)
+            table = np.zeros((max(1, cap), max(1, n_paths), HAPLOTYPE_PATHS_COLS), dtype=np.uint64)
+            self._check(call(_u32p(pad(sets)), pad(fl).ctypes.data_as(_P(C.c_uint8)), cap, _u64p(reads), _u64p(table), C.byref(n_sets)))
+            groups = 2 * int(n_sets.value)
+            if groups <= cap:
+                return reads[:groups], table[:groups], int(n_sets.value)
+            cap = groups
+
+    def haplotype_paths(self, pos, x, y, ps, flip):
+        """vga_haplotype_paths: for every phase set s (ascending ps) and haplotype h the scored kept reads of this context tagged h
+        in s, at the sites pos, x, y of phase_links under the ps and flip of phase_chain -> (reads uint64[2 S], table[2 S, n_paths,
+        2] uint64: (cost, best), group 2 s + h; n_sets; n_reads).  Does not reset."""
+        n, at, (xs, ys) = self._phase_sites(pos, x, y)
+        n_reads = C.c_uint64(0)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        reads, table, n_sets = self._haplotype_paths(lambda sets, fl, cap, reads, table, n_sets: self.L.vga_haplotype_paths(
+            self.h, n, _u32p(at), u8(xs), u8(ys), sets, fl, cap, reads, table, n_sets, C.byref(n_reads)), n, ps, flip, self._n_paths)
+        return reads, table, n_sets, int(n_reads.value)
+
+    def haplotype_paths_lists(self, recs, words, n_bases, deficits, scored, pos, x, y, ref, ps, flip):
+        """vga_haplotype_paths_lists, the kernel seam: the same from explicit records and words (phase_links_lists), dense deficits
+        uint8[n_reads, n_paths] and scored uint8[n_reads] -> (reads, table, n_sets).  Needs a context only."""
+        rc = np.ascontiguousarray(recs, dtype=np.uint32).reshape(-1, 3)
+        wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        df = np.ascontiguousarray(deficits, dtype=np.uint8)
+        sc = np.ascontiguousarray(scored, dtype=np.uint8).reshape(-1)
+        if df.ndim != 2 or len(df) != len(rc) or len(sc) != len(rc):
+            raise VgaError(-1, "haplotype paths: %d reads, deficits of shape %s and %d scored bytes" % (len(rc), df.shape, len(sc)))
+        n_paths = int(df.shape[1])
+        n, at, (xs, ys, rf) = self._phase_sites(pos, x, y, ref)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        pad = lambda a: a if a.size else np.zeros(3, dtype=a.dtype)
+        return self._haplotype_paths(lambda sets, fl, cap, reads, table, n_sets: self.L.vga_haplotype_paths_lists(
+            self.h, int(n_bases), len(rc), _u32p(pad(rc)), len(wd), _u32p(pad(wd)), n_paths, u8(pad(df)), u8(pad(sc)), n, _u32p(at), u8(xs), u8(ys), u8(rf), sets, fl, cap,
+            reads, table, n_sets), n, ps, flip, n_paths)
 
     def path_support_begin(self, step_off, steps) -> int:
         """vga_path_support_begin: step_off[n_paths + 1] into steps, the packed handles (id << 1 | is_reverse) of every path

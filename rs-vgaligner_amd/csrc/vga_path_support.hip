@@ -8,6 +8,8 @@
 #include "vga_genotype.hpp"
 #include "vga_genotype_lik.hpp"
 #include "vga_path_edit.hpp"
+#include "vga_hap_paths.hpp"
+#include "vga_phase.hpp"
 
 #include <algorithm>
 
@@ -248,9 +250,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         const bool gl_from_edit = ps->gl && gl_source(ps->gl.get()) == VGA_GL_FROM_EDIT;
         if (gl_from_edit && !ps->pe)
             return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the likelihood reads the edit distance (vga_genotype_lik_source), which is off (vga_path_edit_begin)");
+        hp_state *hp = hp_active(ctx);  // the deficit store beside the phase store is on: it keeps a row per winner, from the matrices of its source
         if (ps->pe) {  // the edit distance is on: its three kernels over the same winners, on the same stream
             if (!q) return vga_set_error(ctx, VGA_ERR_ARG, "path edit: no queries");
-            const int rc = pe_add_call(ctx, ps, v, ps->d_rows.p, nw, n_reads, *q, gl_from_edit);
+            const int rc = pe_add_call(ctx, ps, v, ps->d_rows.p, nw, n_reads, *q, gl_from_edit || (hp && hp_from_edit(hp)));
             if (rc != VGA_OK) return rc;
         }
         if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
@@ -260,6 +263,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         if (ps->gl) {  // the read likelihood is on: the byte deficits of the two matrices and the cost of every pair, on the same stream
             const int rc = gl_from_edit ? gl_add_call(ctx, ps->gl.get(), n_reads, pe_gl_bases(ps->pe.get()), pe_gl_edges(ps->pe.get()))
                                         : gl_add_call(ctx, ps->gl.get(), n_reads, ps->d_bases.p, ps->d_edges.p);
+            if (rc != VGA_OK) return rc;
+        }
+        if (hp) {  // behind k_ps_score and the edit kernels on the same stream
+            const int rc = hp_keep_winners(ctx, hp, ps, ps->d_rows.p, nw);
             if (rc != VGA_OK) return rc;
         }
     } else if (ps->pe) {  // (no winner: the call's matrix is all NONE)
@@ -277,6 +284,7 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
 // ---------------------------------------------------------------------------------------- C entry points (include/vga_hip.h)
 static void ps_release(vga_ctx *ctx)
 {
+    if (ph_state *ph = ph_active(ctx)) ph_hap_paths(ph).reset();  // (the deficit store holds rows of these paths)
     ctx->index.ps.reset();
     cov_lists_release(ctx, COV_USER_PATHS);
 }

@@ -3,7 +3,8 @@
 // _tags_lists; and what the tagged reads of each haplotype show at the calls: k_hc_tags, k_hc_cols, k_hc_count and vga_haplotype_counts /
 // _counts_lists / _jobs / _call; and which sets the reads tagged in two of them hold together: k_sj_bits, k_sj_pairs and
 // vga_phase_set_links / _set_links_lists / vga_phase_join.  See vga_phase.hpp, vga_hapcall.hpp and vga_phase_join.hpp for the shape.
-// Links, tags, counts and set links run on one ph_frame.
+// Links, tags, counts and set links run on one ph_frame; so do the sums of the haplotype paths (hp_run, vga_haplotype_paths / _lists:
+// k_hp_sums of vga_hap_paths.hip behind k_ph_obs and k_hc_tags; vga_hap_paths.hpp).
 //
 // Meaning (include/vga_hip.h): a stored read observes at a site the base's own letter where a run of matches covers it, the
 // read's letter where a sparse word names a mismatch, D where one names a deleted base, and nothing where it consumes the base
@@ -13,6 +14,7 @@
 #include "vga_phase.hpp"
 #include "vga_hapcall.hpp"
 #include "vga_phase_join.hpp"
+#include "vga_hap_paths.hpp"
 #include "vga_pair_tile.hpp"
 #include "vga_pileup.hpp"
 
@@ -437,6 +439,7 @@ struct ph_state {
     std::vector<ph_rec> recs;
     vga_hbuf<uint32_t> h_dst;
     vga_dbuf<uint32_t> d_dst;
+    vga_owned<hp_state> hp{nullptr, nullptr};  // the deficit rows of the kept reads while the haplotype paths are on
     ~ph_state()
     {
         if (d_words) (void)hipFree(d_words);
@@ -444,6 +447,10 @@ struct ph_state {
 };
 
 ph_state *ph_active(vga_ctx *ctx) { return ctx && ctx->index.loaded && ctx->index.pu ? ctx->index.ph.get() : nullptr; }
+
+uint64_t ph_kept_reads(const ph_state *ph) { return ph->recs.size(); }
+
+vga_owned<hp_state> &ph_hap_paths(ph_state *ph) { return ph->hp; }
 
 int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t nw)
 {
@@ -504,6 +511,7 @@ extern "C" int vga_phase_begin(vga_ctx *ctx)
     ph_state *ph = ctx->index.ph.get();
     ph->n_words = 0;
     ph->recs.clear();
+    if (ph->hp) hp_empty(ph->hp.get());
     if (const char *e = getenv("VGA_PHASE_STORE_WORDS")) ph->first_words = (uint64_t)std::max(1ll, atoll(e));
     return VGA_OK;
 }
@@ -515,6 +523,7 @@ extern "C" int vga_phase_reset(vga_ctx *ctx)
     if (!ph) return vga_set_error(ctx, VGA_ERR_ARG, "vga_phase_reset: the store is off (vga_phase_begin)");
     ph->n_words = 0;
     ph->recs.clear();
+    if (ph->hp) hp_empty(ph->hp.get());
     return VGA_OK;
 }
 
@@ -954,6 +963,56 @@ int sj_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, uint64_t cap_ro
     return f.close();
 }
 
+// The sets of the haplotype paths: somewhere for their number, and for reads and table when they have room; everything ph_check_sets
+// asks of ps and flip; HP_MAX_SETS sets and HP_MAX_ENTRIES table entries at most (refused with the counts, *n_sets written).  Before
+// the frame is made: a refusal uploads and launches nothing.
+int hp_check_sets(vga_ctx *ctx, const char *who, uint64_t n_sites, const uint32_t *ps, const uint8_t *flip, uint32_t n_paths, uint64_t cap_groups,
+                  const uint64_t *reads, const uint64_t *table, uint64_t *n_sets)
+{
+    if (!n_sets || (cap_groups && (!reads || !table))) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null output (n_sets always, reads and table with cap_groups above 0)", who);
+    const int rc = ph_check_sets(ctx, who, n_sites, ps, flip, 0, nullptr, n_sets);
+    if (rc != VGA_OK) return rc;
+    const uint64_t sets = sj_count_sets(n_sites, ps);
+    if (sets > HP_MAX_SETS || 2u * sets * n_paths > HP_MAX_ENTRIES) {
+        *n_sets = sets;
+        if (sets > HP_MAX_SETS) return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu phase sets, %u at most", who, (unsigned long long)sets, HP_MAX_SETS);
+        return vga_set_error(ctx, VGA_ERR_UNSUPPORTED, "%s: %llu phase sets and %u paths are %llu table entries, %llu at most", who, (unsigned long long)sets, n_paths,
+                             (unsigned long long)(2u * sets * n_paths), (unsigned long long)HP_MAX_ENTRIES);
+    }
+    return VGA_OK;
+}
+
+// Per tile of reads k_hc_tags and k_hp_sums (vga_hap_paths.hip) behind k_ph_obs over the frame's reads, whose deficit rows v holds in
+// the frame's order; reads and table stay on the device across the tiles and come back once.  *n_sets = S always (0 without a site
+// or a read); the 2 S groups when cap_groups has room for them, nothing launched otherwise.  Everything was checked by the caller
+// (hp_check_sets, and v.n_rows is the frame's number of reads).
+int hp_run(ph_frame &f, const uint32_t *ps, const uint8_t *flip, const hp_view &v, uint64_t cap_groups, uint64_t *reads, uint64_t *table, uint64_t *n_sets)
+{
+    vga_ctx *ctx = f.ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t sets = f.n_reads ? sj_count_sets(f.s.n, ps) : 0;
+    *n_sets = sets;
+    if (sets == 0 || cap_groups < 2u * sets) return VGA_OK;
+    const uint32_t H = f.H, S = f.group(ps, flip);
+    const size_t group_words = 2 * (size_t)S, table_words = group_words * v.n_paths * HP_COLS;
+    vga_dbuf<unsigned long long> d_out;  // reads, then the table (2 S is even: its entries stay 16-byte aligned)
+    VGA_HIP_CHECK_OOM(ctx, d_out.reserve(group_words + table_words));
+    int rc = f.open(0, S);  // the tile: obs, tags (every tag byte that is counted is written)
+    if (rc != VGA_OK) return rc;
+    uint8_t *d_tags = (uint8_t *)(f.d_tile.p + f.clear_words);
+    VGA_HIP_CHECK(ctx, hipMemsetAsync(d_out.p, 0, (group_words + table_words) * 8, st));
+    rc = f.each_tile([&](uint64_t r0, uint32_t n) {
+        int rc = vga_launch(ctx, "k_hc_tags", (uint64_t)(H + S) * n, k_hc_tags, dim3((n + HC_TAG_BLOCK - 1u) / HC_TAG_BLOCK), dim3(HC_TAG_BLOCK), n, f.T, (const uint8_t *)f.d_tile.p, S,
+                           f.d_sets.p, f.d_sets.p + 2 * (size_t)S + 1u, d_tags);
+        if (rc == VGA_OK) rc = hp_sums_tile(ctx, n, f.T, S, v.n_paths, v.pitch, d_tags, v.d_deficits + r0 * v.pitch, v.d_scored + r0, d_out.p, d_out.p + group_words);
+        return rc;
+    });
+    if (rc != VGA_OK) return rc;
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(reads, d_out.p, group_words * 8, hipMemcpyDeviceToHost, st));
+    VGA_HIP_CHECK(ctx, hipMemcpyAsync(table, d_out.p + group_words, table_words * 8, hipMemcpyDeviceToHost, st));
+    return f.close();
+}
+
 }  // namespace
 
 extern "C" int vga_phase_links(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, uint32_t *links, uint32_t *site_reads,
@@ -1087,6 +1146,58 @@ extern "C" int vga_phase_set_links_lists(vga_ctx *ctx, uint64_t n_bases, uint64_
     ph_frame f(ctx, s);
     const int up = f.from_lists(n_reads, recs, n_words, words);
     return up != VGA_OK ? up : sj_run(f, ps, flip, cap_rows, table, n_sets);
+}
+
+extern "C" int vga_haplotype_paths(vga_ctx *ctx, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y, const uint32_t *ps, const uint8_t *flip,
+                                   uint64_t cap_groups, uint64_t *reads, uint64_t *table, uint64_t *n_sets, uint64_t *n_reads)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const ph_sites s = {n_sites, pos, x, y, nullptr};
+    int rc = ph_check_store(ctx, "vga_haplotype_paths", s, true);
+    if (rc != VGA_OK) return rc;
+    const hp_state *hp = hp_active(ctx);
+    if (!hp) return vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_paths: the deficit store is off (vga_haplotype_paths_begin)");
+    const hp_view v = hp_view_of(hp);
+    if (v.n_rows != ph_kept_reads(ph_active(ctx)))
+        return vga_set_error(ctx, VGA_ERR_ARG, "vga_haplotype_paths: the deficit store holds %llu rows and the phase store %llu reads: it was turned on behind kept reads",
+                             (unsigned long long)v.n_rows, (unsigned long long)ph_kept_reads(ph_active(ctx)));
+    rc = hp_check_sets(ctx, "vga_haplotype_paths", n_sites, ps, flip, v.n_paths, cap_groups, reads, table, n_sets);
+    if (rc != VGA_OK) return rc;
+    ph_frame f(ctx, s);
+    f.from_store(n_reads);
+    return hp_run(f, ps, flip, v, cap_groups, reads, table, n_sets);
+}
+
+extern "C" int vga_haplotype_paths_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, const uint32_t *recs, uint64_t n_words, const uint32_t *words, uint32_t n_paths,
+                                         const uint8_t *deficits, const uint8_t *scored, uint64_t n_sites, const uint32_t *pos, const uint8_t *x, const uint8_t *y,
+                                         const uint8_t *ref, const uint32_t *ps, const uint8_t *flip, uint64_t cap_groups, uint64_t *reads, uint64_t *table,
+                                         uint64_t *n_sets)
+{
+    if (!ctx) return VGA_ERR_ARG;
+    const char *who = "vga_haplotype_paths_lists";
+    const ph_sites s = {n_sites, pos, x, y, ref};
+    int rc = ph_check_lists(ctx, who, n_bases, n_reads, recs, n_words, words, s, true);
+    if (rc != VGA_OK) return rc;
+    if (n_paths < 1u || n_paths > HP_MAX_PATHS) return vga_set_error(ctx, VGA_ERR_ARG, "%s: %u paths (1 .. %u)", who, n_paths, HP_MAX_PATHS);
+    if (n_reads && (!deficits || !scored)) return vga_set_error(ctx, VGA_ERR_ARG, "%s: null array with %llu reads", who, (unsigned long long)n_reads);
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (scored[r] > 1u) return vga_set_error(ctx, VGA_ERR_ARG, "%s: read %llu has scored %u (0 or 1)", who, (unsigned long long)r, scored[r]);
+    rc = hp_check_sets(ctx, who, n_sites, ps, flip, n_paths, cap_groups, reads, table, n_sets);
+    if (rc != VGA_OK) return rc;
+    ph_frame f(ctx, s);
+    const int up = f.from_lists(n_reads, recs, n_words, words);
+    if (up != VGA_OK) return up;
+    // the rows at the store's pitch, the bytes behind the last path zero
+    const uint32_t pitch = hp_pitch(n_paths);
+    vga_dbuf<uint8_t> d_rows;  // deficits, then scored
+    VGA_HIP_CHECK_OOM(ctx, d_rows.reserve((size_t)n_reads * pitch + n_reads + 4));
+    if (n_reads) {
+        VGA_HIP_CHECK(ctx, hipMemsetAsync(d_rows.p, 0, (size_t)n_reads * pitch, ctx->stream));
+        VGA_HIP_CHECK(ctx, hipMemcpy2DAsync(d_rows.p, pitch, deficits, n_paths, n_paths, n_reads, hipMemcpyHostToDevice, ctx->stream));
+        VGA_HIP_CHECK(ctx, hipMemcpyAsync(d_rows.p + (size_t)n_reads * pitch, scored, n_reads, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const hp_view v = {n_reads, n_paths, pitch, d_rows.p, d_rows.p + (size_t)n_reads * pitch};
+    return hp_run(f, ps, flip, v, cap_groups, reads, table, n_sets);
 }
 
 extern "C" int vga_phase_join(uint64_t n_sets, const uint32_t *table, uint32_t min_reads, uint32_t *set_root, uint8_t *set_flip, uint32_t *joins, uint64_t *n_joins,

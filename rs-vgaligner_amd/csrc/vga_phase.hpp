@@ -100,4 +100,10 @@ ph_state *ph_active(vga_ctx *ctx);
 // k_ph_keep: the lists of the nw winners that the pileup's add step (pu_add) has just staged (lists.d_win / h_win, the device lists and the
 // host-built ones) join the store, on the context's stream; not waited for.  VGA_ERR_NOMEM when the store cannot grow.
 int ph_keep_winners(vga_ctx *ctx, ph_state *ph, const oplist_call &lists, size_t nw);
+// the reads the store holds
+uint64_t ph_kept_reads(const ph_state *ph);
+// The deficit store of the haplotype paths (vga_hap_paths.hpp) belongs to the phase store: a row per kept read, emptied and released
+// with it.  Empty until vga_haplotype_paths_begin makes it.
+struct hp_state;
+vga_owned<hp_state> &ph_hap_paths(ph_state *ph);
 #endif

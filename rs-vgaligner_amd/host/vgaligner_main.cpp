@@ -80,7 +80,13 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: the phase sets of --phase joined by the reads that are tagged in two of them,
                           // counted on the GPU (three TSV files; --haplotag and --haplotype-calls then work on the joined sets);
                           // --phase-join-min-reads N: the reads by which cis and trans must differ for a link (2, 1..65535)
-                          {"", "--phase-join", false, "phase-join"}, {"", "--phase-join-min-reads", true, "phase-join-min-reads"}};
+                          {"", "--phase-join", false, "phase-join"}, {"", "--phase-join-min-reads", true, "phase-join-min-reads"},
+                          // --haplotype-paths (with --phase): a haploid ranking of the P lines of --graph for each haplotype of
+                          // each phase set, from that haplotype's own reads, summed on the GPU (<out>-haplotype-paths.tsv);
+                          // --haplotype-paths-cap C: the largest deficit told apart (64, 1..255); --haplotype-paths-top N: the
+                          // paths written per group (5, 0 for all); --haplotype-paths-from support|edit: the matrices scored
+                          {"", "--haplotype-paths", false, "haplotype-paths"}, {"", "--haplotype-paths-cap", true, "haplotype-paths-cap"},
+                          {"", "--haplotype-paths-top", true, "haplotype-paths-top"}, {"", "--haplotype-paths-from", true, "haplotype-paths-from"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -246,6 +252,27 @@ int map_main(int argc, char **argv)
         if (!o.phase_join) throw Error("--phase-join-min-reads has no meaning without --phase-join");
         o.phase_join_min_reads = (uint32_t)std::stoul(v);
     }
+    o.haplotype_paths = m.count("haplotype-paths") > 0;
+    if (o.haplotype_paths && !o.phase) throw Error("--haplotype-paths types the haplotypes of the phase sets of --phase: it needs --phase");
+    for (const char *key : {"haplotype-paths-cap", "haplotype-paths-top", "haplotype-paths-from"})
+        if (m.count(key) && !o.haplotype_paths) throw Error(std::string("--") + key + " has no meaning without --haplotype-paths");
+    if (m.count("haplotype-paths-cap")) {
+        const std::string v = m["haplotype-paths-cap"];
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoul(v) < 1 || std::stoul(v) > 255)
+            throw Error("--haplotype-paths-cap takes a number from 1 to 255: not " + v);
+        o.haplotype_paths_cap = (uint32_t)std::stoul(v);
+    }
+    if (m.count("haplotype-paths-top")) {
+        const std::string v = m["haplotype-paths-top"];
+        if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos)
+            throw Error("--haplotype-paths-top takes a number of paths, 0 for all: not " + v);
+        o.haplotype_paths_top = std::stoull(v);
+    }
+    if (m.count("haplotype-paths-from")) {
+        const std::string v = m["haplotype-paths-from"];
+        if (v != "edit" && v != "support") throw Error("--haplotype-paths-from takes edit or support: not " + v);
+        o.haplotype_paths_from_edit = v == "edit";
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -267,14 +294,14 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    // --path-support, --genotype, --genotype-likelihood, --path-edit: the P lines of --graph, and the graph checked against the index,
+    // --path-support, --genotype, --genotype-likelihood, --path-edit, --haplotype-paths: the P lines of --graph, and the graph checked against the index,
     // before any device is opened
     std::unique_ptr<HashGraph> graph;
     const bool scoring = scoring_on(o);
     if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);
-        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : o.genotype_likelihood ? "--genotype-likelihood: " : "--path-edit: ") + m["graph"] + " has no P line");
+        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : o.genotype_likelihood ? "--genotype-likelihood: " : o.path_edit ? "--path-edit: " : "--haplotype-paths: ") + m["graph"] + " has no P line");
     } else
         prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
@@ -331,6 +358,11 @@ int map_main(int argc, char **argv)
         fprintf(stderr, "[vgaligner] phase-join: %llu sets, %llu joins, %llu sets left, %llu agreeing, %llu conflicting links\n", (unsigned long long)out.n_join_sets,
                 (unsigned long long)out.n_joins, (unsigned long long)(out.n_join_sets - out.n_joins), (unsigned long long)out.n_join_agree,
                 (unsigned long long)out.n_join_conflict);
+    if (o.haplotype_paths) {
+        fprintf(stderr, "[vgaligner] haplotype-paths: %llu sets, %llu groups with reads, %llu of %llu kept reads scored\n", (unsigned long long)out.n_hap_path_sets,
+                (unsigned long long)out.n_hap_path_groups, (unsigned long long)out.n_hap_path_scored, (unsigned long long)out.n_hap_path_kept);
+        fprintf(stderr, "[vgaligner] haplotype-paths: %s\n", out.n_hap_path_groups ? out.hap_path_call.c_str() : "no call");
+    }
     if (o.haplotag)
         fprintf(stderr, "[vgaligner] haplotag: %llu rows of %llu reads: %llu a, %llu b, %llu undecided\n", (unsigned long long)out.n_haplotag_rows,
                 (unsigned long long)out.n_phase_reads, (unsigned long long)out.n_haplotag_a, (unsigned long long)out.n_haplotag_b,
@@ -386,7 +418,9 @@ int main(int argc, char **argv)
                         "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
                         "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n"
                         "                                 (with --haplotag: [--haplotype-calls])\n"
-                        "                                 (with --phase: [--phase-join [--phase-join-min-reads 2]])\n");
+                        "                                 (with --phase: [--phase-join [--phase-join-min-reads 2]])\n"
+                        "                                 (with --phase: [--haplotype-paths [--haplotype-paths-cap 64] [--haplotype-paths-top 5]\n"
+                        "                                                 [--haplotype-paths-from support|edit]])\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

@@ -226,6 +226,15 @@ struct MapOptions {
     // <out>-phase-joins.tsv; haplotag and haplotype_calls then work on the joined sets.  <out>-phase.tsv stays the chain's.
     bool phase_join = false;
     uint32_t phase_join_min_reads = 2;
+    // --haplotype-paths (not in the reference; needs phase and the P lines of --graph): keep a row of path deficits per kept read
+    // beside the phase store (vga_haplotype_paths_begin: haplotype_paths_cap 1 .. 255, from the edit distance under
+    // haplotype_paths_from_edit), sum the rows by (phase set, haplotype) on the GPU (vga_haplotype_paths; several contexts:
+    // vga_haplotype_paths_lists on the first, from the concatenated stores), rank the paths of every group by the rule of
+    // vga_hap_paths.hpp and write the best haplotype_paths_top (0: all) to <out>-haplotype-paths.tsv.  Turns path support on, not
+    // its files; works on the joined sets under phase_join.
+    bool haplotype_paths = false, haplotype_paths_from_edit = false;
+    uint32_t haplotype_paths_cap = 64;
+    uint64_t haplotype_paths_top = 5;
     PathTable paths;
 };
 // the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
@@ -244,6 +253,9 @@ struct MapOutput {
     uint64_t n_variant_tested = 0, n_variant_calls = 0;  // bases tested and bases reported (MapOptions::call_variants)
     uint64_t n_phase_sites = 0, n_phase_sets = 0, n_phase_reads = 0;  // heterozygous sites, phase sets and reads kept (MapOptions::phase)
     uint64_t n_haplotag_rows = 0, n_haplotag_a = 0, n_haplotag_b = 0, n_haplotag_tied = 0;  // rows and their haplotypes (MapOptions::haplotag)
+    // the sets, the groups with reads, the scored and the kept reads, and the call of the largest set (MapOptions::haplotype_paths)
+    uint64_t n_hap_path_sets = 0, n_hap_path_groups = 0, n_hap_path_scored = 0, n_hap_path_kept = 0;
+    std::string hap_path_call;
     uint64_t n_join_sets = 0, n_joins = 0, n_join_agree = 0, n_join_conflict = 0;  // chain sets, accepted links, links inside a component (MapOptions::phase_join)
     uint64_t n_hapcall_jobs = 0, n_hapcall_rows = 0, n_hapcall_differ = 0;  // jobs, lines written, lines whose two decided calls differ (MapOptions::haplotype_calls)
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)

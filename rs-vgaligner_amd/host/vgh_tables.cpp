@@ -6,6 +6,7 @@
 #include "../csrc/vga_phase.hpp"
 #include "../csrc/vga_hapcall.hpp"
 #include "../csrc/vga_phase_join.hpp"
+#include "../csrc/vga_hap_paths.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -55,7 +56,7 @@ void PhaseLinks::chain(uint32_t min_links)
     ph_chain(n, links.data(), min_links, ps.data(), flip.data(), link_d.data());
 }
 
-bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit; }
+bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit || opt.haplotype_paths; }
 
 namespace {
 
@@ -135,6 +136,21 @@ void join_fetch(vga_ctx *ctx, PhaseJoin &j, const PhaseLinks &p, uint32_t min_re
     pj_join(S, j.table.data(), min_reads, j.set_root.data(), j.set_flip.data(), j.joins.data(), &j.n_joins, &j.n_agree, &j.n_conflict);
     j.ps.assign(n + 1, 0); j.flip.assign(n + 1, 0);
     pj_sites(n, p.ps.data(), p.flip.data(), j.set_root.data(), j.set_flip.data(), j.ps.data(), j.flip.data());
+}
+
+// `call(cap_groups, reads, table, &n_sets)` is one of the two library calls with everything before cap_groups bound, asked with room
+// for the groups of the sets of ps (more than HP_MAX_SETS, or a table of more than HP_MAX_ENTRIES: refused with the counts)
+template <typename F>
+void hap_paths_fetch(vga_ctx *ctx, HapPaths &h, const std::vector<uint32_t> &ps, size_t n_sites, size_t n_paths, F call)
+{
+    uint64_t S = 0;
+    for (size_t s = 0; s < n_sites; s++) S += ps[s] == s + 1u ? 1u : 0u;
+    h.reads.assign(2 * S + 2, 0);  // (an empty store leaves them so)
+    h.table.assign(std::min<uint64_t>(2 * S * n_paths, HP_MAX_ENTRIES) * HP_COLS + HP_COLS, 0);
+    uint64_t summed = 0;
+    check(ctx, call(2 * S, h.reads.data(), h.table.data(), &summed));
+    if (summed != S && summed != 0) throw Error("--haplotype-paths: there are " + std::to_string(S) + " sets, and " + std::to_string(summed) + " were summed");
+    h.n_sets = S;
 }
 
 // ---- the writers.  Each gets its table padded to the sizes it indexes.
@@ -283,6 +299,51 @@ void phase_join_write(const Index &ix, const PhaseLinks &p, const PhaseJoin &j, 
         t += l[3] > l[2] ? "trans" : "cis"; t += '\n';
     }
     write_file(out_prefix + "-phase-joins.tsv", t);
+}
+
+// One block per ranked group (reads above 0) in (ps, a before b) order: the best `top` paths (0: all) by the rank rule of
+// vga_hap_paths.hpp (hp_rank), each with its cost, its cost above rank 1, the reads it fits best and the paths tied at the minimum.
+// The call of the set with the most scored tagged reads (the smallest ps on a tie) goes to `out`.
+void haplotype_paths_write(const MapOptions &opt, const std::vector<uint32_t> &ps, size_t n_sites, const HapPaths &h, uint64_t n_kept, MapOutput &out,
+                           const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    const uint64_t S = h.n_sets;
+    std::vector<uint32_t> set_ps, order(np + 1);
+    for (size_t s = 0; s < n_sites; s++)
+        if (ps[s] == s + 1u) set_ps.push_back((uint32_t)(s + 1u));
+    std::string t = "ps\thap\treads\trank\tpath\tcost\tmargin\tbest\ttied\n";
+    out.n_hap_path_sets = S; out.n_hap_path_groups = 0; out.n_hap_path_scored = h.n_scored; out.n_hap_path_kept = n_kept;
+    uint64_t largest = 0, largest_reads = 0;
+    for (uint64_t s = 0; s < S; s++)
+        if (h.reads[2 * s] + h.reads[2 * s + 1] > largest_reads) { largest = s; largest_reads = h.reads[2 * s] + h.reads[2 * s + 1]; }
+    std::string name[2] = {".", "."};
+    uint64_t margin[2] = {0, 0}, tied_of[2] = {0, 0};
+    for (uint64_t g = 0; g < 2 * S; g++) {
+        if (h.reads[g] == 0) continue;
+        out.n_hap_path_groups++;
+        const uint64_t *e = h.table.data() + g * np * HP_COLS;
+        const uint32_t tied = hp_rank((uint32_t)np, e, order.data());
+        const size_t rows = opt.haplotype_paths_top ? std::min<size_t>(opt.haplotype_paths_top, np) : np;
+        for (size_t k = 0; k < rows; k++) {
+            const uint64_t *c = e + (uint64_t)order[k] * HP_COLS;
+            put_u64(t, set_ps[g / 2]); t += '\t'; t += g & 1u ? 'b' : 'a'; t += '\t'; put_u64(t, h.reads[g]); t += '\t'; put_u64(t, k + 1); t += '\t';
+            t += opt.paths.names[order[k]]; t += '\t'; put_u64(t, c[0]); t += '\t'; put_u64(t, c[0] - e[(uint64_t)order[0] * HP_COLS]); t += '\t'; put_u64(t, c[1]);
+            t += '\t'; put_u64(t, tied); t += '\n';
+        }
+        if (g / 2 == largest) {
+            name[g & 1u] = opt.paths.names[order[0]];
+            margin[g & 1u] = np > 1 ? e[(uint64_t)order[1] * HP_COLS] - e[(uint64_t)order[0] * HP_COLS] : 0;
+            tied_of[g & 1u] = tied;
+        }
+    }
+    if (out.n_hap_path_groups) {
+        std::string &c = out.hap_path_call;
+        c = "ps "; put_u64(c, set_ps[largest]); c += ": " + name[0] + " | " + name[1] + " (reads "; put_u64(c, h.reads[2 * largest]); c += " | ";
+        put_u64(c, h.reads[2 * largest + 1]); c += ", margins "; put_u64(c, margin[0]); c += " | "; put_u64(c, margin[1]); c += ", tied "; put_u64(c, tied_of[0]);
+        c += " | "; put_u64(c, tied_of[1]); c += ")";
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-haplotype-paths.tsv", t);
 }
 
 // one line per (kept read, phase set) in which a site votes: the read as the input file numbers it, the set as <out>-phase.tsv
@@ -456,6 +517,10 @@ void check_aligner(const MapOptions &opt)
     if (opt.haplotype_calls && !opt.haplotag) throw Error("--haplotype-calls counts what the reads tagged by --haplotag show: it needs --haplotag");
     if (opt.phase_join && !opt.phase) throw Error("--phase-join joins the phase sets of --phase: it needs --phase");
     if (opt.phase_join && (opt.phase_join_min_reads < 1 || opt.phase_join_min_reads > PJ_MIN_READS_MAX)) throw Error("--phase-join-min-reads is 1 to 65535");
+    if (opt.haplotype_paths && !opt.phase) throw Error("--haplotype-paths types the haplotypes of the phase sets of --phase: it needs --phase");
+    if (opt.haplotype_paths && opt.paths.n_paths() == 0) throw Error("--haplotype-paths: the graph has no P line");
+    if (opt.haplotype_paths && (opt.haplotype_paths_cap < 1 || opt.haplotype_paths_cap > HP_CAP_MAX)) throw Error("--haplotype-paths-cap is 1 to 255");
+    if (opt.haplotype_paths_from_edit && !opt.haplotype_paths) throw Error("--haplotype-paths-from has no meaning without --haplotype-paths");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -478,6 +543,7 @@ void Tables::begin(vga_ctx *ctx) const
     if (piling()) check(ctx, vga_pileup_begin(ctx));
     if (inserting()) check(ctx, vga_insertion_begin(ctx));
     if (phasing()) check(ctx, vga_phase_begin(ctx));
+    if (hap_typing()) check(ctx, vga_haplotype_paths_begin(ctx, opt_.haplotype_paths_cap, opt_.haplotype_paths_from_edit ? VGA_HP_FROM_EDIT : VGA_HP_FROM_SUPPORT));
 }
 
 void Tables::chunk_rows(vga_ctx *ctx, uint64_t b0, uint64_t n, const uint8_t *aligned, ReadRows &rows, const std::function<void(const char *)> &mark)
@@ -573,7 +639,7 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         phase_sites();
         PhaseLinks &p = phase_;
         check(ctx, vga_phase_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.links.data(), p.site_reads.data(), &p.n_reads));
-        if (tagging() || joining()) p.chain(opt_.phase_min_links);
+        if (tagging() || joining() || hap_typing()) p.chain(opt_.phase_min_links);
         if (joining())  // the sets of the chain just made; what follows works on the joined ones
             join_fetch(ctx, join_, p, opt_.phase_join_min_reads, [&](uint64_t cap_rows, uint32_t *table, uint64_t *n_sets) {
                 return vga_phase_set_links(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), p.ps.data(), p.flip.data(), cap_rows, table, n_sets, nullptr);
@@ -587,6 +653,19 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
                 return vga_haplotype_counts(ctx, variants_.n_calls, variants_.pos.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), sets_ps().data(),
                                             sets_flip().data(), cap, rows, n_rows, nullptr);
             });
+        if (hap_typing()) {  // the rows beside the store just linked, under the sets just made
+            HapPaths &h = hap_paths_;
+            uint64_t n_rows = 0;
+            check(ctx, vga_haplotype_paths_store(ctx, nullptr, nullptr, &n_rows, nullptr));
+            h.scored.assign(n_rows + 1, 0);
+            check(ctx, vga_haplotype_paths_store(ctx, nullptr, h.scored.data(), &n_rows, nullptr));
+            h.n_scored = 0;
+            for (uint64_t r = 0; r < n_rows; r++) h.n_scored += h.scored[r];
+            hap_paths_fetch(ctx, h, sets_ps(), p.pos.size(), np, [&](uint64_t cap_groups, uint64_t *reads, uint64_t *table, uint64_t *n_sets) {
+                return vga_haplotype_paths(ctx, p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), sets_ps().data(), sets_flip().data(), cap_groups, reads, table, n_sets,
+                                           nullptr);
+            });
+        }
     } else if (phasing()) {  // the whole store: the context may be gone before the summed call
         PhaseStore s;
         uint64_t n_reads = 0, n_words = 0;
@@ -598,6 +677,18 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
             throw Error("--haplotag: the phase store of slot " + std::to_string(slot) + " holds " + std::to_string(n_reads) + " reads, and " +
                         std::to_string(tags_.read_ids.size()) + " reads were noted as kept");
         phase_store_.add(s);
+        if (hap_typing()) {  // the deficit rows beside it, in the same order
+            uint64_t n_rows = 0;
+            uint32_t paths = 0;
+            check(ctx, vga_haplotype_paths_store(ctx, nullptr, nullptr, &n_rows, &paths));
+            if (n_rows != n_reads || paths != np)
+                throw Error("--haplotype-paths: the deficit store of slot " + std::to_string(slot) + " holds " + std::to_string(n_rows) + " rows of " + std::to_string(paths) +
+                            " paths, and its phase store " + std::to_string(n_reads) + " reads");
+            std::vector<uint8_t> d(n_rows * np + 1), sc(n_rows + 1);
+            check(ctx, vga_haplotype_paths_store(ctx, d.data(), sc.data(), &n_rows, &paths));
+            hap_paths_.deficits.insert(hap_paths_.deficits.end(), d.begin(), d.begin() + (long)(n_rows * np));
+            hap_paths_.scored.insert(hap_paths_.scored.end(), sc.begin(), sc.begin() + (long)n_rows);
+        }
     }
     if (piling() && getenv("VGA_TRACE"))
         fprintf(stderr, "[vgh-trace] slot %u: pileup table read in %.3f ms, variants called in %.3f ms\n", slot,
@@ -609,6 +700,7 @@ void Tables::end(vga_ctx *ctx) const
 {
     if (coverage()) (void)vga_coverage_end(ctx);
     if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
+    if (hap_typing()) (void)vga_haplotype_paths_end(ctx);
     if (phasing()) (void)vga_phase_end(ctx);
     if (piling()) (void)vga_pileup_end(ctx);
     if (inserting()) (void)vga_insertion_end(ctx);
@@ -624,6 +716,8 @@ void Tables::add(const Tables &o)
     pileup_.add(o.pileup_);
     insertions_.add(o.insertions_);
     phase_store_.add(o.phase_store_);
+    hap_paths_.deficits.insert(hap_paths_.deficits.end(), o.hap_paths_.deficits.begin(), o.hap_paths_.deficits.end());  // (in the order of the records)
+    hap_paths_.scored.insert(hap_paths_.scored.end(), o.hap_paths_.scored.begin(), o.hap_paths_.scored.end());
     tags_.read_ids.insert(tags_.read_ids.end(), o.tags_.read_ids.begin(), o.tags_.read_ids.end());  // (in the order of the records)
 }
 
@@ -671,7 +765,7 @@ void Tables::call(vga_ctx *ctx)
         check(ctx, vga_phase_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
                                          p.y.data(), ref.data(), p.links.data(), p.site_reads.data()));
         trace_mark("phase links counted");
-        if (tagging() || joining()) p.chain(opt_.phase_min_links);
+        if (tagging() || joining() || hap_typing()) p.chain(opt_.phase_min_links);
         if (joining()) {
             join_fetch(ctx, join_, p, opt_.phase_join_min_reads, [&](uint64_t cap_rows, uint32_t *table, uint64_t *n_sets) {
                 return vga_phase_set_links_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), p.pos.size(), p.pos.data(), p.x.data(),
@@ -695,6 +789,21 @@ void Tables::call(vga_ctx *ctx)
                                                   sets_flip().data(), cap, rows, n_rows);
             });
             trace_mark("haplotypes counted");
+        }
+        if (hap_typing()) {
+            HapPaths &h = hap_paths_;
+            const size_t np = opt_.paths.n_paths();
+            if (h.scored.size() != p.n_reads || h.deficits.size() != p.n_reads * np)
+                throw Error("--haplotype-paths: the contexts kept " + std::to_string(p.n_reads) + " reads and " + std::to_string(h.scored.size()) + " deficit rows");
+            h.n_scored = 0;
+            for (uint8_t v : h.scored) h.n_scored += v;
+            h.deficits.push_back(0); h.scored.push_back(0);  // (never a null array)
+            hap_paths_fetch(ctx, h, sets_ps(), p.pos.size(), np, [&](uint64_t cap_groups, uint64_t *reads, uint64_t *table, uint64_t *n_sets) {
+                return vga_haplotype_paths_lists(ctx, ix_.seq_length, p.n_reads, s.recs.data(), s.words.size(), s.words.data(), (uint32_t)np, h.deficits.data(),
+                                                 h.scored.data(), p.pos.size(), p.pos.data(), p.x.data(), p.y.data(), ref.data(), sets_ps().data(), sets_flip().data(),
+                                                 cap_groups, reads, table, n_sets);
+            });
+            trace_mark("haplotype paths summed");
         }
     }
     if (!inserting()) return;
@@ -763,6 +872,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
         if (hap_calling()) {
             haplotype_calls_write(ix_, variants_, hap_counts_, out, out_prefix);
             trace_mark("haplotype calls written");
+        }
+        if (hap_typing()) {
+            haplotype_paths_write(opt_, sets_ps(), phase_.pos.size(), hap_paths_, phase_.n_reads, out, out_prefix);
+            trace_mark("haplotype paths written");
         }
     }
     if (inserting()) {

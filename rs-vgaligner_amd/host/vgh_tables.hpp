@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join, --haplotype-paths): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -85,6 +85,16 @@ struct PhaseJoin {
     std::vector<uint8_t> flip;
 };
 
+// The haplotype paths (MapOptions::haplotype_paths): the deficit rows of the kept reads, dense, and their scored bytes, in store
+// order (kept whole only for the route of several contexts; the scored reads are counted either way); per group 2 s + h the reads
+// and per (group, path) the entry (cost, best)
+struct HapPaths {
+    std::vector<uint8_t> deficits, scored;
+    uint64_t n_scored = 0;
+    std::vector<uint64_t> reads, table;
+    uint64_t n_sets = 0;
+};
+
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
 struct ReadRows {
     std::string path, edit;
@@ -103,13 +113,14 @@ public:
     // likelihood from the edit distance turns that on; --call-variants turns the counting of the pileup on, not its file.
     bool coverage() const { return opt_.coverage || opt_.coverage_only; }
     bool scoring() const { return scoring_on(opt_); }
-    bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit); }
+    bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit) || (opt_.haplotype_paths && opt_.haplotype_paths_from_edit); }
     bool piling() const { return opt_.pileup || opt_.call_variants; }
     bool inserting() const { return opt_.call_insertions; }
     bool phasing() const { return opt_.phase; }
     bool tagging() const { return opt_.haplotag; }
     bool hap_calling() const { return opt_.haplotype_calls; }
     bool joining() const { return opt_.phase_join; }
+    bool hap_typing() const { return opt_.haplotype_paths; }
     bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
     // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
     bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
@@ -150,6 +161,7 @@ private:
     PhaseTags tags_;  // (read_ids: of this context's store, then of the concatenated stores)
     HaplotypeCounts hap_counts_;
     PhaseJoin join_;
+    HapPaths hap_paths_;
     // the sets the tags and the haplotype counts work on: the joined ones under --phase-join, else the chain's
     const std::vector<uint32_t> &sets_ps() const { return joining() ? join_.ps : phase_.ps; }
     const std::vector<uint8_t> &sets_flip() const { return joining() ? join_.flip : phase_.flip; }
