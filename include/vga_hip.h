@@ -855,6 +855,59 @@ int vga_haplotype_paths_lists(vga_ctx *ctx, uint64_t n_bases, uint64_t n_reads, 
                               uint64_t *table, uint64_t *n_sets);
 int vga_haplotype_paths_rank(uint32_t n_paths, const uint64_t *cost_best /* n_paths * 2 */, uint32_t *order /* n_paths */, uint32_t *tied);
 
+/* ---- path abundance: the share of the reads that each P line explains, by expectation-maximisation ----------
+ * Stands in for nothing in the reference.  The other path stages call a pair of P lines; this one fits a mixture over all paths at
+ * once, which is what a mixed, pooled, contaminated or copy-number-variable sample needs.  Integers only (but for the table W,
+ * which the library evaluates once on the host); defined on the alignments GAF and the GFA's S and P lines alone
+ * (tests/path_abundance_ref.py recomputes it).
+ *   rows      one per reported alignment of every vga_align_batch while the store is on, in the order they are reported:
+ *             d[r][p] = min(max_p' s[r][p'] - s[r][p], cap), a byte, s as for the haplotype paths (source 0: bases + edges of path
+ *             support; source 1: m - e of the edit distance, 0 for NONE); scored[r] = (max_p' s[r][p'] > 0).  Unscored rows take
+ *             no part.  n: the scored rows; n >= 2^23 is VGA_ERR_UNSUPPORTED.
+ *   table     W[d] = max(1, floor(65536 2^(-lambda d / 256) + 0.5)), d = 0 .. cap, forced non-increasing, W[0] = 65536; entries
+ *             past cap repeat W[cap].  lambda 1 .. 4096 in 1/256 bit per unit of deficit, cap 1 .. 255.
+ *   state     theta[p], uint32 in units of 2^-24; floor(2^24 / n_paths) for every path at the start.
+ *   iteration for every scored row term[p] = theta[p] W[d[r][p]], z = sum_p term[p], resp[p] = floor((term[p] << 16) / z);
+ *             S[p] = sum_r resp[p], total = sum_p S[p], theta'[p] = floor((S[p] << 24) / total), diff = max_p |theta'[p] - theta[p]|.
+ *             The estimate stops after the first iteration with diff <= tol (converged) or after iters iterations.  iters
+ *             1 .. 100 000, tol 0 .. 2^24.
+ *   outputs   theta[n_paths]; reads_q16[n_paths], the S of the last iteration (expected reads x 65 536); best[n_paths], the scored
+ *             rows with d = 0 on the path; n_scored, iterations, converged.  Any pointer may be NULL.  With n = 0: all zeros, 0
+ *             iterations, not converged ("no call").  ppm(theta) = (theta * 1 000 000) >> 24.  Exact; independent of row order,
+ *             batch split and row pitch.  A path whose theta reaches 0 stays at 0.
+ *   vga_path_abundance_table  no context: out[0 .. 255] = W.  VGA_ERR_ARG for lambda or cap out of range or a NULL out.  The one
+ *                             definition (csrc/vga_abundance.hpp).
+ *   vga_path_abundance_begin  turns the store on: from now on every vga_align_batch keeps a row of n_paths bytes (at a pitch of
+ *                             whole 32-bit words) and a scored byte per reported alignment (k_ab_keep, a wave per winner).  After
+ *                             vga_path_support_begin, and vga_path_edit_begin for source 1: VGA_ERR_ARG otherwise, and for cap
+ *                             outside 1 .. 255.  The store grows by doubling (VGA_PATH_ABUNDANCE_STORE_ROWS: its first size in
+ *                             rows); VGA_ERR_NOMEM from vga_align_batch, with the reads kept, when it cannot.  A second begin
+ *                             starts over; vga_path_support_end and a new index drop it.
+ *   vga_path_abundance_reset  empties the store, keeps it on (VGA_ERR_ARG without _begin).
+ *   vga_path_abundance_end    frees it and stops keeping (no error when it is off).
+ *   vga_path_abundance_store  deficits[n_rows * n_paths] dense and scored[n_rows].  *n_rows is always written; with cap_rows below
+ *                             it nothing is copied, and the caller asks again.
+ *   vga_path_abundance        the estimate from the context's own store (k_ab_count once, then k_ab_estep and k_ab_mstep per
+ *                             iteration, enqueued 32 iterations at a time; the result does not depend on that number).
+ *                             VGA_ERR_ARG without _begin or for lambda, iters or tol out of range.  Does not reset the store.
+ *   vga_path_abundance_rows   the kernel seam, and the route of several contexts: the same from explicit dense rows.  Needs a
+ *                             context but no index.  Checked before anything is launched: a NULL array with n_rows > 0, n_paths
+ *                             outside 1 .. 4096, lambda, iters or tol out of range, a scored byte above 1 (VGA_ERR_ARG).
+ * vga_last_kernel_times names the launches of the first 32 iterations only.  Without vga_path_abundance_begin nothing changes: no
+ * k_ab_* launch, no extra allocation. */
+#define VGA_AB_FROM_SUPPORT 0u
+#define VGA_AB_FROM_EDIT 1u
+int vga_path_abundance_table(uint32_t lambda, uint32_t cap, uint32_t *out /* 256 */);
+int vga_path_abundance_begin(vga_ctx *ctx, uint32_t cap, uint32_t source);
+int vga_path_abundance_reset(vga_ctx *ctx);
+int vga_path_abundance_end(vga_ctx *ctx);
+int vga_path_abundance_store(vga_ctx *ctx, uint64_t cap_rows, uint8_t *deficits /* cap_rows * n_paths */, uint8_t *scored /* cap_rows */, uint64_t *n_rows);
+int vga_path_abundance(vga_ctx *ctx, uint32_t lambda, uint32_t iters, uint32_t tol, uint32_t *theta /* n_paths */, uint64_t *reads_q16 /* n_paths */,
+                       uint64_t *best /* n_paths */, uint64_t *n_scored, uint32_t *iterations, uint32_t *converged);
+int vga_path_abundance_rows(vga_ctx *ctx, uint64_t n_rows, uint32_t n_paths, const uint8_t *deficits /* n_rows * n_paths */,
+                            const uint8_t *scored /* n_rows */, uint32_t lambda, uint32_t iters, uint32_t tol, uint32_t *theta, uint64_t *reads_q16,
+                            uint64_t *best, uint64_t *n_scored, uint32_t *iterations, uint32_t *converged);
+
 /* Per-kernel timing of the most recent vga_map_batch / vga_poa_batch / vga_align_batch on this ctx:
  * name[i] / total milliseconds / launches, measured with hipEvents on the stream each launch ran on.
  * The POA sub-batches run two at a time on two streams: `ms` sums every launch's own duration (what

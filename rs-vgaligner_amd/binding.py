@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "vga_phase_set_links", "vga_phase_set_links_lists", "vga_phase_join",
     "vga_haplotype_paths_begin", "vga_haplotype_paths_end", "vga_haplotype_paths_store", "vga_haplotype_paths", "vga_haplotype_paths_lists",
     "vga_haplotype_paths_rank",
+    "vga_path_abundance_table", "vga_path_abundance_begin", "vga_path_abundance_reset", "vga_path_abundance_end", "vga_path_abundance_store",
+    "vga_path_abundance", "vga_path_abundance_rows",
 ]
 
 # k_gt_pairs (csrc/vga_genotype.hpp): the paths on a side of a workgroup's tile (GT_TILE), the reads it stages at a time
@@ -134,6 +136,27 @@ HAPLOTYPE_PATHS_MAX_SETS = 4096
 HAPLOTYPE_PATHS_MAX_ENTRIES = 1 << 23
 HAPLOTYPE_PATHS_CHUNK = 256
 HAPLOTYPE_PATHS_SOURCES = {"support": 0, "edit": 1}
+# the path abundance (csrc/vga_abundance.hpp): the defaults and ranges of its parameters (choices, not measurements), the paths and
+# scored rows of one estimate, the fractional bits of theta and of a responsibility, the rows and paths of k_ab_estep's workgroup,
+# the iterations the host enqueues at a time, the matrices a score is summed from
+PATH_ABUNDANCE_LAMBDA = 512
+PATH_ABUNDANCE_MAX_LAMBDA = 4096
+PATH_ABUNDANCE_CAP = 64
+PATH_ABUNDANCE_MAX_CAP = 255
+PATH_ABUNDANCE_ITERS = 1000
+PATH_ABUNDANCE_MAX_ITERS = 100000
+PATH_ABUNDANCE_TOL = 16
+PATH_ABUNDANCE_MAX_TOL = 1 << 24
+PATH_ABUNDANCE_MAX_PATHS = 4096
+PATH_ABUNDANCE_MAX_ROWS = 1 << 23
+PATH_ABUNDANCE_THETA_BITS = 24
+PATH_ABUNDANCE_RESP_BITS = 16
+PATH_ABUNDANCE_GROUP_ROWS = 256
+PATH_ABUNDANCE_MAX_GROUPS = 4096
+PATH_ABUNDANCE_MAX_ROW_FACTOR = 8
+PATH_ABUNDANCE_CHUNK = 1024
+PATH_ABUNDANCE_BLOCK_ITERS = 32
+PATH_ABUNDANCE_SOURCES = {"support": 0, "edit": 1}
 
 
 class VgaError(RuntimeError):
@@ -365,6 +388,19 @@ def load_library():
         for name in ABI_SYMBOLS:
             if name.startswith(("vga_phase_", "vga_haplotype_")) and hasattr(L, name):
                 getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_path_abundance"):  # (absent from an older build named by VGA_LIB; the Context.path_abundance* calls then fail)
+        u64p, u32p, u8p, u64, u32 = _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint8), C.c_uint64, C.c_uint32
+        outs = [u32p, u64p, u64p, u64p, u32p, u32p]
+        L.vga_path_abundance_table.argtypes = [u32, u32, u32p]
+        L.vga_path_abundance_begin.argtypes = [vp, u32, u32]
+        L.vga_path_abundance_reset.argtypes = [vp]
+        L.vga_path_abundance_end.argtypes = [vp]
+        L.vga_path_abundance_store.argtypes = [vp, u64, u8p, u8p, u64p]
+        L.vga_path_abundance.argtypes = [vp, u32, u32, u32] + outs
+        L.vga_path_abundance_rows.argtypes = [vp, u64, u32, u8p, u8p, u32, u32, u32] + outs
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_path_abundance"):
+                getattr(L, name).restype = C.c_int
     _lib = L
     return L
 
@@ -487,6 +523,25 @@ def haplotype_paths_rank(cost_best):
     if rc != VGA_OK:
         raise VgaError(rc, "haplotype_paths_rank: %d paths (1 to %d)" % (n, HAPLOTYPE_PATHS_MAX_PATHS))
     return order[:n], int(tied.value)
+
+
+def path_abundance_table(lam: int = PATH_ABUNDANCE_LAMBDA, cap: int = PATH_ABUNDANCE_CAP) -> np.ndarray:
+    """vga_path_abundance_table -> W, uint32[256]: W[d] = max(1, floor(65536 2^(-lam d / 256) + 0.5)) for d <= cap, non-increasing,
+    the entries past cap repeating W[cap]; the library's one definition (csrc/vga_abundance.hpp); needs no context and no device"""
+    if not (0 <= int(lam) < 1 << 32 and 0 <= int(cap) < 1 << 32):
+        raise VgaError(-1, "path_abundance_table: lam %r, cap %r" % (lam, cap))
+    w = np.zeros(256, dtype=np.uint32)
+    rc = load_library().vga_path_abundance_table(int(lam), int(cap), _u32p(w))
+    if rc != 0:
+        raise VgaError(rc, "path_abundance_table: lam %r is 1 to %d and cap %r 1 to %d" % (lam, PATH_ABUNDANCE_MAX_LAMBDA, cap, PATH_ABUNDANCE_MAX_CAP))
+    return w
+
+
+def path_abundance_ppm(theta):
+    """parts per million of a theta (or an array of them): (theta * 1 000 000) >> 24, as csrc/vga_abundance.hpp defines it"""
+    t = np.asarray(theta, dtype=np.uint64)
+    out = (t * np.uint64(1000000)) >> np.uint64(PATH_ABUNDANCE_THETA_BITS)
+    return int(out) if out.ndim == 0 else out
 
 
 def haplotype_jobs(cpos, pos, ps):
@@ -1396,6 +1451,60 @@ class Context:
         self._check(self.L.vga_genotype_lik_pairs(self.h, n_reads, n_paths, _u32p(b) if b.size else None, _u32p(e) if e.size else None,
                                                   int(lam), int(cap), d.ctypes.data_as(_P(C.c_uint8)), _u64p(c), C.byref(scored)))
         return {"cost": c[:n], "deficit": d[:b.size].reshape(b.shape), "n_scored": int(scored.value), "n_paths": n_paths}
+
+    def path_abundance_begin(self, cap: int = PATH_ABUNDANCE_CAP, source: str = "support") -> None:
+        """vga_path_abundance_begin: from now on every align() of this context keeps a row of deficit bytes per reported alignment
+        against every path (needs path_support_begin; source "edit" reads the edit distance and needs path_edit_begin).  cap: 1 .. 255."""
+        if source not in PATH_ABUNDANCE_SOURCES:
+            raise VgaError(-1, "path_abundance_begin: source %r (support or edit)" % (source,))
+        if not 0 <= int(cap) < 1 << 32:
+            raise VgaError(-1, "path_abundance_begin: cap %r" % (cap,))
+        self._check(self.L.vga_path_abundance_begin(self.h, int(cap), PATH_ABUNDANCE_SOURCES[source]))
+
+    def path_abundance_reset(self) -> None:
+        """vga_path_abundance_reset: empty the store, keep keeping"""
+        self._check(self.L.vga_path_abundance_reset(self.h))
+
+    def path_abundance_end(self) -> None:
+        """vga_path_abundance_end: free the store, stop keeping"""
+        self._check(self.L.vga_path_abundance_end(self.h))
+
+    def path_abundance_store(self):
+        """vga_path_abundance_store -> (deficits uint8[n, n_paths], scored uint8[n]): the rows of the reported alignments in the order
+        they were reported; does not reset"""
+        n = C.c_uint64(0)
+        self._check(self.L.vga_path_abundance_store(self.h, 0, None, None, C.byref(n)))
+        rows = n.value
+        d, sc = np.zeros((max(1, rows), max(1, self._n_paths)), dtype=np.uint8), np.zeros(max(1, rows), dtype=np.uint8)
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8))
+        self._check(self.L.vga_path_abundance_store(self.h, rows, u8(d), u8(sc), C.byref(n)))
+        return d.ravel()[:rows * self._n_paths].reshape(rows, self._n_paths), sc[:rows]
+
+    def _path_abundance(self, call, n_paths, lam, iters, tol, who):
+        if not all(0 <= int(v) < 1 << 32 for v in (lam, iters, tol)):
+            raise VgaError(-1, "%s: lam %r, iters %r, tol %r" % (who, lam, iters, tol))
+        theta = np.zeros(max(1, n_paths), dtype=np.uint32)
+        reads, best = np.zeros(max(1, n_paths), dtype=np.uint64), np.zeros(max(1, n_paths), dtype=np.uint64)
+        n, it, conv = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(call(int(lam), int(iters), int(tol), _u32p(theta), _u64p(reads), _u64p(best), C.byref(n), C.byref(it), C.byref(conv)))
+        return {"theta": theta[:n_paths], "reads_q16": reads[:n_paths], "best": best[:n_paths], "n_scored": int(n.value), "iterations": int(it.value),
+                "converged": bool(conv.value), "n_paths": n_paths}
+
+    def path_abundance(self, lam: int = PATH_ABUNDANCE_LAMBDA, iters: int = PATH_ABUNDANCE_ITERS, tol: int = PATH_ABUNDANCE_TOL) -> dict:
+        """vga_path_abundance: the EM estimate from this context's own store -> {theta: uint32[n_paths] in units of 2^-24, reads_q16:
+        uint64[n_paths] (expected reads x 65 536), best: uint64[n_paths] (scored rows with deficit 0), n_scored, iterations, converged,
+        n_paths}; does not reset the store"""
+        return self._path_abundance(lambda *a: self.L.vga_path_abundance(self.h, *a), self._n_paths, lam, iters, tol, "path_abundance")
+
+    def path_abundance_rows(self, deficits, scored, lam: int = PATH_ABUNDANCE_LAMBDA, iters: int = PATH_ABUNDANCE_ITERS, tol: int = PATH_ABUNDANCE_TOL) -> dict:
+        """vga_path_abundance_rows, the kernel seam: the same from explicit rows, deficits uint8[n_rows, n_paths] and scored
+        uint8[n_rows]; needs no index and touches no store"""
+        d, sc = np.ascontiguousarray(deficits, dtype=np.uint8), np.ascontiguousarray(scored, dtype=np.uint8).reshape(-1)
+        assert d.ndim == 2 and d.shape[0] == len(sc)
+        n_rows, n_paths = d.shape
+        u8 = lambda a: a.ctypes.data_as(_P(C.c_uint8)) if a.size else None
+        return self._path_abundance(lambda *a: self.L.vga_path_abundance_rows(self.h, n_rows, n_paths, u8(d), u8(sc), *a), n_paths, lam, iters, tol,
+                                    "path_abundance_rows")
 
     def path_edit_begin(self) -> None:
         """vga_path_edit_begin: needs path_support_begin; from now on every align() of this context scores the read of every

@@ -15,27 +15,14 @@ static_assert(HP_MAX_PATHS == PS_MAX_PATHS, "the paths of path support");
 
 namespace {
 
-// One wave per winner i: row rows[i] of the call's two matrices, lanes over the paths as in k_gl_deficit (a path past the end is
-// never loaded: 0 is the identity of an unsigned maximum), the maximum reduced over the wave, then the byte row and the scored byte
-// of store row i (the caller passes the store from kept_before on).  The bytes behind the last path are written as zero.
+// One wave per winner i (hp_keep_row, vga_hap_paths.hpp); the caller passes the store from kept_before on.
 __global__ __launch_bounds__(64) void k_hp_keep(uint32_t n, uint32_t n_paths, uint32_t pitch, uint32_t cap, const uint32_t *__restrict__ rows,
                                                  const uint32_t *__restrict__ bases, const uint32_t *__restrict__ edges, uint8_t *__restrict__ deficits,
                                                  uint8_t *__restrict__ scored)
 {
     const uint32_t i = blockIdx.x, lane = threadIdx.x;
     if (i >= n) return;
-    const size_t row = (size_t)rows[i] * n_paths;
-    unsigned long long m = 0;
-    for (uint32_t p = lane; p < n_paths; p += 64u) m = max(m, (unsigned long long)bases[row + p] + edges[row + p]);
-#pragma unroll
-    for (int off = 32; off; off >>= 1) m = max(m, __shfl_xor(m, off));
-    uint8_t *out = deficits + (size_t)i * pitch;
-    for (uint32_t p = lane; p < pitch; p += 64u) {
-        unsigned long long d = 0;
-        if (p < n_paths) d = min(m - ((unsigned long long)bases[row + p] + edges[row + p]), (unsigned long long)cap);
-        out[p] = (uint8_t)d;
-    }
-    if (lane == 0) scored[i] = m != 0 ? 1u : 0u;
+    hp_keep_row(i, lane, n_paths, pitch, cap, rows, bases, edges, deficits, scored);
 }
 
 // the four bytes of a word of a row, added to a lane's counters: the deficit to cost, one to best where it is zero
@@ -144,46 +131,53 @@ void hp_empty(hp_state *hp) { hp->n_rows = 0; }
 
 hp_view hp_view_of(const hp_state *hp) { return hp_view{hp->n_rows, hp->n_paths, hp->pitch, hp->d_deficits, hp->d_scored}; }
 
+int hp_store_grow(vga_ctx *ctx, const char *what, uint8_t *&d_deficits, uint8_t *&d_scored, uint64_t &cap_rows, uint64_t n_rows, uint64_t first_rows,
+                  uint32_t pitch, uint64_t at)
+{
+    if (at <= cap_rows) return VGA_OK;
+    hipStream_t st = ctx->stream;
+    uint64_t cap = cap_rows ? cap_rows : std::max<uint64_t>(first_rows, 1);  // grows by doubling; what is stored moves on the context's stream
+    while (cap < at) cap *= 2;
+    uint8_t *grown = nullptr, *grown_scored = nullptr;
+    {
+        vga_alloc_urgent urgent;
+        if (hipMalloc((void **)&grown, cap * pitch) != hipSuccess || hipMalloc((void **)&grown_scored, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            if (grown) (void)hipFree(grown);
+            return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_align_batch: the %s store cannot grow to %llu rows of %u bytes: %llu reads kept", what,
+                                 (unsigned long long)cap, pitch, (unsigned long long)n_rows);
+        }
+    }
+    hipError_t e = hipSuccess;
+    if (n_rows) {
+        e = hipMemcpyAsync(grown, d_deficits, n_rows * pitch, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(grown_scored, d_scored, n_rows, hipMemcpyDeviceToDevice, st);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(grown);
+        (void)hipFree(grown_scored);
+        return vga_set_error(ctx, VGA_ERR_HIP, "vga_align_batch: moving the %s store: %s", what, hipGetErrorString(e));
+    }
+    if (d_deficits) vga_defer_release(d_deficits, nullptr, nullptr, 0);
+    if (d_scored) vga_defer_release(d_scored, nullptr, nullptr, 0);
+    if (getenv("VGA_TRACE"))
+        fprintf(stderr, "[vga-trace] %s: the store grows from %llu to %llu rows\n", what, (unsigned long long)cap_rows, (unsigned long long)cap);
+    d_deficits = grown;
+    d_scored = grown_scored;
+    cap_rows = cap;
+    return VGA_OK;
+}
+
 int hp_keep_winners(vga_ctx *ctx, hp_state *hp, ps_state *ps, const uint32_t *d_rows, size_t nw)
 {
     if (nw == 0) return VGA_OK;
-    hipStream_t st = ctx->stream;
     if (hp->n_paths != ps->n_paths)
         return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the haplotype paths store was made for %u paths, path support has %u", hp->n_paths, ps->n_paths);
     if (hp_from_edit(hp) && !ps->pe)
         return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the haplotype paths read the edit distance (vga_haplotype_paths_begin), which is off (vga_path_edit_begin)");
     const uint64_t at = hp->n_rows + nw;
-    if (at > hp->cap_rows) {  // grows by doubling; what is stored moves on the context's stream
-        uint64_t cap = hp->cap_rows ? hp->cap_rows : std::max<uint64_t>(hp->first_rows, 1);
-        while (cap < at) cap *= 2;
-        uint8_t *grown = nullptr, *grown_scored = nullptr;
-        {
-            vga_alloc_urgent urgent;
-            if (hipMalloc((void **)&grown, cap * hp->pitch) != hipSuccess || hipMalloc((void **)&grown_scored, cap) != hipSuccess) {
-                (void)hipGetLastError();
-                if (grown) (void)hipFree(grown);
-                return vga_set_error(ctx, VGA_ERR_NOMEM, "vga_align_batch: the haplotype paths store cannot grow to %llu rows of %u bytes: %llu reads kept",
-                                     (unsigned long long)cap, hp->pitch, (unsigned long long)hp->n_rows);
-            }
-        }
-        hipError_t e = hipSuccess;
-        if (hp->n_rows) {
-            e = hipMemcpyAsync(grown, hp->d_deficits, hp->n_rows * hp->pitch, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(grown_scored, hp->d_scored, hp->n_rows, hipMemcpyDeviceToDevice, st);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(grown);
-            (void)hipFree(grown_scored);
-            return vga_set_error(ctx, VGA_ERR_HIP, "vga_align_batch: moving the haplotype paths store: %s", hipGetErrorString(e));
-        }
-        if (hp->d_deficits) vga_defer_release(hp->d_deficits, nullptr, nullptr, 0);
-        if (hp->d_scored) vga_defer_release(hp->d_scored, nullptr, nullptr, 0);
-        if (getenv("VGA_TRACE"))
-            fprintf(stderr, "[vga-trace] haplotype paths: the store grows from %llu to %llu rows\n", (unsigned long long)hp->cap_rows, (unsigned long long)cap);
-        hp->d_deficits = grown;
-        hp->d_scored = grown_scored;
-        hp->cap_rows = cap;
-    }
+    const int grown = hp_store_grow(ctx, "haplotype paths", hp->d_deficits, hp->d_scored, hp->cap_rows, hp->n_rows, hp->first_rows, hp->pitch, at);
+    if (grown != VGA_OK) return grown;
     const bool edit = hp_from_edit(hp);
     const uint32_t *d_bases = edit ? pe_gl_bases(ps->pe.get()) : ps->d_bases.p, *d_edges = edit ? pe_gl_edges(ps->pe.get()) : ps->d_edges.p;
     const int rc = vga_launch(ctx, "k_hp_keep", nw * ((uint64_t)hp->n_paths * 8u + hp->pitch), k_hp_keep, dim3((unsigned)nw), dim3(64), nw, hp->n_paths, hp->pitch, hp->cap,

@@ -90,4 +90,32 @@ hp_view hp_view_of(const hp_state *hp);
 // first read on), added into d_reads (2 S words) and d_table (2 S n_paths entries), which the launch's workgroups own
 int hp_sums_tile(vga_ctx *ctx, uint32_t n, uint32_t tile_reads, uint32_t n_sets, uint32_t n_paths, uint32_t pitch, const uint8_t *d_tags, const uint8_t *d_deficits,
                  const uint8_t *d_scored, unsigned long long *d_reads, unsigned long long *d_table);
+
+// The row code of k_hp_keep, which the store of the path abundance (k_ab_keep, vga_abundance.hip) keeps its rows with as well.  A wave
+// per winner i: row rows[i] of the call's two matrices, lanes over the paths as in k_gl_deficit (a path past the end is never
+// loaded: 0 is the identity of an unsigned maximum), the maximum reduced over the wave, then the byte row and the scored byte of
+// store row i.  The bytes behind the last path are written as zero.
+__device__ __forceinline__ void hp_keep_row(uint32_t i, uint32_t lane, uint32_t n_paths, uint32_t pitch, uint32_t cap, const uint32_t *__restrict__ rows,
+                                            const uint32_t *__restrict__ bases, const uint32_t *__restrict__ edges, uint8_t *__restrict__ deficits,
+                                            uint8_t *__restrict__ scored)
+{
+    const size_t row = (size_t)rows[i] * n_paths;
+    unsigned long long m = 0;
+    for (uint32_t p = lane; p < n_paths; p += 64u) m = max(m, (unsigned long long)bases[row + p] + edges[row + p]);
+#pragma unroll
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_xor(m, off));
+    uint8_t *out = deficits + (size_t)i * pitch;
+    for (uint32_t p = lane; p < pitch; p += 64u) {
+        unsigned long long d = 0;
+        if (p < n_paths) d = min(m - ((unsigned long long)bases[row + p] + edges[row + p]), (unsigned long long)cap);
+        out[p] = (uint8_t)d;
+    }
+    if (lane == 0) scored[i] = m != 0 ? 1u : 0u;
+}
+
+// A grow-only store of deficit rows and scored bytes makes room for `at` rows: it doubles from first_rows on, and what is stored
+// (n_rows rows) moves on the context's stream.  `what` names the store in the messages.  VGA_ERR_NOMEM, with the rows kept, when it
+// cannot grow.
+int hp_store_grow(vga_ctx *ctx, const char *what, uint8_t *&d_deficits, uint8_t *&d_scored, uint64_t &cap_rows, uint64_t n_rows, uint64_t first_rows,
+                  uint32_t pitch, uint64_t at);
 #endif

@@ -9,6 +9,7 @@
 #include "vga_genotype_lik.hpp"
 #include "vga_path_edit.hpp"
 #include "vga_hap_paths.hpp"
+#include "vga_abundance.hpp"
 #include "vga_phase.hpp"
 
 #include <algorithm>
@@ -251,9 +252,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         if (gl_from_edit && !ps->pe)
             return vga_set_error(ctx, VGA_ERR_ARG, "vga_align_batch: the likelihood reads the edit distance (vga_genotype_lik_source), which is off (vga_path_edit_begin)");
         hp_state *hp = hp_active(ctx);  // the deficit store beside the phase store is on: it keeps a row per winner, from the matrices of its source
+        ab_state *ab = ps->ab.get();    // ... and so does the store of the path abundance
         if (ps->pe) {  // the edit distance is on: its three kernels over the same winners, on the same stream
             if (!q) return vga_set_error(ctx, VGA_ERR_ARG, "path edit: no queries");
-            const int rc = pe_add_call(ctx, ps, v, ps->d_rows.p, nw, n_reads, *q, gl_from_edit || (hp && hp_from_edit(hp)));
+            const int rc = pe_add_call(ctx, ps, v, ps->d_rows.p, nw, n_reads, *q, gl_from_edit || (hp && hp_from_edit(hp)) || (ab && ab_from_edit(ab)));
             if (rc != VGA_OK) return rc;
         }
         if (ps->gt) {  // genotyping is on: the pairs of paths over the two matrices, behind k_ps_score on the same stream
@@ -267,6 +269,10 @@ int ps_score_winners(vga_ctx *ctx, ps_state *ps, const cov_win_view &v, const st
         }
         if (hp) {  // behind k_ps_score and the edit kernels on the same stream
             const int rc = hp_keep_winners(ctx, hp, ps, ps->d_rows.p, nw);
+            if (rc != VGA_OK) return rc;
+        }
+        if (ab) {  // likewise
+            const int rc = ab_keep_winners(ctx, ab, ps, ps->d_rows.p, nw);
             if (rc != VGA_OK) return rc;
         }
     } else if (ps->pe) {  // (no winner: the call's matrix is all NONE)

@@ -28,6 +28,7 @@ struct gt_state;
 struct gl_state;
 struct pe_state;
 struct pe_queries;
+struct ab_state;
 
 // The per-path accumulators of path support and of the edit distance: four columns of n_paths 64-bit words, then two scalars.
 struct ps_acc_block {
@@ -63,11 +64,13 @@ struct ps_state {
     vga_owned<gl_state> gl{nullptr, nullptr};
     // ---- the path sequences and accumulators while the edit distance is on (vga_path_edit.hip), released with this state
     vga_owned<pe_state> pe{nullptr, nullptr};
+    // ---- the store of deficit rows while the path abundance is on (vga_abundance.hip), released with this state
+    vga_owned<ab_state> ab{nullptr, nullptr};
 };
 // the context's path support state while it is on (vga_path_support_begin), else null
 ps_state *ps_active(vga_ctx *ctx);
 
-// The life cycle of a stage S that lives in a slot of ps_state (gt, gl, pe), behind its _begin, _end and _reset entry points, which
+// The life cycle of a stage S that lives in a slot of ps_state (gt, gl, pe, ab), behind its _begin, _end and _reset entry points, which
 // keep their own argument checks.  begin: path support is on; a second begin starts over; init(ps, s) sets the new state up, and a
 // failure drains the stream (host arrays of init, or of the state itself, may be on their way) and releases it.
 template <typename S, class Init>

@@ -86,7 +86,17 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // --haplotype-paths-cap C: the largest deficit told apart (64, 1..255); --haplotype-paths-top N: the
                           // paths written per group (5, 0 for all); --haplotype-paths-from support|edit: the matrices scored
                           {"", "--haplotype-paths", false, "haplotype-paths"}, {"", "--haplotype-paths-cap", true, "haplotype-paths-cap"},
-                          {"", "--haplotype-paths-top", true, "haplotype-paths-top"}, {"", "--haplotype-paths-from", true, "haplotype-paths-from"}};
+                          {"", "--haplotype-paths-top", true, "haplotype-paths-top"}, {"", "--haplotype-paths-from", true, "haplotype-paths-from"},
+                          // not in the reference: the share of the reads that each P line of --graph explains, fitted over all paths at
+                          // once by expectation-maximisation on the GPU (<out>-path-abundance.tsv); --abundance-lambda N: the cost of one
+                          // unit of deficit in 1/256 bit (512, 1..4096); --abundance-cap C: the largest deficit told apart (64, 1..255);
+                          // --abundance-iters N: the most iterations (1000, 1..100000); --abundance-tol N: the largest move of a share,
+                          // in units of 2^-24, at which the estimate stops (16, 0..16777216); --abundance-min N: the parts per million
+                          // from which a path is written (10000, 0 for every path); --abundance-from support|edit: the matrices scored
+                          {"", "--path-abundance", false, "path-abundance"}, {"", "--abundance-lambda", true, "abundance-lambda"},
+                          {"", "--abundance-cap", true, "abundance-cap"}, {"", "--abundance-iters", true, "abundance-iters"},
+                          {"", "--abundance-tol", true, "abundance-tol"}, {"", "--abundance-min", true, "abundance-min"},
+                          {"", "--abundance-from", true, "abundance-from"}};
 
 template <size_t N>
 std::map<std::string, std::string> parse(const Flag (&flags)[N], int argc, char **argv, int first)
@@ -273,6 +283,26 @@ int map_main(int argc, char **argv)
         if (v != "edit" && v != "support") throw Error("--haplotype-paths-from takes edit or support: not " + v);
         o.haplotype_paths_from_edit = v == "edit";
     }
+    o.path_abundance = m.count("path-abundance") > 0;
+    if (o.path_abundance && !o.also_align) throw Error("--path-abundance estimates from alignments: it needs --also-align");
+    for (const char *key : {"abundance-lambda", "abundance-cap", "abundance-iters", "abundance-tol", "abundance-min", "abundance-from"})
+        if (m.count(key) && !o.path_abundance) throw Error(std::string("--") + key + " has no meaning without --path-abundance");
+    auto abundance_value = [&](const char *key, uint64_t lo, uint64_t hi) -> uint64_t {
+        const std::string v = m[key], flag = std::string("--") + key;
+        if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos || std::stoull(v) < lo || std::stoull(v) > hi)
+            throw Error(flag + " takes a number " + (hi == UINT64_MAX ? "of at least " + std::to_string(lo) : "from " + std::to_string(lo) + " to " + std::to_string(hi)) + ": not " + v);
+        return std::stoull(v);
+    };
+    if (m.count("abundance-lambda")) o.abundance_lambda = (uint32_t)abundance_value("abundance-lambda", 1, 4096);
+    if (m.count("abundance-cap")) o.abundance_cap = (uint32_t)abundance_value("abundance-cap", 1, 255);
+    if (m.count("abundance-iters")) o.abundance_iters = (uint32_t)abundance_value("abundance-iters", 1, 100000);
+    if (m.count("abundance-tol")) o.abundance_tol = (uint32_t)abundance_value("abundance-tol", 0, 1u << 24);
+    if (m.count("abundance-min")) o.abundance_min = abundance_value("abundance-min", 0, UINT64_MAX);
+    if (m.count("abundance-from")) {
+        const std::string v = m["abundance-from"];
+        if (v != "edit" && v != "support") throw Error("--abundance-from takes edit or support: not " + v);
+        o.abundance_from_edit = v == "edit";
+    }
     o.also_validate = m.count("also-validate") > 0;
     if (o.also_validate) {
         if (!o.also_align) fprintf(stderr, "[vgaligner] --also-validate has no effect without --also-align (map.rs:150-186)\n");
@@ -294,14 +324,14 @@ int map_main(int argc, char **argv)
         }
         if (o.devices.empty()) throw Error("--devices needs a comma-separated list of GPU ids");
     }
-    // --path-support, --genotype, --genotype-likelihood, --path-edit, --haplotype-paths: the P lines of --graph, and the graph checked against the index,
+    // --path-support, --genotype, --genotype-likelihood, --path-edit, --haplotype-paths, --path-abundance: the P lines of --graph, and the graph checked against the index,
     // before any device is opened
     std::unique_ptr<HashGraph> graph;
     const bool scoring = scoring_on(o);
     if (scoring) {
         graph.reset(new HashGraph(HashGraph::from_gfa(m["graph"])));
         o.paths = path_table(*graph);
-        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : o.genotype_likelihood ? "--genotype-likelihood: " : o.path_edit ? "--path-edit: " : "--haplotype-paths: ") + m["graph"] + " has no P line");
+        if (o.paths.n_paths() == 0) throw Error(std::string(o.path_support ? "--path-support: " : o.genotype ? "--genotype: " : o.genotype_likelihood ? "--genotype-likelihood: " : o.path_edit ? "--path-edit: " : o.haplotype_paths ? "--haplotype-paths: " : "--path-abundance: ") + m["graph"] + " has no P line");
     } else
         prewarm_contexts(o);  // (HIP starts beside the reading of the index and the reads)
     Index ix = Index::load(exact ? idx : idx + ".idx");
@@ -363,6 +393,16 @@ int map_main(int argc, char **argv)
                 (unsigned long long)out.n_hap_path_groups, (unsigned long long)out.n_hap_path_scored, (unsigned long long)out.n_hap_path_kept);
         fprintf(stderr, "[vgaligner] haplotype-paths: %s\n", out.n_hap_path_groups ? out.hap_path_call.c_str() : "no call");
     }
+    if (o.path_abundance) {
+        if (out.n_abundance_scored) {
+            std::string s;
+            for (size_t i = 0; i < out.abundance_ppm.size(); i++) s += (i ? ", " : ": ") + std::to_string(out.abundance_ppm[i]) + " ppm";
+            fprintf(stderr, "[vgaligner] path-abundance: %llu reads scored of %llu kept, %llu iterations (%s), %zu paths at or above %llu ppm%s\n",
+                    (unsigned long long)out.n_abundance_scored, (unsigned long long)out.n_abundance_kept, (unsigned long long)out.abundance_iterations,
+                    out.abundance_converged ? "converged" : "not converged", out.abundance_ppm.size(), (unsigned long long)o.abundance_min, s.c_str());
+        } else
+            fprintf(stderr, "[vgaligner] path-abundance: no call\n");
+    }
     if (o.haplotag)
         fprintf(stderr, "[vgaligner] haplotag: %llu rows of %llu reads: %llu a, %llu b, %llu undecided\n", (unsigned long long)out.n_haplotag_rows,
                 (unsigned long long)out.n_phase_reads, (unsigned long long)out.n_haplotag_a, (unsigned long long)out.n_haplotag_b,
@@ -420,7 +460,9 @@ int main(int argc, char **argv)
                         "                                 (with --haplotag: [--haplotype-calls])\n"
                         "                                 (with --phase: [--phase-join [--phase-join-min-reads 2]])\n"
                         "                                 (with --phase: [--haplotype-paths [--haplotype-paths-cap 64] [--haplotype-paths-top 5]\n"
-                        "                                                 [--haplotype-paths-from support|edit]])\n");
+                        "                                                 [--haplotype-paths-from support|edit]])\n"
+                        "                [--path-abundance [--abundance-lambda 512] [--abundance-cap 64] [--abundance-iters 1000] [--abundance-tol 16]\n"
+                        "                                  [--abundance-min 10000] [--abundance-from support|edit]]\n");
         return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "vgaligner: %s\n", e.what());

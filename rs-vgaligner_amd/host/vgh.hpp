@@ -235,9 +235,21 @@ struct MapOptions {
     bool haplotype_paths = false, haplotype_paths_from_edit = false;
     uint32_t haplotype_paths_cap = 64;
     uint64_t haplotype_paths_top = 5;
+    // --path-abundance (not in the reference; needs also_align and the P lines of --graph): keep a row of path deficits per reported
+    // alignment (vga_path_abundance_begin: abundance_cap 1 .. 255, from the edit distance under abundance_from_edit) and estimate,
+    // on the GPU, the share of the reads that every P line explains by expectation-maximisation (vga_path_abundance: abundance_lambda
+    // 1 .. 4096 in 1/256 bit per unit of deficit, at most abundance_iters iterations, 1 .. 100 000, until no share moves by more than
+    // abundance_tol, 0 .. 2^24, in units of 2^-24; several contexts: each hands its store over, n_paths + 1 bytes per reported
+    // alignment, and the first estimates once from the concatenated rows, vga_path_abundance_rows).  Writes the paths of at least
+    // abundance_min parts per million (0: every path) to <out>-path-abundance.tsv.  Turns path support on, not its files; the edit
+    // distance likewise under abundance_from_edit.
+    bool path_abundance = false, abundance_from_edit = false;
+    uint32_t abundance_lambda = 512, abundance_cap = 64, abundance_iters = 1000, abundance_tol = 16;
+    uint64_t abundance_min = 10000;
     PathTable paths;
 };
-// the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit): it needs `paths`
+// the run scores alignments against the P lines of the graph (path_support, genotype, genotype_likelihood, path_edit, haplotype_paths,
+// path_abundance): it needs `paths`
 bool scoring_on(const MapOptions &opt);
 
 // VGA_TRACE=1: wall-clock marks of the driver's phases on stderr (since the first call)
@@ -269,6 +281,11 @@ struct MapOutput {
     // bit) and how much more the next pair costs
     uint64_t n_likelihood_scored = 0, likelihood_cost = 0, likelihood_next = 0;
     std::string likelihood_a, likelihood_b;
+    // MapOptions::path_abundance: the scored rows (0: no call) of the rows kept, the iterations and whether they converged, and the
+    // parts per million of the paths written, from the largest down
+    uint64_t n_abundance_scored = 0, n_abundance_kept = 0, abundance_iterations = 0;
+    bool abundance_converged = false;
+    std::vector<uint64_t> abundance_ppm;
 };
 
 // One [begin, end) range of the read list, the device slot (index into MapOptions::devices) that maps it.

@@ -7,6 +7,7 @@
 #include "../csrc/vga_hapcall.hpp"
 #include "../csrc/vga_phase_join.hpp"
 #include "../csrc/vga_hap_paths.hpp"
+#include "../csrc/vga_abundance.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -56,7 +57,7 @@ void PhaseLinks::chain(uint32_t min_links)
     ph_chain(n, links.data(), min_links, ps.data(), flip.data(), link_d.data());
 }
 
-bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit || opt.haplotype_paths; }
+bool scoring_on(const MapOptions &opt) { return opt.path_support || opt.genotype || opt.genotype_likelihood || opt.path_edit || opt.haplotype_paths || opt.path_abundance; }
 
 namespace {
 
@@ -346,6 +347,29 @@ void haplotype_paths_write(const MapOptions &opt, const std::vector<uint32_t> &p
     if (!out_prefix.empty()) write_file(out_prefix + "-haplotype-paths.tsv", t);
 }
 
+// One line per path of at least abundance_min parts per million, by theta descending, then in P-line order; the header alone
+// without a call.
+void abundance_write(const MapOptions &opt, const Abundance &a, MapOutput &out, const std::string &out_prefix)
+{
+    const size_t np = opt.paths.n_paths();
+    out.n_abundance_scored = a.n_scored; out.n_abundance_kept = a.n_kept; out.abundance_iterations = a.iterations; out.abundance_converged = a.converged != 0;
+    out.abundance_ppm.clear();
+    std::string t = "rank\tpath\tppm\ttheta\treads_q16\tbest\n";
+    if (a.n_scored) {
+        std::vector<uint32_t> order(np);
+        for (uint32_t p = 0; p < np; p++) order[p] = p;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a.theta[x] > a.theta[y]; });
+        for (uint32_t p : order) {
+            const uint64_t ppm = vga_ab_ppm(a.theta[p]);
+            if (ppm < opt.abundance_min) continue;
+            out.abundance_ppm.push_back(ppm);
+            put_u64(t, out.abundance_ppm.size()); t += '\t'; t += opt.paths.names[p]; t += '\t'; put_u64(t, ppm); t += '\t'; put_u64(t, a.theta[p]); t += '\t';
+            put_u64(t, a.reads_q16[p]); t += '\t'; put_u64(t, a.best[p]); t += '\n';
+        }
+    }
+    if (!out_prefix.empty()) write_file(out_prefix + "-path-abundance.tsv", t);
+}
+
 // one line per (kept read, phase set) in which a site votes: the read as the input file numbers it, the set as <out>-phase.tsv
 // numbers it, the haplotype with more votes (. on a tie) and the votes; by read, then by set.  The rows come in store order, which
 // is read order unless several contexts kept the reads.
@@ -521,6 +545,11 @@ void check_aligner(const MapOptions &opt)
     if (opt.haplotype_paths && opt.paths.n_paths() == 0) throw Error("--haplotype-paths: the graph has no P line");
     if (opt.haplotype_paths && (opt.haplotype_paths_cap < 1 || opt.haplotype_paths_cap > HP_CAP_MAX)) throw Error("--haplotype-paths-cap is 1 to 255");
     if (opt.haplotype_paths_from_edit && !opt.haplotype_paths) throw Error("--haplotype-paths-from has no meaning without --haplotype-paths");
+    if (opt.path_abundance && !opt.also_align) throw Error("--path-abundance estimates from alignments: it needs --also-align");
+    if (opt.path_abundance && opt.paths.n_paths() == 0) throw Error("--path-abundance: the graph has no P line");
+    if (opt.path_abundance && (opt.abundance_cap < 1 || opt.abundance_cap > AB_CAP_MAX || !vga_ab_params_ok(opt.abundance_lambda, opt.abundance_iters, opt.abundance_tol)))
+        throw Error("--path-abundance: --abundance-lambda is 1 to 4096, --abundance-cap 1 to 255, --abundance-iters 1 to 100000 and --abundance-tol 0 to 16777216");
+    if (opt.abundance_from_edit && !opt.path_abundance) throw Error("--abundance-from has no meaning without --path-abundance");
     if ((opt.coverage || opt.coverage_only) && !opt.also_align) throw Error("--coverage counts alignments: it needs --also-align");
     if (opt.poa_aligner != "abpoa") {
         if (opt.poa_aligner == "rspoa") throw Error("the rspoa aligner is not available in the MI355X build yet; use -p abpoa");
@@ -539,6 +568,7 @@ void Tables::begin(vga_ctx *ctx) const
         if (opt_.genotype) check(ctx, vga_genotype_begin(ctx));
         if (opt_.genotype_likelihood) check(ctx, vga_genotype_lik_begin(ctx, opt_.genotype_lambda, opt_.genotype_cap));
         if (opt_.genotype_likelihood && opt_.genotype_from_edit) check(ctx, vga_genotype_lik_source(ctx, VGA_GL_FROM_EDIT));
+        if (abundance()) check(ctx, vga_path_abundance_begin(ctx, opt_.abundance_cap, opt_.abundance_from_edit ? VGA_AB_FROM_EDIT : VGA_AB_FROM_SUPPORT));
     }
     if (piling()) check(ctx, vga_pileup_begin(ctx));
     if (inserting()) check(ctx, vga_insertion_begin(ctx));
@@ -609,6 +639,21 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         t.pad({np, np, np, np});
         check(ctx, vga_path_edit_read(ctx, t.v[0].data(), t.v[1].data(), t.v[2].data(), t.v[3].data(), &t.n[0], &t.n[1]));
         edit_.add(t);
+    }
+    if (abundance()) {
+        Abundance &a = abundance_;
+        check(ctx, vga_path_abundance_store(ctx, 0, nullptr, nullptr, &a.n_kept));
+        if (call_now) {  // from the context's own store
+            a.theta.assign(np + 1, 0); a.reads_q16.assign(np + 1, 0); a.best.assign(np + 1, 0);
+            check(ctx, vga_path_abundance(ctx, opt_.abundance_lambda, opt_.abundance_iters, opt_.abundance_tol, a.theta.data(), a.reads_q16.data(), a.best.data(),
+                                          &a.n_scored, &a.iterations, &a.converged));
+        } else {  // the whole store for the estimate from all of them: n_paths + 1 bytes per reported alignment
+            uint64_t n_rows = a.n_kept;
+            a.deficits.assign(n_rows * np + 1, 0); a.scored.assign(n_rows + 1, 0);
+            check(ctx, vga_path_abundance_store(ctx, n_rows, a.deficits.data(), a.scored.data(), &n_rows));
+            if (n_rows != a.n_kept) throw Error("--path-abundance: the store of slot " + std::to_string(slot) + " changed while it was read");
+            a.deficits.resize(n_rows * np); a.scored.resize(n_rows);
+        }
     }
     // (VGA_TRACE: what each of the two routes to the sites costs at the device's end, tests/prof_variant.py)
     const auto t0 = std::chrono::steady_clock::now();
@@ -699,7 +744,7 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
 void Tables::end(vga_ctx *ctx) const
 {
     if (coverage()) (void)vga_coverage_end(ctx);
-    if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping and the edit distance with it)
+    if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping, the edit distance and the store of the path abundance with it)
     if (hap_typing()) (void)vga_haplotype_paths_end(ctx);
     if (phasing()) (void)vga_phase_end(ctx);
     if (piling()) (void)vga_pileup_end(ctx);
@@ -719,6 +764,9 @@ void Tables::add(const Tables &o)
     hap_paths_.deficits.insert(hap_paths_.deficits.end(), o.hap_paths_.deficits.begin(), o.hap_paths_.deficits.end());  // (in the order of the records)
     hap_paths_.scored.insert(hap_paths_.scored.end(), o.hap_paths_.scored.begin(), o.hap_paths_.scored.end());
     tags_.read_ids.insert(tags_.read_ids.end(), o.tags_.read_ids.begin(), o.tags_.read_ids.end());  // (in the order of the records)
+    abundance_.deficits.insert(abundance_.deficits.end(), o.abundance_.deficits.begin(), o.abundance_.deficits.end());  // (the estimate does not depend on the order)
+    abundance_.scored.insert(abundance_.scored.end(), o.abundance_.scored.begin(), o.abundance_.scored.end());
+    abundance_.n_kept += o.abundance_.n_kept;
 }
 
 void Tables::phase_sites()
@@ -749,6 +797,18 @@ std::vector<uint32_t> Tables::insertion_sites()
 
 void Tables::call(vga_ctx *ctx)
 {
+    if (abundance()) {
+        Abundance &a = abundance_;
+        const size_t np = opt_.paths.n_paths();
+        if (a.scored.size() != a.n_kept || a.deficits.size() != a.n_kept * np)
+            throw Error("--path-abundance: the contexts kept " + std::to_string(a.n_kept) + " rows and handed over " + std::to_string(a.scored.size()));
+        a.theta.assign(np + 1, 0); a.reads_q16.assign(np + 1, 0); a.best.assign(np + 1, 0);
+        a.deficits.push_back(0); a.scored.push_back(0);  // (never a null array)
+        check(ctx, vga_path_abundance_rows(ctx, a.n_kept, (uint32_t)np, a.deficits.data(), a.scored.data(), opt_.abundance_lambda, opt_.abundance_iters,
+                                           opt_.abundance_tol, a.theta.data(), a.reads_q16.data(), a.best.data(), &a.n_scored, &a.iterations, &a.converged));
+        trace_mark("path abundance estimated");
+    }
+    if (!opt_.call_variants) return;
     pileup_.pad({ix_.seq_length * 7});
     variant_fetch(ctx, variants_, [&](uint64_t cap, uint32_t *pos, uint8_t *gt, uint32_t *qual, uint64_t *iq, uint64_t *depth, uint64_t *counts, uint64_t *nt, uint64_t *nc) {
         return vga_variant_call_table(ctx, ix_.seq_length, pileup_.v[0].data(), ix_.seq_fwd.data(), opt_.call_error, opt_.call_min_depth, opt_.call_min_qual, cap,
@@ -852,6 +912,11 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
             if (files) path_support_write(opt_, paths_, rows.path, out_prefix);
             trace_mark("path support tables written");
         }
+    }
+    if (abundance()) {
+        abundance_.theta.resize(np + 1, 0); abundance_.reads_q16.resize(np + 1, 0); abundance_.best.resize(np + 1, 0);
+        abundance_write(opt_, abundance_, out, out_prefix);
+        trace_mark("path abundance written");
     }
     if (opt_.call_variants) {
         out.n_variant_tested = variants_.n_tested; out.n_variant_calls = variants_.n_calls;

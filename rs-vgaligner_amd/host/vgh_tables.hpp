@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join, --haplotype-paths): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join, --haplotype-paths, --path-abundance): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -95,6 +95,16 @@ struct HapPaths {
     uint64_t n_sets = 0;
 };
 
+// The path abundance (MapOptions::path_abundance): the deficit rows of the reported alignments, dense, and their scored bytes (kept
+// only for the route of several contexts), the rows kept, and the estimate
+struct Abundance {
+    std::vector<uint8_t> deficits, scored;
+    uint64_t n_kept = 0, n_scored = 0;
+    std::vector<uint32_t> theta;
+    std::vector<uint64_t> reads_q16, best;
+    uint32_t iterations = 0, converged = 0;
+};
+
 // The per-read lines of <out>-path-support-reads.tsv and <out>-path-edit-reads.tsv, in read order
 struct ReadRows {
     std::string path, edit;
@@ -113,7 +123,8 @@ public:
     // likelihood from the edit distance turns that on; --call-variants turns the counting of the pileup on, not its file.
     bool coverage() const { return opt_.coverage || opt_.coverage_only; }
     bool scoring() const { return scoring_on(opt_); }
-    bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit) || (opt_.haplotype_paths && opt_.haplotype_paths_from_edit); }
+    bool edit() const { return opt_.path_edit || (opt_.genotype_likelihood && opt_.genotype_from_edit) || (opt_.haplotype_paths && opt_.haplotype_paths_from_edit) ||
+                              (opt_.path_abundance && opt_.abundance_from_edit); }
     bool piling() const { return opt_.pileup || opt_.call_variants; }
     bool inserting() const { return opt_.call_insertions; }
     bool phasing() const { return opt_.phase; }
@@ -121,9 +132,11 @@ public:
     bool hap_calling() const { return opt_.haplotype_calls; }
     bool joining() const { return opt_.phase_join; }
     bool hap_typing() const { return opt_.haplotype_paths; }
+    bool abundance() const { return opt_.path_abundance; }
     bool any() const { return coverage() || scoring() || piling() || inserting(); }  // (phasing needs piling)
-    // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call())
-    bool call_summed(uint32_t n_contexts) const { return opt_.call_variants && n_contexts > 1; }
+    // --call-variants over several contexts: they hand their pileup tables over, and the first calls from the sum (call());
+    // --path-abundance likewise: they hand their stores over, and the first estimates from the concatenated rows
+    bool call_summed(uint32_t n_contexts) const { return (opt_.call_variants || opt_.path_abundance) && n_contexts > 1; }
 
     // turns the analyses on, on a context that holds the index
     void begin(vga_ctx *ctx) const;
@@ -139,7 +152,8 @@ public:
     void end(vga_ctx *ctx) const;
     void add(const Tables &o);
     // the variants of the summed pileup table, and the insertions at their sites from the summed insertion table, called on `ctx`
-    // and the links of the heterozygous sites, the reads' tags and the haplotype counts from the concatenated stores (any context: its own counters are not touched)
+    // and the links of the heterozygous sites, the reads' tags and the haplotype counts from the concatenated stores (any context: its own counters are not touched);
+    // the path abundance from the concatenated rows
     void call(vga_ctx *ctx);
     // the TSV files beside the GAF files (out_prefix == "": none) and the fields of `out`
     void write(MapOutput &out, const ReadRows &rows, const std::string &out_prefix);
@@ -162,6 +176,7 @@ private:
     HaplotypeCounts hap_counts_;
     PhaseJoin join_;
     HapPaths hap_paths_;
+    Abundance abundance_;
     // the sets the tags and the haplotype counts work on: the joined ones under --phase-join, else the chain's
     const std::vector<uint32_t> &sets_ps() const { return joining() ? join_.ps : phase_.ps; }
     const std::vector<uint8_t> &sets_flip() const { return joining() ? join_.flip : phase_.flip; }
