@@ -616,6 +616,58 @@ int vga_insertion_call_table(vga_ctx *ctx, uint64_t n, const uint64_t *rows_in /
                              uint64_t *length_reads /* n */, uint8_t *seq /* n * 8 */, uint64_t *seq_reads /* n * 8 */,
                              uint64_t *rows /* n * 49 */);
 
+/* ---- deletion call: deletions of several graph bases as one event each ----------
+ * Stands in for nothing in the reference.  The pileup counts a deleted base where it lies and the variant call calls every base
+ * alone: a deletion of ten bases is ten D calls.  Here a deletion is one event.  It is defined on the alignments GAF text, the
+ * node starts and the pileup table alone (tests/deletion_ref.py recomputes it).
+ *   run        one "-g.." token of the cs string of the record reported for a read (a maximal sequence of D operations): len its
+ *              letters, first and last the positions on the linearised graph of its first and last deleted base.
+ *   end run    a run with no ":" or "*" token before it in the record, or none behind it.  The alignment is global over its
+ *              subgraph, so such a run is where the subgraph ends, not a deletion of the sample: it is counted in n_end_runs and
+ *              otherwise ignored (it still counts in the pileup and in the variant call).
+ *   event      every other run, as the three 32-bit words (first, len, last).  last - first != len - 1 means the run crosses
+ *              nodes; the same (first, len) may have two values of last through a bubble, so last is part of the identity.
+ *   store      while it is on, every vga_align_batch appends the events of its reported alignments to a grow-only store on the
+ *              device, in the order of the reported alignments and then along the alignment.  It doubles; VGA_ERR_NOMEM, with the
+ *              alignments kept, when it cannot grow or would pass 2^32 - 1 words.
+ *   call       the events sorted by (first, len, last) ascending and grouped: reads is the size of a group, depth the sum
+ *              A + C + G + T + N + del of the pileup row at first (the depth of the variant call, end runs of other reads
+ *              included).  With k = min(reads, depth) and the error cost E: none costs k E, het 256 depth, hom (depth - k) E; the
+ *              first minimum in that order is the state (0 none, 1 het, 2 hom) and qual the second smallest cost minus the
+ *              smallest, saturated at 2^32 - 1: the insertion-state rule of the variant call.  vga_deletion_state is that rule.
+ *   reported   a group with depth >= min_depth, a state other than none and qual >= min_qual; the calls come in sort order.
+ *   not done   no haplotype is attributed, a run split by one spurious match is two events, nearly identical events (a start
+ *              shifted by one) are not merged, and the depth is taken at the first base only.
+ *   vga_deletion_begin       after vga_pileup_begin (VGA_ERR_ARG without it; VGA_ERR_NO_INDEX without an index); empties the store.
+ *   vga_deletion_read        events: 3 x n_events words (ask with NULL first); n_alignments counted since _begin / _reset; any
+ *                            pointer may be NULL; does not reset.
+ *   vga_deletion_reset       empty, keep storing (VGA_ERR_ARG without _begin).
+ *   vga_deletion_end         free, stop storing.  vga_pileup_end and a new index drop the store as well.
+ *   vga_deletion_call        from the context's own store and pileup counters.  E, min_depth and min_qual as in vga_variant_call.
+ *                            Per reported group first, len, last, state, qual, depth, reads: the first min(n_calls, cap) of them;
+ *                            n_distinct (the groups) and n_calls always.  When cap < n_calls nothing is written beyond cap and the
+ *                            caller asks again.  VGA_ERR_ARG for a NULL array with cap > 0.  Does not reset.
+ *   vga_deletion_call_table  the kernel seam, and the route of several contexts: explicit events (3 x n_events words) and an
+ *                            explicit pileup table (n_bases x 7 counters of 64 bits).  Needs a context only.  Every event is
+ *                            checked before anything is launched: first and last below n_bases and len >= 1, else VGA_ERR_ARG.
+ *                            VGA_ERR_UNSUPPORTED for 2^32 - 1 events or more, for 2^31 bases or more and for a counter of 2^40 or
+ *                            more (found on the device).
+ * With the store off vga_align_batch does what it did before these calls existed: no extra launch, no extra allocation. */
+int vga_deletion_begin(vga_ctx *ctx);
+int vga_deletion_read(vga_ctx *ctx, uint32_t *events /* 3 * n_events */, uint64_t *n_alignments, uint64_t *n_events, uint64_t *n_end_runs);
+int vga_deletion_reset(vga_ctx *ctx);
+int vga_deletion_end(vga_ctx *ctx);
+int vga_deletion_call(vga_ctx *ctx, uint32_t error, uint64_t min_depth, uint64_t min_qual, uint64_t cap, uint32_t *first /* cap */,
+                      uint32_t *len /* cap */, uint32_t *last /* cap */, uint8_t *state /* cap */, uint32_t *qual /* cap */,
+                      uint64_t *depth /* cap */, uint64_t *reads /* cap */, uint64_t *n_distinct, uint64_t *n_calls);
+int vga_deletion_call_table(vga_ctx *ctx, uint64_t n_events, const uint32_t *events /* 3 * n_events */, uint64_t n_bases,
+                            const uint64_t *counts /* n_bases * 7 */, uint32_t error, uint64_t min_depth, uint64_t min_qual, uint64_t cap,
+                            uint32_t *first /* cap */, uint32_t *len /* cap */, uint32_t *last /* cap */, uint8_t *state /* cap */,
+                            uint32_t *qual /* cap */, uint64_t *depth /* cap */, uint64_t *reads /* cap */, uint64_t *n_distinct,
+                            uint64_t *n_calls);
+/* the rule alone, no context: the state for `reads` alignments that hold an event at a base of `depth`; *qual (may be NULL) */
+uint32_t vga_deletion_state(uint64_t reads, uint64_t depth, uint32_t error, uint32_t *qual);
+
 /* ---- phase: which alleles of the heterozygous calls travel together on the reads ----------
  * Stands in for nothing in the reference.  The variant call reports independent diploid sites; this is the read-backed linkage
  * between the heterozygous ones.  It is defined on the alignments GAF text, the node starts, the graph's letters and the sites

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "vga_path_edit_begin", "vga_path_edit_read", "vga_path_edit_last", "vga_path_edit_reset", "vga_path_edit_end", "vga_path_edit_pairs",
     "vga_variant_call", "vga_variant_call_table",
     "vga_insertion_begin", "vga_insertion_read", "vga_insertion_reset", "vga_insertion_end", "vga_insertion_call", "vga_insertion_call_table",
+    "vga_deletion_begin", "vga_deletion_read", "vga_deletion_reset", "vga_deletion_end", "vga_deletion_call", "vga_deletion_call_table", "vga_deletion_state",
     "vga_phase_begin", "vga_phase_read", "vga_phase_reset", "vga_phase_end", "vga_phase_links", "vga_phase_links_lists", "vga_phase_chain",
     "vga_phase_tags", "vga_phase_tags_lists",
     "vga_haplotype_counts", "vga_haplotype_counts_lists", "vga_haplotype_jobs", "vga_haplotype_call",
@@ -98,6 +99,13 @@ VARIANT_MIN_QUAL = 512
 VARIANT_ALLELES = "ACGT-"  # alleles 0..4 as <out>-variants.tsv writes them: D, the deleted base, is '-'
 VARIANT_INS_STATES = (".", "het", "hom")
 
+# the deletion events (csrc/vga_deletion.hpp): the words of an event (first, len, last), the first size of the grow-only store in
+# events, the events one call takes, the bound of a 64-bit counter of vga_deletion_call_table, and the states of a call
+DELETION_EVENT_WORDS = 3
+DELETION_STORE_EVENTS0 = 1024
+DELETION_MAX_EVENTS = (1 << 32) - 1
+DELETION_MAX_COUNT = 1 << 40
+DELETION_STATES = ("none", "het", "hom")
 # the insertion table (csrc/vga_insertion.hpp): the letters of an inserted run that are kept, and the 32-bit counters of a graph
 # base -- the bins of length 1 .. 8 and `more`, then per kept position the letters A C G T N; the graph and the counters that
 # vga_insertion_begin and vga_insertion_call_table serve
@@ -358,6 +366,19 @@ def load_library():
         for name in ABI_SYMBOLS:
             if name.startswith("vga_insertion_"):
                 getattr(L, name).restype = C.c_int
+    if hasattr(L, "vga_deletion_begin"):  # (absent from an older build named by VGA_LIB; the Context.deletion* calls then fail)
+        u64p, u32p, u8p, u64 = _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint8), C.c_uint64
+        for name in ("vga_deletion_begin", "vga_deletion_reset", "vga_deletion_end"):
+            getattr(L, name).argtypes = [vp]
+        L.vga_deletion_read.argtypes = [vp, u32p, u64p, u64p, u64p]
+        outs = [u64, u32p, u32p, u32p, u8p, u32p, u64p, u64p, u64p, u64p]
+        L.vga_deletion_call.argtypes = [vp, C.c_uint32, u64, u64] + outs
+        L.vga_deletion_call_table.argtypes = [vp, u64, u32p, u64, u64p, C.c_uint32, u64, u64] + outs
+        L.vga_deletion_state.argtypes = [u64, u64, C.c_uint32, u32p]
+        for name in ABI_SYMBOLS:
+            if name.startswith("vga_deletion_"):
+                getattr(L, name).restype = C.c_int
+        L.vga_deletion_state.restype = C.c_uint32
     if hasattr(L, "vga_phase_begin"):  # (absent from an older build named by VGA_LIB; the Context.phase* calls then fail)
         u64p, u32p, u8p, u64 = _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint8), C.c_uint64
         for name in ("vga_phase_begin", "vga_phase_reset", "vga_phase_end"):
@@ -1057,6 +1078,66 @@ class Context:
         return self._insertion(lambda *outs: self.L.vga_insertion_call_table(self.h, len(tab), _u64p(tab if len(tab) else np.zeros((1, INSERTION_COLS), dtype=np.uint64)),
                                                                              *outs), len(tab))
 
+    def deletion_begin(self) -> None:
+        """vga_deletion_begin: from now on every align() of this context appends the deletion events of its reported alignments to
+        the context's store (needs pileup_begin)"""
+        self._check(self.L.vga_deletion_begin(self.h))
+
+    def deletions(self):
+        """vga_deletion_read -> (events[n_events, 3] uint32: first, len, last, in the order of the reported alignments and along
+        each; n_alignments, n_end_runs); does not reset"""
+        n, ev, ends = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.vga_deletion_read(self.h, None, C.byref(n), C.byref(ev), C.byref(ends)))
+        events = np.zeros((max(1, int(ev.value)), DELETION_EVENT_WORDS), dtype=np.uint32)
+        self._check(self.L.vga_deletion_read(self.h, _u32p(events), C.byref(n), C.byref(ev), C.byref(ends)))
+        return events[:int(ev.value)], int(n.value), int(ends.value)
+
+    def deletion_reset(self) -> None:
+        """vga_deletion_reset: empty the store, keep storing"""
+        self._check(self.L.vga_deletion_reset(self.h))
+
+    def deletion_end(self) -> None:
+        """vga_deletion_end: free the store, stop storing"""
+        self._check(self.L.vga_deletion_end(self.h))
+
+    def _deletion(self, call, cap, ask_again) -> dict:
+        """`call(cap, *outs)` is one of the two C calls with everything before cap bound: asks again with a larger cap when the
+        first answer holds more calls than it had room for (ask_again False: returns the first min(n_calls, cap) calls)"""
+        cap = max(0, int(cap))
+        while True:
+            m = max(1, cap)
+            first, length, last, qual = (np.zeros(m, dtype=np.uint32) for _ in range(4))
+            state, depth, reads = np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+            nd, nc = C.c_uint64(0), C.c_uint64(0)
+            self._check(call(cap, _u32p(first), _u32p(length), _u32p(last), state.ctypes.data_as(_P(C.c_uint8)), _u32p(qual), _u64p(depth), _u64p(reads),
+                             C.byref(nd), C.byref(nc)))
+            n = int(nc.value)
+            if n <= cap or not ask_again:
+                break
+            cap = n
+        k = min(n, cap)
+        return {"first": first[:k], "len": length[:k], "last": last[:k], "state": state[:k], "qual": qual[:k], "depth": depth[:k], "reads": reads[:k],
+                "n_distinct": int(nd.value), "n_calls": n}
+
+    def deletion_call(self, error: int = VARIANT_ERROR, min_depth: int = VARIANT_MIN_DEPTH, min_qual: int = VARIANT_MIN_QUAL, cap: int = 1024,
+                      ask_again: bool = True) -> dict:
+        """vga_deletion_call: the events of this context's store sorted, grouped and called against its pileup counters (needs
+        pileup_begin and deletion_begin; does not reset) -> {first, len, last, state (0 none, 1 het, 2 hom), qual, depth, reads:
+        arrays over the reported groups in the order of (first, len, last); n_distinct, n_calls}.  cap: the calls the first request
+        has room for."""
+        return self._deletion(lambda c, *outs: self.L.vga_deletion_call(self.h, int(error), int(min_depth), int(min_qual), c, *outs), cap, ask_again)
+
+    def deletion_call_table(self, events, counts, error: int = VARIANT_ERROR, min_depth: int = VARIANT_MIN_DEPTH, min_qual: int = VARIANT_MIN_QUAL,
+                            cap: int = 1024, ask_again: bool = True) -> dict:
+        """vga_deletion_call_table, the kernel seam: the same call from explicit events[n, 3] (uint32) and an explicit pileup table
+        counts[n_bases, 7] (uint64).  Needs a context only."""
+        ev = np.ascontiguousarray(events, dtype=np.uint32).reshape(-1, DELETION_EVENT_WORDS)
+        tab = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1, len(PILEUP_COLUMNS))
+        evp = _u32p(ev if len(ev) else np.zeros((1, DELETION_EVENT_WORDS), dtype=np.uint32))
+        tabp = _u64p(tab if len(tab) else np.zeros((1, len(PILEUP_COLUMNS)), dtype=np.uint64))
+        return self._deletion(lambda c, *outs: self.L.vga_deletion_call_table(self.h, len(ev), evp, len(tab), tabp, int(error), int(min_depth), int(min_qual),
+                                                                             c, *outs), cap, ask_again)
+
     def phase_begin(self) -> None:
         """vga_phase_begin: from now on every align() of this context keeps the pileup lists of its reported alignments (needs
         pileup_begin)"""
@@ -1582,3 +1663,10 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def deletion_state(reads: int, depth: int, error: int = VARIANT_ERROR):
+    """vga_deletion_state: the rule of the deletion call alone -> (state: 0 none, 1 het, 2 hom; qual)"""
+    q = C.c_uint32(0)
+    state = load_library().vga_deletion_state(int(reads), int(depth), int(error), C.byref(q))
+    return int(state), int(q.value)

@@ -38,6 +38,7 @@ struct cov_state;
 struct ps_state;
 struct pu_state;
 struct ia_state;
+struct dl_state;
 struct ph_state;
 struct poa_ws;
 
@@ -85,6 +86,9 @@ struct vga_dev_index {
     // the table of inserted lengths and letters of this index while it is counted (vga_insertion.hip), with event lists of its own:
     // released with the index
     vga_owned<ia_state> ia{nullptr, nullptr};
+    // the store of deletion events of this index while it is kept (vga_deletion.hip), with event lists of its own: released with the
+    // index, and with the pileup
+    vga_owned<dl_state> dl{nullptr, nullptr};
     // the store of the winners' pileup lists while the phase store is on (vga_phase.hip): released with the index, and with the pileup
     vga_owned<ph_state> ph{nullptr, nullptr};
 };

@@ -159,6 +159,7 @@ void vga_index_release(vga_dev_index &ix)
     ix.ps.reset();   // (and so does path support)
     ix.pu.reset();   // (and the pileup)
     ix.ia.reset();   // (and the insertion table)
+    ix.dl.reset();   // (and the store of deletion events)
     ix.ph.reset();   // (and the phase store)
     ix = vga_dev_index();
 }

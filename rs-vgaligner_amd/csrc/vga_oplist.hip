@@ -1,12 +1,13 @@
 // vga_oplist.hip -- the table of the list makers and the part of their host frame that is no template (vga_oplist.hpp).
 #include "vga_coverage.hpp"
+#include "vga_deletion.hpp"
 #include "vga_insertion.hpp"
 #include "vga_pileup.hpp"
 
 // in the order in which vga_align_batch counts the winners
-const std::array<const oplist_maker *, 3> &oplist_makers()
+const std::array<const oplist_maker *, 4> &oplist_makers()
 {
-    static const std::array<const oplist_maker *, 3> table = {&cov_maker(), &pu_maker(), &ia_maker()};
+    static const std::array<const oplist_maker *, 4> table = {&cov_maker(), &pu_maker(), &ia_maker(), &dl_maker()};
     return table;
 }
 

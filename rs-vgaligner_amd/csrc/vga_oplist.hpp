@@ -1,5 +1,5 @@
-// vga_oplist.hpp -- what the three list makers share: coverage's k_cov_runs (vga_coverage.hip), the pileup's k_pu_events
-// (vga_pileup.hip) and the insertion table's k_ia_events (vga_insertion.hip) condense the traceback of every finished problem into
+// vga_oplist.hpp -- what the four list makers share: coverage's k_cov_runs (vga_coverage.hip), the pileup's k_pu_events
+// (vga_pileup.hip), the insertion table's k_ia_events (vga_insertion.hip) and the deletion store's k_dl_events (vga_deletion.hip) condense the traceback of every finished problem into
 // a short list, and the winners' lists are counted once the host has picked them.  Here is the one copy of the walk over the
 // operations (device, and host for a list that found no room), of the record of a list, of the per-call store of lists and of the
 // host frame of a maker: the base of its state, the enqueue of its list kernel, the add of the staged winners, its begin / reset /
@@ -26,7 +26,8 @@
 struct oplist_rec {
     uint32_t off, n_a, n_b;
     uint32_t flags;  // low two bits: 0 nothing (the problem has no alignment yet), 1 in the call's device buffer, 2 no room there,
-                     // 3 built by the host; bit 2 (pileup and insertion table): the alignment starts with an insertion (it belongs to no base)
+                     // 3 built by the host; bit 2 (pileup and insertion table): the alignment starts with an insertion (it belongs to no base);
+                     // from bit 2 up (deletion store): the number of end runs of the record
 };
 #define PU_LEADING 4u
 
@@ -228,7 +229,7 @@ struct oplist_call {
     // start of a poa_run call of n problems whose queries hold total_q bases: the buffer of lists is sized (cap_words caps it when
     // has_cap) and its cursor zeroed.  About a word per read base is what coverage needs on a graph of short nodes with reads of
     // 10 % errors, the pileup 0.4.  Not a bound -- a problem that finds no room says so and the host builds its list
-    // (VGA_COV_LIST_WORDS, VGA_PILEUP_LIST_WORDS and VGA_INS_LIST_WORDS cap the buffers: the tests force that route with them)
+    // (VGA_COV_LIST_WORDS, VGA_PILEUP_LIST_WORDS, VGA_INS_LIST_WORDS and VGA_DEL_LIST_WORDS cap the buffers: the tests force that route with them)
     int begin(vga_ctx *ctx, uint64_t n, uint64_t total_q, bool has_cap, uint64_t cap_words)
     {
         uint64_t words = std::min<uint64_t>(total_q + 256ull * n + 4096ull, 0xFFFFFF00ull);
@@ -351,7 +352,7 @@ struct oplist_launch {
 // a buffer of a maker's 32-bit counters: begin reserves `words`, begin and reset zero them unless the buffer is scratch of its read
 struct oplist_counter { vga_dbuf<uint32_t> *buf; size_t words; bool zeroed; };
 
-// One per maker, handed out by a function of its .hip (cov_maker(), pu_maker(), ia_maker(): a constant at namespace scope would be
+// One per maker, handed out by a function of its .hip (cov_maker(), pu_maker(), ia_maker(), dl_maker(): a constant at namespace scope would be
 // emitted for the device too, where its hooks do not exist); oplist_makers() (vga_oplist.hip) is the table poa_run and
 // vga_align_batch walk, in the order in which the winners are counted.  The frame below calls the hooks.
 struct oplist_maker {
@@ -368,7 +369,7 @@ struct oplist_maker {
     std::vector<oplist_counter> (*counters)(const vga_dev_index &ix, oplist_state *s);  // its device counters for this index (seq_length is set)
     void (*zero_own)(oplist_state *s);                            // its own host counters start again (null: it has none)
 };
-const std::array<const oplist_maker *, 3> &oplist_makers();
+const std::array<const oplist_maker *, 4> &oplist_makers();
 
 // vga_<name>_begin / _reset / _end for the entry point fn (its __func__)
 int oplist_begin(vga_ctx *ctx, const oplist_maker &m, const char *fn);

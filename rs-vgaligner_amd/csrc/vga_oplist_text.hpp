@@ -14,6 +14,7 @@ struct oplist_text {
 };
 static const oplist_text OPLIST_TEXT_COV = {"coverage", "coverage", "run", "run list", "coverage", "read coverage is not counted", "32-bit"};
 static const oplist_text OPLIST_TEXT_PU = {"pileup", "pileup", "event", "pileup list", "pileup", "the pileup is not counted", "29-bit"};
+static const oplist_text OPLIST_TEXT_DL = {"deletion", "deletions", "deletion", "deletion list", "deletions", "the deletion events are not kept", "29-bit"};
 static const oplist_text OPLIST_TEXT_IA = {"insertion", "insertions", "insertion", "insertion list", "insertions", "the inserted letters are not counted", "26-bit"};
 #define OPLIST_REFUSAL_PATHS "path support is not scored"  // (no maker: it reads coverage's lists, and is refused and scored right behind coverage)
 

@@ -191,7 +191,8 @@ const oplist_maker &pu_maker()
         pu_add,
         [](const vga_dev_index &ix) { return ix.seq_length < PU_MAX_SEQ && ix.n_nodes < (1ull << 31); },
         [](vga_ctx *ctx, const char *fn) { return oplist_make(ctx, ctx->index.pu, fn); },
-        [](vga_ctx *ctx) { ctx->index.ph.reset(); ctx->index.pu.reset(); },  // (the phase store keeps the pileup's lists: it ends with it)
+        // (the phase store keeps the pileup's lists and the deletion call takes its depth from the table: they end with it)
+        [](vga_ctx *ctx) { ctx->index.ph.reset(); ctx->index.dl.reset(); ctx->index.pu.reset(); },
         pu_counters,
         [](oplist_state *s) { static_cast<pu_state *>(s)->leading_ins = 0; },
     };

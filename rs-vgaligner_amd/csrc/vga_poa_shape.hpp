@@ -78,10 +78,11 @@ struct poa_switches {
     bool text_memcpy = false; // VGA_POA_TEXT_MEMCPY: the device text comes back by hipMemcpy, not by the copy kernel
     bool has_text_arena = false;
     uint64_t text_arena = 0;  // VGA_POA_TEXT_ARENA: caps the text arena (the overflow path)
-    bool has_cov_words = false, has_pileup_words = false, has_ins_words = false;
+    bool has_cov_words = false, has_pileup_words = false, has_ins_words = false, has_del_words = false;
     uint64_t cov_words = 0;     // VGA_COV_LIST_WORDS: caps the buffer of run lists (the no-room route; 0: every problem takes it)
     uint64_t pileup_words = 0;  // VGA_PILEUP_LIST_WORDS: the same for the pileup lists
     uint64_t ins_words = 0;     // VGA_INS_LIST_WORDS: the same for the insertion lists
+    uint64_t del_words = 0;     // VGA_DEL_LIST_WORDS: the same for the deletion lists
     bool has_dump_rows = false;
     std::string dump_rows;    // VGA_POA_DUMP_ROWS: file for the row records of every launch's first problem
     bool has_pool_fraction = false, has_pool_bytes = false, has_pool_seg = false;
@@ -125,6 +126,7 @@ static inline poa_switches poa_read_switches()
     if (const char *e = getenv("VGA_COV_LIST_WORDS")) { s.has_cov_words = true; s.cov_words = (uint64_t)std::max(0ll, atoll(e)); }
     u64("VGA_PILEUP_LIST_WORDS", s.has_pileup_words, s.pileup_words);
     u64("VGA_INS_LIST_WORDS", s.has_ins_words, s.ins_words);
+    u64("VGA_DEL_LIST_WORDS", s.has_del_words, s.del_words);
     if (const char *e = getenv("VGA_POA_DUMP_ROWS")) { s.has_dump_rows = true; s.dump_rows = e; }
     if (const char *e = getenv("VGA_POOL_FRACTION")) { s.has_pool_fraction = true; s.pool_fraction = atof(e); }
     u64("VGA_POOL_BYTES", s.has_pool_bytes, s.pool_bytes);

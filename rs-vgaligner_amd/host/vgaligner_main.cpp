@@ -67,6 +67,9 @@ const Flag MAP_FLAGS[] = {{"-i", "--index", true, "index"}, {"-f", "--input-file
                           // not in the reference: length and letters of what the reads insert at the sites --call-variants reports
                           // with an insertion, counted and called on the GPU (one TSV file)
                           {"", "--call-insertions", false, "call-insertions"},
+                          // not in the reference (needs --call-variants): every run of deleted graph bases as one event, sorted, counted and
+                          // called on the GPU (one TSV file)
+                          {"", "--call-deletions", false, "call-deletions"},
                           // not in the reference: the read-backed links between the heterozygous sites --call-variants reports,
                           // counted on the GPU, and the phase chain on them (one TSV file); --phase-min-links N: the reads by which
                           // cis and trans must differ for a link to join two sites (2, 1..65535)
@@ -240,6 +243,9 @@ int map_main(int argc, char **argv)
     o.call_insertions = m.count("call-insertions") > 0;
     if (o.call_insertions && !o.also_align) throw Error("--call-insertions calls from alignments: it needs --also-align");
     if (o.call_insertions && !o.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
+    o.call_deletions = m.count("call-deletions") > 0;
+    if (o.call_deletions && !o.also_align) throw Error("--call-deletions calls from alignments: it needs --also-align");
+    if (o.call_deletions && !o.call_variants) throw Error("--call-deletions calls with the depth and the parameters of --call-variants: it needs --call-variants");
     o.phase = m.count("phase") > 0;
     if (o.phase && !o.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
     if (m.count("phase-min-links")) {
@@ -379,6 +385,10 @@ int map_main(int argc, char **argv)
                 (unsigned long long)out.n_leading_ins);
     if (o.call_variants)
         fprintf(stderr, "[vgaligner] call-variants: %llu bases tested, %llu calls\n", (unsigned long long)out.n_variant_tested, (unsigned long long)out.n_variant_calls);
+    if (o.call_deletions)
+        fprintf(stderr, "[vgaligner] call-deletions: %llu runs of %llu alignments, %llu at an end, %llu distinct, %llu calls\n", (unsigned long long)out.n_deletion_runs,
+                (unsigned long long)out.n_deletion_alignments, (unsigned long long)out.n_deletion_end_runs, (unsigned long long)out.n_deletion_distinct,
+                (unsigned long long)out.n_deletion_calls);
     if (o.call_insertions)
         fprintf(stderr, "[vgaligner] call-insertions: %llu sites, %llu longer than 8\n", (unsigned long long)out.n_insertion_sites, (unsigned long long)out.n_insertion_long);
     if (o.phase)
@@ -455,7 +465,7 @@ int main(int argc, char **argv)
                         "                [--genotype-likelihood [--genotype-lambda 512] [--genotype-cap 64] [--genotype-top 20]\n"
                         "                                       [--genotype-from support|edit]]\n"
                         "                [--path-edit]\n"
-                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions]\n"
+                        "                [--call-variants [--call-error 1280] [--call-min-depth 4] [--call-min-qual 512] [--call-insertions] [--call-deletions]\n"
                         "                                 [--phase [--phase-min-links 2] [--haplotag]]]\n"
                         "                                 (with --haplotag: [--haplotype-calls])\n"
                         "                                 (with --phase: [--phase-join [--phase-join-min-reads 2]])\n"

@@ -204,6 +204,11 @@ struct MapOptions {
     // whole table over, 196 bytes per base and context over PCIe, they are added in 64 bits, then vga_insertion_call_table on the
     // first with the summed rows of the sites), and write <out>-insertions.tsv
     bool call_insertions = false;
+    // --call-deletions (not in the reference; needs call_variants): keep, on the GPU, every run of deleted graph bases of the
+    // reported alignments as one event (vga_deletion_begin), sort, group and call the events against the pileup's depth with the
+    // parameters of --call-variants (vga_deletion_call; several contexts: each hands its store over, 12 bytes per event, and the
+    // first calls once on the summed pileup table with vga_deletion_call_table), and write <out>-deletions.tsv
+    bool call_deletions = false;
     // --phase [--phase-min-links N] (not in the reference; needs call_variants): keep, on the GPU, the pileup list of every
     // reported alignment (vga_phase_begin), count the read-backed links between the heterozygous sites of <out>-variants.tsv up to
     // eight sites apart (vga_phase_links; several contexts: each hands its whole store over PCIe, the stores are concatenated,
@@ -270,6 +275,8 @@ struct MapOutput {
     std::string hap_path_call;
     uint64_t n_join_sets = 0, n_joins = 0, n_join_agree = 0, n_join_conflict = 0;  // chain sets, accepted links, links inside a component (MapOptions::phase_join)
     uint64_t n_hapcall_jobs = 0, n_hapcall_rows = 0, n_hapcall_differ = 0;  // jobs, lines written, lines whose two decided calls differ (MapOptions::haplotype_calls)
+    // runs of deleted bases, the alignments they come from, those at an end of an alignment, distinct events, calls (MapOptions::call_deletions)
+    uint64_t n_deletion_runs = 0, n_deletion_alignments = 0, n_deletion_end_runs = 0, n_deletion_distinct = 0, n_deletion_calls = 0;
     uint64_t n_insertion_sites = 0, n_insertion_long = 0;  // sites called and those longer than 8 letters (MapOptions::call_insertions)
     uint64_t n_coverage = 0;             // alignments counted into the coverage tables (MapOptions::coverage)
     uint64_t n_edit_alignments = 0, n_edit_too_long = 0;  // alignments seen by the edit distance, and those whose read it does not serve (MapOptions::path_edit)

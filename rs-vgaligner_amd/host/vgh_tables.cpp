@@ -1,6 +1,7 @@
 // vgh_tables.cpp -- the analysis tables of map_reads / map_reads_multi (vgh_tables.hpp): reading them from a context, adding them
 // over the contexts, the two rankings and the TSV files.  Nothing of this is in the reference.
 #include "vgh_tables.hpp"
+#include "../csrc/vga_deletion.hpp"
 #include "../csrc/vga_insertion.hpp"
 #include "../csrc/vga_pair_index.hpp"
 #include "../csrc/vga_phase.hpp"
@@ -209,6 +210,45 @@ void variant_write(const Index &ix, const VariantCalls &v, const std::string &ou
         t += '\n';
     }
     write_file(out_prefix + "-variants.tsv", t);
+}
+
+// `call(cap, first, len, last, state, qual, depth, reads, &n_distinct, &n_calls)` is one of the two library calls with everything
+// before cap bound: asked again when the first answer holds more calls than it had room for
+template <typename F>
+void deletion_fetch(vga_ctx *ctx, DeletionCalls &d, F call)
+{
+    uint64_t cap = 4096;
+    for (;;) {
+        d.first.resize(cap); d.len.resize(cap); d.last.resize(cap); d.qual.resize(cap); d.state.resize(cap); d.depth.resize(cap); d.reads.resize(cap);
+        check(ctx, call(cap, d.first.data(), d.len.data(), d.last.data(), d.state.data(), d.qual.data(), d.depth.data(), d.reads.data(), &d.n_distinct, &d.n_calls));
+        if (d.n_calls <= cap) break;
+        cap = d.n_calls;
+    }
+}
+
+// <out>-deletions.tsv: one line per reported group, in sort order
+void deletion_write(const Index &ix, const DeletionCalls &d, MapOutput &out, const std::string &out_prefix)
+{
+    out.n_deletion_runs = d.n_events + d.n_end_runs; out.n_deletion_alignments = d.n_alignments; out.n_deletion_end_runs = d.n_end_runs;
+    out.n_deletion_distinct = d.n_distinct; out.n_deletion_calls = d.n_calls;
+    if (out_prefix.empty()) return;
+    std::string t = "node\toffset\tend_node\tend_offset\tlength\tstate\tqual\tdepth\treads\n";
+    auto node_of = [&](uint64_t pos) {  // the 1-based id of the node that holds the base: the last whose start is not behind it
+        uint64_t lo = 1, hi = ix.n_nodes + 1;
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) / 2;
+            if (ix.node_ref[mid - 1].seq_idx <= pos) lo = mid; else hi = mid;
+        }
+        return lo;
+    };
+    for (uint64_t i = 0; i < d.n_calls; i++) {
+        const uint64_t a = node_of(d.first[i]), b = node_of(d.last[i]);
+        put_u64(t, a); t += '\t'; put_u64(t, d.first[i] - ix.node_ref[a - 1].seq_idx); t += '\t';
+        put_u64(t, b); t += '\t'; put_u64(t, d.last[i] - ix.node_ref[b - 1].seq_idx); t += '\t';
+        put_u64(t, d.len[i]); t += '\t'; t += dl_state_name(d.state[i]); t += '\t'; put_u64(t, d.qual[i]); t += '\t';
+        put_u64(t, d.depth[i]); t += '\t'; put_u64(t, d.reads[i]); t += '\n';
+    }
+    write_file(out_prefix + "-deletions.tsv", t);
 }
 
 // one line per called site: where it is and what the variant call says of it, then length (1 .. 8, or >8), the reads of that
@@ -535,6 +575,8 @@ void check_aligner(const MapOptions &opt)
     if (opt.call_variants && !opt.also_align) throw Error("--call-variants calls from alignments: it needs --also-align");
     if (opt.call_variants && !variant_params_ok(opt)) throw Error("--call-variants: --call-error is 257 to 8192 and --call-min-depth at least 1");
     if (opt.call_insertions && !opt.call_variants) throw Error("--call-insertions calls at the sites of --call-variants: it needs --call-variants");
+    if (opt.call_deletions && !opt.also_align) throw Error("--call-deletions calls from alignments: it needs --also-align");
+    if (opt.call_deletions && !opt.call_variants) throw Error("--call-deletions calls with the depth and the parameters of --call-variants: it needs --call-variants");
     if (opt.phase && !opt.call_variants) throw Error("--phase links the heterozygous sites of --call-variants: it needs --call-variants");
     if (opt.phase && (opt.phase_min_links < 1 || opt.phase_min_links > PH_MIN_LINKS_MAX)) throw Error("--phase-min-links is 1 to 65535");
     if (opt.haplotag && !opt.phase) throw Error("--haplotag assigns reads to the haplotypes of the phase sets of --phase: it needs --phase");
@@ -572,6 +614,7 @@ void Tables::begin(vga_ctx *ctx) const
     }
     if (piling()) check(ctx, vga_pileup_begin(ctx));
     if (inserting()) check(ctx, vga_insertion_begin(ctx));
+    if (deleting()) check(ctx, vga_deletion_begin(ctx));
     if (phasing()) check(ctx, vga_phase_begin(ctx));
     if (hap_typing()) check(ctx, vga_haplotype_paths_begin(ctx, opt_.haplotype_paths_cap, opt_.haplotype_paths_from_edit ? VGA_HP_FROM_EDIT : VGA_HP_FROM_SUPPORT));
 }
@@ -680,6 +723,22 @@ void Tables::take(vga_ctx *ctx, uint32_t slot, bool call_now)
         t.v = {widen(c, ix_.seq_length * IA_COLS)};
         insertions_.add(t);
     }
+    if (deleting()) {
+        DeletionCalls &d = deletions_;
+        check(ctx, vga_deletion_read(ctx, nullptr, &d.n_alignments, &d.n_events, &d.n_end_runs));
+        if (call_now) {  // from the context's own store and counters
+            deletion_fetch(ctx, d, [&](uint64_t cap, uint32_t *first, uint32_t *len, uint32_t *last, uint8_t *state, uint32_t *qual, uint64_t *depth, uint64_t *reads,
+                                       uint64_t *nd, uint64_t *nc) {
+                return vga_deletion_call(ctx, opt_.call_error, opt_.call_min_depth, opt_.call_min_qual, cap, first, len, last, state, qual, depth, reads, nd, nc);
+            });
+        } else {  // the whole store for the call on the summed table: 12 bytes per event
+            uint64_t n_events = 0;
+            d.events.assign(d.n_events * DL_EVENT_WORDS + 1, 0);
+            check(ctx, vga_deletion_read(ctx, d.events.data(), nullptr, &n_events, nullptr));
+            if (n_events != d.n_events) throw Error("--call-deletions: the store of slot " + std::to_string(slot) + " changed while it was read");
+            d.events.resize(n_events * DL_EVENT_WORDS);
+        }
+    }
     if (phasing() && call_now) {  // the heterozygous sites of the calls just made, from the context's own store
         phase_sites();
         PhaseLinks &p = phase_;
@@ -747,6 +806,7 @@ void Tables::end(vga_ctx *ctx) const
     if (scoring()) (void)vga_path_support_end(ctx);  // (and genotyping, the edit distance and the store of the path abundance with it)
     if (hap_typing()) (void)vga_haplotype_paths_end(ctx);
     if (phasing()) (void)vga_phase_end(ctx);
+    if (deleting()) (void)vga_deletion_end(ctx);
     if (piling()) (void)vga_pileup_end(ctx);
     if (inserting()) (void)vga_insertion_end(ctx);
 }
@@ -760,6 +820,8 @@ void Tables::add(const Tables &o)
     edit_.add(o.edit_);
     pileup_.add(o.pileup_);
     insertions_.add(o.insertions_);
+    deletions_.events.insert(deletions_.events.end(), o.deletions_.events.begin(), o.deletions_.events.end());  // (the call does not depend on the order)
+    deletions_.n_alignments += o.deletions_.n_alignments; deletions_.n_events += o.deletions_.n_events; deletions_.n_end_runs += o.deletions_.n_end_runs;
     phase_store_.add(o.phase_store_);
     hap_paths_.deficits.insert(hap_paths_.deficits.end(), o.hap_paths_.deficits.begin(), o.hap_paths_.deficits.end());  // (in the order of the records)
     hap_paths_.scored.insert(hap_paths_.scored.end(), o.hap_paths_.scored.begin(), o.hap_paths_.scored.end());
@@ -815,6 +877,18 @@ void Tables::call(vga_ctx *ctx)
                                       pos, gt, qual, iq, depth, counts, nt, nc);
     });
     trace_mark("variants called");
+    if (deleting()) {  // the concatenated stores against the summed pileup table
+        DeletionCalls &d = deletions_;
+        if (d.events.size() != d.n_events * DL_EVENT_WORDS)
+            throw Error("--call-deletions: the contexts kept " + std::to_string(d.n_events) + " events and handed over " + std::to_string(d.events.size() / DL_EVENT_WORDS));
+        d.events.push_back(0);  // (never a null array)
+        deletion_fetch(ctx, d, [&](uint64_t cap, uint32_t *first, uint32_t *len, uint32_t *last, uint8_t *state, uint32_t *qual, uint64_t *depth, uint64_t *reads,
+                                   uint64_t *nd, uint64_t *nc) {
+            return vga_deletion_call_table(ctx, d.n_events, d.events.data(), ix_.seq_length, pileup_.v[0].data(), opt_.call_error, opt_.call_min_depth,
+                                           opt_.call_min_qual, cap, first, len, last, state, qual, depth, reads, nd, nc);
+        });
+        trace_mark("deletions called");
+    }
     if (phasing()) {
         phase_sites();
         PhaseLinks &p = phase_;
@@ -946,6 +1020,10 @@ void Tables::write(MapOutput &out, const ReadRows &rows, const std::string &out_
     if (inserting()) {
         insertion_write(ix_, variants_, ins_calls_, out, out_prefix);
         trace_mark("insertions written");
+    }
+    if (deleting()) {
+        deletion_write(ix_, deletions_, out, out_prefix);
+        trace_mark("deletions written");
     }
     if (opt_.pileup) {
         pileup_.pad({ix_.seq_length * 7});

@@ -1,5 +1,5 @@
 // vgh_tables.hpp -- the per-run analysis tables of `vgaligner map` (--coverage, --path-support, --pileup, --genotype,
-// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --phase, --haplotag, --haplotype-calls, --phase-join, --haplotype-paths, --path-abundance): what a context has counted and scored, added over the contexts in 64 bits,
+// --genotype-likelihood, --path-edit, --call-variants, --call-insertions, --call-deletions, --phase, --haplotag, --haplotype-calls, --phase-join, --haplotype-paths, --path-abundance): what a context has counted and scored, added over the contexts in 64 bits,
 // and the TSV files.  Internal to the host library: map_chunk, map_reads and map_reads_multi (vgh_map.cpp) drive one Tables per
 // context through begin .. write and know nothing of the single analyses.
 #pragma once
@@ -42,6 +42,17 @@ struct InsertionCalls {
     std::vector<uint64_t> site;  // index into the variant calls
     std::vector<uint8_t> length, seq;            // seq: 8 per site
     std::vector<uint64_t> length_reads, seq_reads;  // seq_reads: 8 per site
+};
+
+// The deletion events (MapOptions::call_deletions): three words per event, of this context's store or of the concatenated stores
+// (kept only for the route of several contexts; the counts are kept either way), and the calls in sort order
+struct DeletionCalls {
+    std::vector<uint32_t> events;
+    uint64_t n_alignments = 0, n_events = 0, n_end_runs = 0;
+    std::vector<uint32_t> first, len, last, qual;
+    std::vector<uint8_t> state;
+    std::vector<uint64_t> depth, reads;
+    uint64_t n_distinct = 0, n_calls = 0;
 };
 
 // The heterozygous sites of VariantCalls in that order, and their links (MapOptions::phase)
@@ -127,6 +138,7 @@ public:
                               (opt_.path_abundance && opt_.abundance_from_edit); }
     bool piling() const { return opt_.pileup || opt_.call_variants; }
     bool inserting() const { return opt_.call_insertions; }
+    bool deleting() const { return opt_.call_deletions; }
     bool phasing() const { return opt_.phase; }
     bool tagging() const { return opt_.haplotag; }
     bool hap_calling() const { return opt_.haplotype_calls; }
@@ -170,6 +182,7 @@ private:
     VariantCalls variants_;
     Counters insertions_;  // seq_length x 49; n: alignments, leading insertions (only kept for the sum of several contexts)
     InsertionCalls ins_calls_;
+    DeletionCalls deletions_;
     PhaseStore phase_store_;  // (only kept for the route of several contexts)
     PhaseLinks phase_;
     PhaseTags tags_;  // (read_ids: of this context's store, then of the concatenated stores)
